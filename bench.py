@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the DSVGP ELBO training step (BASELINE.json metric) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without a launcher: this process starts ``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a
 child BEFORE anything touches the GPU, relays its output (rank 0 prints the JSON line) and exits with its status; under a
@@ -12,10 +12,19 @@ directionalvi/directional_vi.py:229-254): minibatch gather, fused ELBO forward +
 steps and both LR-scheduler steps.  Workload = BASELINE config 4: d=20, N=1M, M=500, p=5, global
 minibatch 4096 (sharded by rows over the ranks, packed-triangle RCCL all-reduce per step: strong scaling).
 Synthetic data (X ~ U[0,1]^d, y=[f, grad f], f=sin(2 pi |x|^2), reference tests/testfun.py) is resident in
-HBM before the timed region.  Rank 0 prints ONE JSON line with
+HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times K steps and reports `ms_per_step` / `value` (at C4 on one GPU, `ms_per_step` includes
+1/50 of the measured cost of the reference's every-50th-step report, as it always has).  `--dump-outputs DIR` writes what
+the last timed step computed (loss, predictive mean of its minibatch, every model parameter after the optimizer update) as
+DIR/<name>.npy, float32 or float64; arrays of more than 4M entries as a fixed, seeded sample of their flattened entries.
+Data, permutation, derivative columns and initial parameters are seeded: the same arguments give the same inputs every run.
+`--full` adds everything else the line can carry:
   roofline           the dominant kernel (fp64 MFMA panel-solve GEMM), timed live with HIP events on its launch stream;
   roofline_assembly  the HBM-bound kernel assembly forward (K_ZX) and backward (K_ZX-bar), same method (north_star);
-  cpu_baseline       the oracle's reference-op-sequence training step on this host's cores (N = 1 only).
+  cpu_baseline       the oracle's reference-op-sequence training step on this host's cores (N = 1 only);
+  config.*           repeated windows, the split-bf16 second figure, the other BASELINE configurations and the eval
+                     throughput (C4, one GPU, unless --no-extras), the collective probe / host trace / replica check (N > 1).
 """
 import argparse
 import json
@@ -120,6 +129,45 @@ def cpu_baseline(cfg, budget_s=150.0, min_steps=3, fp64=False):
                           st.assembly_seconds / steps))
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 22
+
+
+def step_outputs(loop, loss, output):
+    """What a caller of the timed step receives from its last call, as host arrays: the loss, the predictive mean of the
+    minibatch that the step's forward pass left behind, and every model parameter after the optimizers' update."""
+    import torch
+    arrays = {"loss": loss.detach().reshape(-1)}
+    mu = getattr(output, "_mu", None)
+    if mu is not None:
+        arrays["mean"] = mu.detach().reshape(-1)
+    for name, v in loop.model._param_dict(loop.likelihood).items():
+        arrays["param_" + name] = v.detach()
+    out = {}
+    for name, t in arrays.items():
+        t = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        out[name] = t.contiguous().numpy()
+    return out
+
+
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy per array; an array of more than DUMP_SAMPLE entries is replaced by the entries of its flattened form at a
+    fixed, seeded, sorted set of DUMP_SAMPLE positions (the same positions for the same shape), so two builds compare entry for entry"""
+    import numpy as np
+    cap = DUMP_SAMPLE
+    while True:
+        total = sum(min(a.size, cap) * a.itemsize for a in arrays.values())
+        if total <= DUMP_MAX_BYTES or cap <= 1:
+            break
+        cap //= 2
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -155,7 +203,14 @@ def main():
     ap.add_argument("--event-every", type=int, default=0,
                     help="HIP events (dominant-kernel / assembly timings) on every K-th timed step; 0 = every step, except on the "
                          "sub-millisecond configuration c2 where six event records are 5 %% of the step: every 8th there")
+    ap.add_argument("--full", action="store_true",
+                    help="also the HIP-event kernel timings and rooflines, MFMA-rate probes, repeated windows, split-bf16 figure, other "
+                         "configurations, eval throughput, CPU baseline, and (N > 1) the collective probe, host trace and replica check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = CONFIGS[args.config]
     if args.event_every <= 0:
         args.event_every = 8 if args.config == "c2" else 1
@@ -193,6 +248,9 @@ def main():
     def build(cfg, fp64):
         """dataset + training loop of one configuration, engine switches applied; returns (loop, engine, batch(k))"""
         d, N, M, p, B = cfg["d"], cfg["N"], cfg["M"], cfg["p"], cfg["B"]
+        # the initial jitter of the variational mean draws from torch's global generators, whose seed otherwise differs from
+        # process to process: seeded here, every run of the same command starts from the same inputs
+        torch.manual_seed(0)
         prev = torch.get_default_dtype()
         if fp64:
             torch.set_default_dtype(torch.float64)
@@ -225,27 +283,27 @@ def main():
         eng.pack_reduce = not args.no_pack_reduce
         if loop.dp is not None:
             loop.dp.algo = args.dp_algo
-            # replica check on by default under the bench (every 64 steps; DSVGP_DP_CHECK=N / 0 overrides): the replicas' L_S, m and Adam
-            # moments are never re-broadcast, so the first run on real multi-GPU hardware reports whether they stayed bitwise equal
-            if os.environ.get("DSVGP_DP_CHECK") is None:
+            # replica check on by default under `--full` (every 64 steps; DSVGP_DP_CHECK=N / 0 overrides): the replicas' L_S, m and Adam
+            # moments are never re-broadcast, so the first run on real multi-GPU hardware reports whether they stayed bitwise equal (--full)
+            if os.environ.get("DSVGP_DP_CHECK") is None and args.full:
                 loop.dp.check_every = 64
         perm = loop.epoch_permutation()
         nbatches = N // B
         return loop, eng, (lambda k: perm[(k % nbatches) * B:(k % nbatches + 1) * B])
 
     def window(loop, batch, first, steps):
-        """`steps` optimisation steps bracketed by barrier + synchronize on both sides; returns (seconds, last loss)"""
+        """`steps` optimisation steps bracketed by barrier + synchronize on both sides; returns (seconds, last loss, last output)"""
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for k in range(steps):
-            loss, _, _ = loop.step(batch(first + k))
+            loss, output, _ = loop.step(batch(first + k))
         loop.finish()                    # (graph replay: the status of the last replayed step is read here)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
-        return time.perf_counter() - t0, loss
+        return time.perf_counter() - t0, loss, output
 
     def events_on(eng, every):
         eng.record_events = True
@@ -287,10 +345,13 @@ def main():
 
     for k in range(args.warmup):
         loop.step(batch(k))
-    events_on(eng, args.event_every)
-    if (world > 1 or args.emulate_world > 1) and hasattr(eng, "dp_host_trace"):
+    if args.full:
+        events_on(eng, args.event_every)
+    if args.full and (world > 1 or args.emulate_world > 1) and hasattr(eng, "dp_host_trace"):
         eng.dp_host_trace = []           # host time stamps of the five C calls + collectives of every rank step in the window
-    elapsed, loss = window(loop, batch, args.warmup, args.steps)
+    elapsed, loss, last_output = window(loop, batch, args.warmup, args.steps)
+    dumped = step_outputs(loop, loss, last_output) if args.dump_outputs and rank == 0 else None
+    del last_output
     dp_trace, replica_check = None, None
     if getattr(eng, "dp_host_trace", None):
         tr_ = eng.dp_host_trace
@@ -310,7 +371,7 @@ def main():
                                   "a divergence re-broadcasts rank 0's parameters and Adam moments")
     if hasattr(eng, "record_every"):
         eng.record_every = 1             # (the untimed passes below: every step)
-    if loop._graphs:
+    if args.full and loop._graphs:
         # the timed steps were graph replays (no HIP events inside a graph): the per-kernel timings of the roofline entries
         # come from three more, untimed, eager steps of the same loop
         loop.graph = False
@@ -325,7 +386,7 @@ def main():
     EVENT_NAMES = ("solve_fwd", "assemble_fwd", "assemble_bwd", "gram", "dense", "early_reduce_wait", "final_reduce", "ciq_stacked_backward")
     durations = event_durations(eng, EVENT_NAMES)
     iso_fwd = iso_bwd = None
-    if not cfg.get("ciq") and world == 1 and not args.fp64:
+    if args.full and not cfg.get("ciq") and world == 1 and not args.fp64:
         saved = eng.overlap
         eng.overlap, eng.events = False, []
         if hasattr(eng, "c_step_timed"):
@@ -349,11 +410,13 @@ def main():
     # ---- the same window twice more (box-to-box and run-to-run spread of a 0.3 s timed region is +-3 %): min / median / max of the
     # three, `steps` / `ms_per_step` stay those of the FIRST window
     repeat_ms = None
-    extras = args.config == "c4" and world == 1 and args.emulate_world == 1 and not args.fp64 and not args.no_extras
+    # (the reporting-step cost below is part of the headline ms_per_step; the other extras are --full only)
+    report = args.config == "c4" and world == 1 and args.emulate_world == 1 and not args.fp64 and not args.no_extras
+    extras = report and args.full
     if extras:
         ws_ = [elapsed]
         for r in range(2):
-            e_r, _ = window(loop, batch, args.warmup + args.steps * (r + 1) + 6, args.steps)
+            e_r, _, _ = window(loop, batch, args.warmup + args.steps * (r + 1) + 6, args.steps)
             ws_.append(e_r)
         ws_ = sorted(1e3 * w / args.steps for w in ws_)
         repeat_ms = [ws_[0], ws_[1], ws_[2]]
@@ -364,7 +427,7 @@ def main():
         eng.split_bf16 = True
         for k in range(3):
             loop.step(batch(args.warmup + 3 * args.steps + 20 + k))
-        e_s, loss_s = window(loop, batch, args.warmup + 3 * args.steps + 23, args.steps)
+        e_s, loss_s, _ = window(loop, batch, args.warmup + 3 * args.steps + 23, args.steps)
         eng.split_bf16 = False
         split_fig = dict(ms_per_step=1e3 * e_s / args.steps, steps=args.steps, final_loss=float(loss_s.item()),
                          dtype="f32 model; the Gram product and the dense K_ZX-bar product as six bf16 MFMA products per fp32 product "
@@ -379,7 +442,7 @@ def main():
     # output.mean / output.variance of that forward pass): one reporting step costs a host synchronisation (the step pipeline
     # drains) plus the value-row variances; measured over 5 reporting steps in a row, 1/50 of the extra goes into ms_per_step
     report_extra_ms = None
-    if extras and hasattr(eng, "value_variances"):
+    if report and hasattr(eng, "value_variances"):
         q_ = p + 1
 
         def report_step(k):
@@ -403,7 +466,7 @@ def main():
     # N > 1: what the collectives this design could use cost on THIS node, measured after the timed region (all ranks take part;
     # priced for the next design step: sharding the replicated M' x M' products would add two 72 MB all-gathers per step)
     coll_probe = None
-    if world > 1 and not rehearse and os.environ.get("DSVGP_BENCH_COLL_PROBE", "1") == "1":
+    if args.full and world > 1 and not rehearse and os.environ.get("DSVGP_BENCH_COLL_PROBE", "1") == "1":
         coll_probe = {}
         Mp_ = M * (p + 1)
         for name, fn, numel, dt in (("allreduce_packed_G_ms", "ar", Mp_ * (Mp_ + 1) // 2 + Mp_, torch.float32),
@@ -574,7 +637,7 @@ def main():
 
         return roof, roof_asm
 
-    roof, roof_asm = rooflines(cfg, eng, durations, iso_fwd, args.fp64, args.config, True, iso_bwd)
+    roof, roof_asm = rooflines(cfg, eng, durations, iso_fwd, args.fp64, args.config, True, iso_bwd) if args.full else (None, None)
     Mp = M * (p + 1)
     hl = (eng.trsm_nb, eng.lib_dense_gemm, bool(getattr(eng, "c_step_used", False)), getattr(eng, "pack_reduce", None),
           int(getattr(eng, "early_wire_numel", 0) or 0))
@@ -586,7 +649,7 @@ def main():
         for k in range(warm_):
             loop_o.step(batch_o(k))
         events_on(eng_o, 8 if name == "c2" else 1)
-        e_o, loss_o = window(loop_o, batch_o, warm_, steps_)
+        e_o, loss_o, _ = window(loop_o, batch_o, warm_, steps_)
         eng_o.record_events = False
         roof_o, asm_o = rooflines(cfg_o, eng_o, event_durations(eng_o, EVENT_NAMES), None, fp64_, name, False)
         res = dict(workload=cfg_o["name"] + (" (float64 model mode)" if fp64_ else ""), steps=steps_, warmup=warm_,
@@ -716,7 +779,7 @@ def main():
                        "graph_replay": graph_replay,
                        "one_call_step": c_used_,
                        "kernel_events": "HIP events around the roofline kernels on every %s timed step" % (
-                           "single" if args.event_every == 1 else "%d-th" % args.event_every),
+                           "single" if args.event_every == 1 else "%d-th" % args.event_every) if args.full else None,
                        "dense_product": "rocBLAS sgemm" if lib_dense_ else "hand-written (gemm32.hip, v_mfma_f32_32x32x2_f32)",
                        "timed_window_ms_per_step": 1e3 * elapsed / args.steps,
                        "reporting_step_extra_ms": report_extra_ms,
@@ -765,8 +828,10 @@ def main():
             out["config"]["host_us_per_rank_step"] = dp_trace
         if cfg.get("ciq"):
             out["config"]["ciq"] = ciq_stats
-        if world == 1 and not args.no_cpu_baseline and not cfg.get("ciq"):
+        if args.full and world == 1 and not args.no_cpu_baseline and not cfg.get("ciq"):
             out["cpu_baseline"] = cpu_baseline(cfg, fp64=args.fp64)
+        if dumped is not None:
+            dump_outputs(dumped, args.dump_outputs)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

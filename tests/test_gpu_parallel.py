@@ -445,7 +445,7 @@ def test_bench_line_of_a_four_rank_rehearsal(gpu_device):
 def test_bench_self_launch_of_a_four_rank_rehearsal(gpu_device):
     """`python bench.py --gpus 4` from a plain invocation: bench.py starts ONE child launcher (`torch.distributed.run --standalone`)
     before anything in that process touches the GPU, relays its output and exits with its status -- rehearsed on one card over gloo.
-    The line must carry what the first run on real multi-GPU hardware is to report: the replica check (on by default under the bench,
+    The line must carry what the first run on real multi-GPU hardware is to report: the replica check (on by default under `bench.py --full`,
     no divergence), the host time of a rank step phase by phase, and the collective block."""
     import json
     import subprocess
@@ -453,7 +453,7 @@ def test_bench_self_launch_of_a_four_rank_rehearsal(gpu_device):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DSVGP_DP_CHECK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--config", "c4", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-extras"]
+           "--no-cpu-baseline", "--no-extras", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=540)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]

@@ -22,7 +22,8 @@ def make_ngd_problem(N, d, M, p, B, seed=0, dtype=torch.float32):
     P = O.init_natural_params(X[:M].clone(), V, dtype, mean_init_std=0.2, generator=g)
     Mp = M * (p + 1)
     R = 0.15 * torch.randn(Mp, Mp, generator=g)
-    P["natural_mat"] = (-0.5 * (torch.eye(Mp) + R @ R.t())).to(dtype)      # generic SPD precision
+    RRt = R @ R.t()                          # (not bitwise symmetric on every CPU's sgemm kernel: symmetrised exactly below)
+    P["natural_mat"] = (-0.5 * (torch.eye(Mp) + 0.5 * (RRt + RRt.t()))).to(dtype)      # generic SPD precision
     P["constant"] = torch.tensor([0.1], dtype=dtype)
     P["raw_outputscale"] = torch.tensor(0.2, dtype=dtype)
     P["raw_lengthscale"] = torch.tensor([[0.3]], dtype=dtype)

@@ -31,7 +31,7 @@ for m in list(sys.modules.values()):
         m.lib = w
 cfg = sys.argv[1] if len(sys.argv) > 1 else "c2"
 steps = 300
-sys.argv = ["bench.py", "--config", cfg, "--steps", str(steps), "--warmup", "20", "--no-cpu-baseline", "--no-extras"]
+sys.argv = ["bench.py", "--config", cfg, "--steps", str(steps), "--warmup", "20", "--no-cpu-baseline", "--no-extras", "--full"]
 try:
     runpy.run_path(os.path.join(ROOT, "bench.py"), run_name="__main__")
 except SystemExit:

@@ -7,7 +7,7 @@ python -m pytest tests/test_gpu_step.py -x -q -m gpu -k "stated or statement" -r
 grep "parity\|passed\|failed" $O/tests4.txt | tail -25
 python -m pytest tests/test_gpu_step.py tests/test_gpu_train.py -x -q -m gpu > $O/tests5.txt 2>&1 || { tail -40 $O/tests5.txt; exit 1; }
 tail -2 $O/tests5.txt
-python bench.py > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 python - <<'PY'
 import json
 r = json.loads(open("gpurun_out/r06_canon/bench_default.json").read().strip().splitlines()[-1])

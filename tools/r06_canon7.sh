@@ -6,7 +6,7 @@ cd $R
 timeout -k 10 600 python -m pytest tests/test_gpu_step.py -x -q -m gpu -k "drop_in or reference or committed" > $O/tests9.txt 2>&1 || { tail -40 $O/tests9.txt; exit 1; }
 tail -2 $O/tests9.txt
 for c in c3 c2 c4; do
-timeout -k 10 300 python bench.py --config $c --no-extras > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 1; }
+timeout -k 10 300 python bench.py --config $c --no-extras --full > $O/bench_$c.json 2> $O/bench_$c.err || { tail -20 $O/bench_$c.err; exit 1; }
 python - $c <<'PY'
 import json, sys
 r = json.loads(open("gpurun_out/r06_canon/bench_%s.json" % sys.argv[1]).read().strip().splitlines()[-1])

@@ -8,4 +8,4 @@ echo "tests rc=$?"; tail -3 $O/tests.txt; grep -h "^\[train\]\|^\[dp\]" $O/tests
 python3 tools/train_quality.py --config c4 --epochs 1 --data welch --out $O/train_c4_welch.json > $O/train_c4_welch.log 2>&1; echo "train c4 welch rc=$?"; tail -c 600 $O/train_c4_welch.log
 python3 tools/train_quality.py --config c4 --epochs 1 --data sin --out $O/train_c4_sin.json > $O/train_c4_sin.log 2>&1; echo "train c4 sin rc=$?"
 python3 tools/train_quality.py --config c2 --epochs 2 --against-oracle 50 --n-test 2000 --out $O/train_c2.json > $O/train_c2.log 2>&1; echo "train c2 rc=$?"
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -1 $O/bench_default.json | cut -c1-300
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?"; tail -1 $O/bench_default.json | cut -c1-300
