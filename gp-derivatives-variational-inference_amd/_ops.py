@@ -463,6 +463,37 @@ def kernel_bwd(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d
     return workspace
 
 
+def kernel_fwd_wide(ctx, pack1, n1, pack2, n2, d, p, hyp, jitter=0.0, out=None, dtype=f32):
+    """kernel_fwd on the wide-input kernels (csrc/assemble_wide.hip) whatever d: kernel_fwd takes them by itself when the packed width
+    exceeds 96; this entry runs them at any d (checks against the whole-row kernels)"""
+    P1, s1 = pack1[0], pack1[1]
+    P2, s2 = pack2[0], pack2[1]
+    q = p + 1
+    if out is None:
+        out = torch.empty(n1 * q, n2 * q, dtype=dtype, device=P1.device)
+    _req(out, dtype, "out", 2)
+    if out.shape != (n1 * q, n2 * q):
+        raise ValueError("out has shape %s, expected %s" % (tuple(out.shape), (n1 * q, n2 * q)))
+    check(lib.dsvgp_kernel_fwd_wide(ctx.h, _ptr(P1), _ptr(s1), n1, _ptr(P2), _ptr(s2), n2, d, p, _ptr(hyp), float(jitter),
+                                    _ptr(out), _ld(out), 1 if dtype == f64 else 0), "dsvgp_kernel_fwd_wide")
+    return out
+
+
+def kernel_bwd_wide(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp, workspace=None):
+    """kernel_bwd on the wide-input kernels whatever d (see kernel_fwd_wide)"""
+    P1, s1, vn1 = pack1
+    P2, s2 = pack2[0], pack2[1]
+    isd = G.dtype == f64
+    _req(G, f64 if isd else f32, "G", 2)
+    nbytes = int(lib.dsvgp_kernel_bwd_wide_workspace_bytes(n1, n2, d, p))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
+    check(lib.dsvgp_kernel_bwd_wide(ctx.h, _ptr(G), _ld(G), 1 if isd else 0, _ptr(P1), _ptr(s1), _ptr(vn1), n1, _ptr(P2),
+                                    _ptr(s2), n2, d, p, _ptr(hyp), 1 if symmetric else 0, _ptr(d_x1),
+                                    _ptr(d_v1 if p > 0 else None), _ptr(d_hyp), _ptr(workspace)), "dsvgp_kernel_bwd_wide")
+    return workspace
+
+
 def potrf_workspace(n, device):
     """Scratch of the blocked MFMA Cholesky (inverted 64 x 64 diagonal blocks, W_k tiles).  Owned by the caller, ONE per
     factor: ``trtri_blocks`` later seeds its recursion from the blocks the factorisation left in it."""

@@ -108,6 +108,51 @@ __global__ void pack_points_kernel(const float* __restrict__ x, const float* __r
     pack_row(x, v, row, d, p, hyp[0], center, P, self, vnorm, K4, DP);
 }
 
+// pack_points_kernel for wide inputs (packed width > 96): ONE WAVE per packed row.  With a thread per row the 64 lanes of a wave walk 64
+// different rows, every load touches 64 cache lines (4.2 ms for the 2816 rows of B = 256, q = 11 at d = 4035).  Here the lanes write the
+// row coalesced and lane 0 runs pack_row's serial chains (|v|^2, the self term) over the row on its own: the output is pack_row's, bit for bit.
+__global__ __launch_bounds__(256) void pack_points_wide_kernel(const float* __restrict__ x, const float* __restrict__ v, int n, int d,
+                                                               int p, const float* __restrict__ hyp, const float* __restrict__ center,
+                                                               float* __restrict__ P, float* __restrict__ self, float* __restrict__ vnorm,
+                                                               int K4, int DP) {
+    const int q = p + 1;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= n * q) return;
+    const int i = row / q, a = row - i * q;
+    const float ell = hyp[0];
+    float* Pr = P + (int64_t)row * DP;
+    const float* xi = x + (int64_t)i * d;
+    if (a == 0) {
+        for (int k = lane; k < d; k += 64) Pr[k] = (xi[k] - (center ? center[k] : 0.f)) / ell;
+        for (int k = d + lane; k < DP; k += 64) Pr[k] = k == K4 ? 1.f : 0.f;      // indicator column
+        if (lane == 0) {
+            float acc = 0.f;
+            for (int k = 0; k < d; ++k) {
+                const float xt = (xi[k] - (center ? center[k] : 0.f)) / ell;
+                acc = __builtin_fmaf(xt, xt, acc);
+            }
+            self[row] = acc;
+        }
+    } else {
+        const float* vi = v + ((int64_t)i * p + (a - 1)) * d;
+        float nrm = 0.f;
+        if (lane == 0) {
+            float ss = 0.f;
+            for (int k = 0; k < d; ++k) ss = __builtin_fmaf(vi[k], vi[k], ss);
+            nrm = sqrtf(ss);
+        }
+        nrm = __shfl(nrm, 0);
+        for (int k = lane; k < d; k += 64) Pr[k] = vi[k] / nrm;
+        for (int k = d + lane; k < DP; k += 64) Pr[k] = 0.f;
+        if (lane == 0) {
+            float acc = 0.f;
+            for (int k = 0; k < d; ++k) acc = __builtin_fmaf(vi[k] / nrm, (xi[k] - (center ? center[k] : 0.f)) / ell, acc);
+            self[row] = acc;
+            vnorm[(int64_t)i * p + (a - 1)] = nrm;
+        }
+    }
+}
+
 // The one-call step's first launch (round 6): column_mean_hyp_kernel + pack_points_kernel of the inducing set + pack_points_kernel of the
 // minibatch in ONE.  Every workgroup forms the centre (column means of Z: one wave per column, lanes over the rows, double sums, the
 // wave's lanes added in a fixed order -- the same in every workgroup) and the constrained hyper-parameters for itself, workgroup 0
@@ -2082,8 +2127,113 @@ __global__ __launch_bounds__(PTS_NT) void kernel_bwd_points_kernel(const float* 
     }
 }
 
+// wide-input points reduction (packed width > 96): kernel_bwd_points_kernel's arithmetic with LDS that does not depend on d.  The summed dP
+// rows are not held: every pass re-adds the split slabs (fixed order s = 0, 1, ...) of the columns it needs -- column K4 of every row
+// (alphabar_a), the dots vhat_a . vhat-bar_a (one fixed-shape block reduction per direction), then d_x1 and d_v1.
+__device__ __forceinline__ float wide_dp(const float* __restrict__ slab, int nsplit, float sym, const float* __restrict__ slab2, int nsplit2,
+                                         float sym2, int64_t off, int64_t sstride) {
+    // (loads four at a time, added in the order s = 0, 1, ...: a serial load-add chain was latency bound)
+    auto ordered = [&](const float* __restrict__ sl, int ns) {
+        float sum = 0.f;
+        int sp = 0;
+        for (; sp + 4 <= ns; sp += 4) {
+            const float a0 = sl[off + sp * sstride], a1 = sl[off + (sp + 1) * sstride];
+            const float a2 = sl[off + (sp + 2) * sstride], a3 = sl[off + (sp + 3) * sstride];
+            sum += a0; sum += a1; sum += a2; sum += a3;
+        }
+        for (; sp < ns; ++sp) sum += sl[off + sp * sstride];
+        return sum;
+    };
+    float sum = ordered(slab, nsplit);
+    if (slab2) sum = sum * sym + ordered(slab2, nsplit2) * sym2;
+    return sum;
+}
+__global__ __launch_bounds__(PTS_NT) void kernel_bwd_points_wide_kernel(const float* __restrict__ slab, int nsplit,
+                                                                        const float* __restrict__ P1,
+                                                                        const float* __restrict__ vnorm1, int n1, int d, int p,
+                                                                        int K4, int DP, int NP, const float* __restrict__ hyp,
+                                                                        float sym, float* __restrict__ d_x1,
+                                                                        float* __restrict__ d_v1, const float* __restrict__ partials,
+                                                                        int nblocks, float* __restrict__ d_hyp,
+                                                                        const float* __restrict__ slab2, int nsplit2, float sym2,
+                                                                        const float* __restrict__ partials2, int nblocks2,
+                                                                        PointsTail tail) {
+    __shared__ float ab[TMAX];              // -alphabar_a = dP[a, K4]
+    __shared__ float dots[TMAX];
+    __shared__ float wred[PTS_NT / 64];
+    const int i = blockIdx.x, t = threadIdx.x, w = t >> 6, l = t & 63;
+    constexpr int nth = PTS_NT, nw = PTS_NT / 64;
+    const int q = p + 1;
+    const int64_t sstride = (int64_t)n1 * q * NP;
+    const float ell = hyp[0];
+    for (int a = t; a < q; a += nth) ab[a] = wide_dp(slab, nsplit, sym, slab2, nsplit2, sym2, ((int64_t)i * q + a) * NP + K4, sstride);
+    __syncthreads();
+    const float* xt = P1 + (int64_t)i * q * DP;
+    for (int a = 1; a <= p; ++a) {
+        const float* vh = P1 + ((int64_t)i * q + a) * DP;
+        const int64_t off = ((int64_t)i * q + a) * NP;
+        float dot = 0.f;
+        for (int k = t; k < d; k += nth) dot += vh[k] * (wide_dp(slab, nsplit, sym, slab2, nsplit2, sym2, off + k, sstride) - ab[a] * xt[k]);
+        for (int o = 32; o > 0; o >>= 1) dot += __shfl_down(dot, o);
+        if (l == 0) wred[w] = dot;
+        __syncthreads();
+        if (t == 0) {
+            float s_ = 0.f;
+            for (int ww = 0; ww < nw; ++ww) s_ += wred[ww];
+            dots[a] = s_;
+        }
+        __syncthreads();
+    }
+    float sc = slab2 ? 1.f : sym;           // (both sets are weighted inside wide_dp)
+    if (tail.scal) sc *= tail.inv_rows / hyp[2];
+    const float nbar = -0.5f * ab[0];
+    for (int k = t; k < d; k += nth) {
+        float xb = wide_dp(slab, nsplit, sym, slab2, nsplit2, sym2, (int64_t)i * q * NP + k, sstride) + 2.f * nbar * xt[k];
+        for (int a = 1; a <= p; ++a) xb += -ab[a] * P1[((int64_t)i * q + a) * DP + k];
+        d_x1[(int64_t)i * d + k] += sc * xb / ell;
+    }
+    for (int a = 1; a <= p; ++a) {
+        const float* vh = P1 + ((int64_t)i * q + a) * DP;
+        const int64_t off = ((int64_t)i * q + a) * NP;
+        const float inv = 1.f / vnorm1[(int64_t)i * p + (a - 1)];
+        for (int k = t; k < d; k += nth) {
+            const float vb = wide_dp(slab, nsplit, sym, slab2, nsplit2, sym2, off + k, sstride) - ab[a] * xt[k];
+            d_v1[((int64_t)i * p + (a - 1)) * d + k] += sc * (vb - vh[k] * dots[a]) * inv;   // normalisation Jacobian
+        }
+    }
+    if (i == 0) {       // kernel_bwd_points_kernel's block-0 tail, verbatim
+        __shared__ double r0[PTS_NT], r1[PTS_NT];
+        double a = 0, b = 0;
+        for (int j = t; j < nblocks; j += nth) { a += partials[2 * j]; b += partials[2 * j + 1]; }
+        for (int j = t; j < nblocks2; j += nth) { a += partials2[2 * j]; b += partials2[2 * j + 1]; }
+        r0[t] = a; r1[t] = b;
+        __syncthreads();
+        for (int off = PTS_NT / 2; off > 0; off >>= 1) {
+            if (t < off) { r0[t] += r0[t + off]; r1[t] += r1[t + off]; }
+            __syncthreads();
+        }
+        if (t == 0) {
+            d_hyp[1] += (float)(r0[0] / (double)hyp[1]);
+            d_hyp[0] += (float)r1[0];
+            if (tail.scal) {
+                const float sc = tail.inv_rows / hyp[2];
+                const float* scal = tail.scal;
+                const float d0 = d_hyp[0] * sc + scal[4], d1 = d_hyp[1] * sc + scal[3], d2 = d_hyp[2] + scal[1];
+                d_hyp[0] = d0; d_hyp[1] = d1; d_hyp[2] = d2;
+                auto sigm = [](float v) { return 1.f / (1.f + expf(-v)); };
+                tail.drl[0] += d0 * sigm(tail.rl[0]);
+                tail.drs[0] += d1 * sigm(tail.rs[0]);
+                tail.drn[0] += d2 * sigm(tail.rn[0]);
+                tail.dconst[0] += scal[2];
+                tail.loss[0] = -scal[0] * tail.inv_rows + tail.kl0[0] * tail.inv_num_data;
+            }
+        }
+    }
+}
+
 struct Geom { int q, R, T, K4, DP, NP, Rr, Tr; };
-inline int make_geom(int d, int p, Geom& g) {
+// any d >= 1 (the wide kernels take packed widths above 96)
+inline int make_geom_any(int d, int p, Geom& g) {
     g.q = p + 1;
     if (d < 1 || p < 0 || g.q > TMAX) return DSVGP_EINVAL;
     g.R = TMAX / g.q;
@@ -2093,7 +2243,13 @@ inline int make_geom(int d, int p, Geom& g) {
     g.K4 = (d + 3) & ~3;
     g.DP = g.K4 + 4;
     g.NP = (g.DP + 15) & ~15;
-    if (g.NP > 96) return DSVGP_EINVAL;   // d <= 88
+    return 0;
+}
+inline bool geom_wide(const Geom& g) { return g.NP > 96; }
+// the geometries of the whole-row kernels (packed rows held in LDS): packed width <= 96, i.e. d <= 92
+inline int make_geom(int d, int p, Geom& g) {
+    if (int rc = make_geom_any(d, p, g)) return rc;
+    if (geom_wide(g)) return DSVGP_EINVAL;   // d <= 92
     return 0;
 }
 
@@ -2101,6 +2257,12 @@ inline int launch_points(hipStream_t st, const Geom& g, const float* slab, int n
                          const float* hyp, float sym, float* d_x1, float* d_v1, const float* partials, int nparts, float* d_hyp,
                          const float* slab2 = nullptr, int ns2 = 0, float sym2 = 0.f, const float* partials2 = nullptr, int nparts2 = 0,
                          PointsTail tail = PointsTail{}) {
+    if (geom_wide(g)) {
+        hipLaunchKernelGGL(kernel_bwd_points_wide_kernel, dim3(n1), dim3(PTS_NT), 0, st, slab, ns, P1, vnorm1, n1, d, p, g.K4, g.DP, g.NP, hyp,
+                           sym, d_x1, d_v1, partials, nparts, d_hyp, slab2, ns2, sym2, partials2, nparts2, tail);
+        DSVGP_LAUNCH_CHECK();
+        return 0;
+    }
     const int pts_waves = (g.q * g.DP > 3072) ? 1 : PTS_NT / 64;       // (wave partials: <= 48 KB of LDS)
     hipLaunchKernelGGL(kernel_bwd_points_kernel, dim3(n1), dim3(64 * pts_waves), sizeof(float) * (pts_waves * g.q * g.DP + g.q + 1), st, slab, ns,
                        P1, vnorm1, n1, d, p, g.K4, g.DP, g.NP, hyp, sym, d_x1, d_v1, partials, nparts, d_hyp, slab2, ns2, sym2, partials2, nparts2,
@@ -3186,7 +3348,7 @@ int kernel_bwd_points_flush(dsvgp_ctx* ctx, const float* P1, const float* vnorm1
                             float* d_v1, float* d_hyp, const float* scal, const float* kl0, double rows, double num_data, const float* rl,
                             const float* rs, const float* rn, float* drl, float* drs, float* drn, float* dconst, float* loss) {
     Geom g;
-    if (int rc = make_geom(d, p, g)) return rc;
+    if (int rc = make_geom_any(d, p, g)) return rc;
     const int n = ctx->n_deferred;
     ctx->n_deferred = 0;
     if (n < 1) return DSVGP_EINVAL;
@@ -3228,8 +3390,22 @@ int launch_pack_both(hipStream_t st, const float* Z, const float* V, int M, cons
                      const float* rl, const float* rs, const float* rn, float* hyp, float* center, float* PZ, float* sZ, float* vZ,
                      float* PX, float* sX, float* vX) {
     Geom g;
-    if (int rc = make_geom(d, p, g)) return rc;
+    if (int rc = make_geom_any(d, p, g)) return rc;
     const int nbz = cdiv((int64_t)M * g.q, 256), nbx = cdiv((int64_t)B * g.q, 256);
+    if (geom_wide(g)) {
+        // wide inputs: every workgroup of pack_both_kernel would form all d column means on its own (d serial wave reductions); the
+        // centre and hyp come from column_mean_hyp_kernel (one workgroup per column, as the piecewise step) and the two sets are
+        // packed by pack_points_wide_kernel
+        hipLaunchKernelGGL(column_mean_hyp_kernel, dim3(d), dim3(256), 0, st, Z, M, d, center, rl, rs, rn, hyp);
+        DSVGP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pack_points_wide_kernel, dim3(cdiv((int64_t)M * g.q, 4)), dim3(256), 0, st, Z, V, M, d, p, hyp, center, PZ, sZ, vZ,
+                           g.K4, g.DP);
+        DSVGP_LAUNCH_CHECK();
+        hipLaunchKernelGGL(pack_points_wide_kernel, dim3(cdiv((int64_t)B * g.q, 4)), dim3(256), 0, st, X, D, B, d, p, hyp, center, PX, sX, vX,
+                           g.K4, g.DP);
+        DSVGP_LAUNCH_CHECK();
+        return 0;
+    }
     hipLaunchKernelGGL(pack_both_kernel, dim3(nbz + nbx), dim3(256), sizeof(float) * (d + 1), st, Z, V, M, X, D, B, d, p, rl, rs, rn, hyp,
                        center, PZ, sZ, vZ, PX, sX, vX, g.K4, g.DP, nbz);
     DSVGP_LAUNCH_CHECK();
@@ -3254,11 +3430,15 @@ extern "C" int dsvgp_pack_points(dsvgp_ctx* ctx, const float* x, const float* v,
                                  const float* hyp, const float* center, float* P, float* self, float* vnorm) {
     if (!ctx || !x || !hyp || !P || !self || n < 0 || (p > 0 && (!v || !vnorm))) return DSVGP_EINVAL;
     Geom g;
-    if (int rc = make_geom(d, p, g)) return rc;
+    if (int rc = make_geom_any(d, p, g)) return rc;
     if (n == 0) return 0;
     const int rows = n * g.q;
-    hipLaunchKernelGGL(pack_points_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, ctx->stream, x, v, n, d, p, hyp, center,
-                       P, self, vnorm, g.K4, g.DP);
+    if (geom_wide(g))
+        hipLaunchKernelGGL(pack_points_wide_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, ctx->stream, x, v, n, d, p, hyp, center,
+                           P, self, vnorm, g.K4, g.DP);
+    else
+        hipLaunchKernelGGL(pack_points_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, ctx->stream, x, v, n, d, p, hyp, center,
+                           P, self, vnorm, g.K4, g.DP);
     DSVGP_LAUNCH_CHECK();
     return 0;
 }
@@ -3268,10 +3448,11 @@ extern "C" int dsvgp_kernel_fwd(dsvgp_ctx* ctx, const float* P1, const float* se
                                 int64_t ld, int out_is_double) {
     if (!ctx || !P1 || !self1 || !P2 || !self2 || !hyp || !out || n1 < 0 || n2 < 0) return DSVGP_EINVAL;
     Geom g;
-    if (int rc = make_geom(d, p, g)) return rc;
+    if (int rc = make_geom_any(d, p, g)) return rc;
     if (n1 == 0 || n2 == 0) return 0;
     const int n1q = n1 * g.q, n2q = n2 * g.q;
     if (ld < n2q) return DSVGP_EINVAL;
+    if (geom_wide(g)) return launch_kernel_fwd_wide(ctx->stream, P1, self1, n1q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
     if (FWD_RUN && (g.q == 6 || g.q == 3) && g.NP <= 32 && n1q % g.q == 0) {
         // "run" kernel (16-byte stores): needs 16-byte aligned rows of the output
         const int esz = out_is_double ? 8 : 4;
@@ -3370,14 +3551,59 @@ extern "C" int dsvgp_kernel_diag(dsvgp_ctx* ctx, int n, int p, const float* hyp,
     return 0;
 }
 
+extern "C" int dsvgp_kernel_fwd_wide(dsvgp_ctx* ctx, const float* P1, const float* self1, int n1, const float* P2,
+                                     const float* self2, int n2, int d, int p, const float* hyp, float jitter, void* out,
+                                     int64_t ld, int out_is_double) {
+    if (!ctx || !P1 || !self1 || !P2 || !self2 || !hyp || !out || n1 < 0 || n2 < 0) return DSVGP_EINVAL;
+    Geom g;
+    if (int rc = make_geom_any(d, p, g)) return rc;
+    if (n1 == 0 || n2 == 0) return 0;
+    const int n1q = n1 * g.q, n2q = n2 * g.q;
+    if (ld < n2q) return DSVGP_EINVAL;
+    return launch_kernel_fwd_wide(ctx->stream, P1, self1, n1q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
+}
+
+extern "C" size_t dsvgp_kernel_bwd_wide_workspace_bytes(int n1, int n2, int d, int p) {
+    Geom g;
+    if (make_geom_any(d, p, g) || n1 <= 0 || n2 <= 0) return 0;
+    return kernel_bwd_wide_workspace(n1 * g.q, n2 * g.q, g.q, g.NP);
+}
+
 extern "C" size_t dsvgp_kernel_bwd_workspace_bytes(int n1, int n2, int d, int p) {
     Geom g;
-    if (make_geom(d, p, g) || n1 <= 0 || n2 <= 0) return 0;
+    if (make_geom_any(d, p, g) || n1 <= 0 || n2 <= 0) return 0;
+    if (geom_wide(g)) return kernel_bwd_wide_workspace(n1 * g.q, n2 * g.q, g.q, g.NP);
     const int ns = bwd_nsplit(n1, n2, g);
     int tr, tc, wgs;
     bwd_tiles(g, tr, tc, wgs);
     const int rt = cdiv((int64_t)n1 * g.q, tr);
     return sizeof(float) * ((size_t)ns * n1 * g.q * g.NP + (size_t)2 * ns * rt + 64);
+}
+
+// the wide backward (assemble_wide.hip: Tbar tiles, then the contraction into the split slabs) and the points launch, queued or deferred
+static int kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
+                           const float* vnorm1, int n1, const float* P2, const float* self2, int n2, int d, int p, const Geom& g,
+                           const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_hyp, void* workspace) {
+    float *slab, *partials;
+    int ns, nparts;
+    if (int rc = launch_kernel_bwd_wide(ctx->stream, G, ldg, g_is_double, P1, self1, n1 * g.q, P2, self2, n2 * g.q, g.q, g.K4, g.DP, g.NP,
+                                        hyp, workspace, &slab, &ns, &partials, &nparts))
+        return rc;
+    return finish_points(ctx, g, slab, ns, P1, vnorm1, n1, d, p, hyp, symmetric ? 2.f : 1.f, d_x1, d_v1, partials, nparts, d_hyp);
+}
+
+extern "C" int dsvgp_kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1,
+                                     const float* self1, const float* vnorm1, int n1, const float* P2,
+                                     const float* self2, int n2, int d, int p, const float* hyp, int symmetric,
+                                     float* d_x1, float* d_v1, float* d_hyp, void* workspace) {
+    if (!ctx || !G || !P1 || !self1 || !P2 || !self2 || !hyp || !d_x1 || !d_hyp || !workspace) return DSVGP_EINVAL;
+    if (p > 0 && (!vnorm1 || !d_v1)) return DSVGP_EINVAL;
+    Geom g;
+    if (int rc = make_geom_any(d, p, g)) return rc;
+    if (n1 <= 0 || n2 <= 0) return 0;
+    if (ldg < (int64_t)n2 * g.q) return DSVGP_EINVAL;
+    return kernel_bwd_wide(ctx, G, ldg, g_is_double, P1, self1, vnorm1, n1, P2, self2, n2, d, p, g, hyp, symmetric, d_x1, d_v1, d_hyp,
+                           workspace);
 }
 
 extern "C" int dsvgp_kernel_bwd(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1,
@@ -3387,10 +3613,13 @@ extern "C" int dsvgp_kernel_bwd(dsvgp_ctx* ctx, const void* G, int64_t ldg, int 
     if (!ctx || !G || !P1 || !self1 || !P2 || !self2 || !hyp || !d_x1 || !d_hyp || !workspace) return DSVGP_EINVAL;
     if (p > 0 && (!vnorm1 || !d_v1)) return DSVGP_EINVAL;
     Geom g;
-    if (int rc = make_geom(d, p, g)) return rc;
+    if (int rc = make_geom_any(d, p, g)) return rc;
     if (n1 <= 0 || n2 <= 0) return 0;
     const int n1q = n1 * g.q, n2q = n2 * g.q;
     if (ldg < n2q) return DSVGP_EINVAL;
+    if (geom_wide(g))
+        return kernel_bwd_wide(ctx, G, ldg, g_is_double, P1, self1, vnorm1, n1, P2, self2, n2, d, p, g, hyp, symmetric, d_x1, d_v1, d_hyp,
+                               workspace);
     const int ns = bwd_nsplit(n1, n2, g);
     int tr_, tc_, wgs_;
     bwd_tiles(g, tr_, tc_, wgs_);

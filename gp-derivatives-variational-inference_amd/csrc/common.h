@@ -110,6 +110,15 @@ int kernel_bwd_points_flush(dsvgp_ctx* ctx, const float* P1, const float* vnorm1
                             const float* rs, const float* rn, float* drl, float* drs, float* drn, float* dconst, float* loss);
 int launch_column_mean_hyp(hipStream_t st, const float* x, int n, int d, float* center, const float* rl, const float* rs,
                            const float* rn, float* hyp);                                       // assemble.hip
+// wide-input assembly (assemble_wide.hip; packed width > 96, any d through the dsvgp_kernel_*_wide entries): the forward into `out`, and
+// the backward's tile and contraction launches -- slab[ns][n1q][NP] and partials[nparts][2] inside `workspace` (kernel_bwd_wide_workspace
+// bytes), for kernel_bwd_points_kernel's contract (assemble.hip)
+int launch_kernel_fwd_wide(hipStream_t st, const float* P1, const float* self1, int n1q, const float* P2, const float* self2, int n2q,
+                           int q, int K4, int DP, const float* hyp, float jitter, void* out, int64_t ld, int out_is_double);
+size_t kernel_bwd_wide_workspace(int n1q, int n2q, int q, int NP);
+int launch_kernel_bwd_wide(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1q,
+                           const float* P2, const float* self2, int n2q, int q, int K4, int DP, int NP, const float* hyp, void* workspace,
+                           float** slab, int* ns, float** partials, int* nparts);
 int launch_widen_sym_f32_f64(hipStream_t st, const float* src, int64_t lds, double* dst, int64_t ldd, int n);    // elbo.hip: fp64 mirror of an fp32 lower triangle
 int launch_mirror_sminus_i_col(hipStream_t st, float* A, int n, int64_t lda, const float* m, const float* hyp, float rows, double* W = nullptr,
                                int64_t ldw = 0);   // elbo.hip

@@ -113,6 +113,18 @@ int dsvgp_kernel_bwd(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double
                      const float* self1, const float* vnorm1, int n1, const float* P2,
                      const float* self2, int n2, int d, int p, const float* hyp, int symmetric,
                      float* d_x1, float* d_v1, float* d_hyp, void* workspace);
+/* Packed width dsvgp_packed_width(d) > 96 (d >= 93): dsvgp_pack_points, dsvgp_kernel_fwd, dsvgp_kernel_bwd and
+ * dsvgp_kernel_bwd_workspace_bytes route to the wide-input kernels, which accumulate T = P1 P2^T over a K loop of fixed column chunks
+ * (workgroup LDS independent of d).  The _wide entries below run those kernels for ANY d >= 1, with the arguments and contracts of
+ * dsvgp_kernel_fwd / dsvgp_kernel_bwd (workspace: dsvgp_kernel_bwd_wide_workspace_bytes).  The backward uses no floating-point atomics. */
+int dsvgp_kernel_fwd_wide(dsvgp_ctx* ctx, const float* P1, const float* self1, int n1, const float* P2,
+                          const float* self2, int n2, int d, int p, const float* hyp, float jitter,
+                          void* out, int64_t ld, int out_is_double);
+size_t dsvgp_kernel_bwd_wide_workspace_bytes(int n1, int n2, int d, int p);
+int dsvgp_kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1,
+                          const float* self1, const float* vnorm1, int n1, const float* P2,
+                          const float* self2, int n2, int d, int p, const float* hyp, int symmetric,
+                          float* d_x1, float* d_v1, float* d_hyp, void* workspace);
 /* 1 when dsvgp_kernel_fwd_canon / _bwd_canon take the geometry (d, p), 0 otherwise */
 int dsvgp_kernel_canon_supported(int d, int p);
 /* backward of dsvgp_kernel_fwd_canon (symmetric = 0 semantics; same workspace size as dsvgp_kernel_bwd) */
