@@ -16,26 +16,16 @@
 // directly in the interleaved M(p+1)-stride layout (no permutation pass, :105-107).
 // The self terms use the same k-ordered fma chain as the MFMA, so r == 0 exactly on the diagonal
 // of K_ZZ.  The backward recomputes T, forms Tbar per micro-block and contracts Tbar . P2 on MFMA.
+// The "without the stores / the MFMA product / the loads" figures quoted below came from timing-ablation builds (wrong results by
+// construction: ASM_ABLATE, FWDP_ABL, BWD_ABLATE, PAIR_ABLATE, BWDS_ABL, CAN_ABL); removed in the build-variant clean-up; last present in 8a953b7.
 #include "common.h"
 #include <type_traits>
-
-#ifndef ASM_ABLATE
-#define ASM_ABLATE 0      // tools only: 1 = no global stores, 2 = stores of a constant (no MFMA / epilogue math)
-#endif
 
 // One-wave workgroups (64 threads) exchange through LDS, which serves a wave's instructions in issue order: all they need between a write
 // and another lane's read is that the COMPILER keeps the order.  __syncthreads() would add "s_waitcnt vmcnt(0)" (its fence covers global
 // memory too), i.e. drain the tile's global stores and the next tile's prefetch at every exchange (profiles/r06_c_*).
-// ASM_WAVE_SYNC = 0 restores the workgroup barrier (tools/assemble_variants.sh).
-#ifndef ASM_WAVE_SYNC
-#define ASM_WAVE_SYNC 1
-#endif
-#if ASM_WAVE_SYNC
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
                          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-#else
-#define WAVE_SYNC() __syncthreads()
-#endif
 
 
 namespace {
@@ -242,20 +232,11 @@ __global__ __launch_bounds__(256) void kernel_fwd_kernel(const float* __restrict
     float* KK = s2 + Tcp;                       // Rr * Rc pair values
     const int row0 = blockIdx.y * Tr, col0 = blockIdx.x * Tc;
     const int rows = min(Tr, n1q - row0), cols = min(Tc, n2q - col0);
-    if (ASM_ABLATE == 2) {
-        for (int e = threadIdx.x; e < Tr * Tc; e += 256) {
-            const int r = e / Tc, c = e - r * Tc;
-            if (r < rows && c < cols) out[(int64_t)(row0 + r) * ld + col0 + c] = (OutT)1.f;
-        }
-        return;
-    }
     stage_pack(P1s, s1, P1, self1, row0, Tr, n1q, Trp, DP, K4, LDP);
     stage_pack(P2s, s2, P2, self2, col0, Tc, n2q, Tcp, DP, K4, LDP);
     __syncthreads();
-    if (ASM_ABLATE == 3) { if (P1s[threadIdx.x] == 123.456f) out[0] = (OutT)1.f; return; }
     mfma_T(Ts, P1s, P2s, Trp / 16, Tcp / 16, K4, LDP);
     __syncthreads();
-    if (ASM_ABLATE == 4) { if (Ts[threadIdx.x] == 123.456f) out[0] = (OutT)1.f; return; }
 
     const float ell = hyp[0], s = hyp[1];
     const float il = 1.f / ell, il2 = il * il;
@@ -297,8 +278,7 @@ __global__ __launch_bounds__(256) void kernel_fwd_kernel(const float* __restrict
                 const float f1 = b ? ((t - u * w) * il2) : (-u * il);
                 float val = (a ? f1 : f0) * k;
                 if (row0 + r == gc) val += jitter;
-                if (ASM_ABLATE == 1) { if (val == 123.456f) *optr = (OutT)val; }
-                else *optr = (OutT)val;
+                *optr = (OutT)val;
                 optr += ostep;
                 a += da; ri += di;
                 if (a >= q) { a -= q; ++ri; }
@@ -321,18 +301,6 @@ __global__ __launch_bounds__(256) void kernel_fwd_kernel(const float* __restrict
 // pair(s) into the kernel micro-block with one exp and writes it straight to HBM in the interleaved layout.
 // ~15 KB of LDS per wave: 8 waves per CU overlap each other's staging, MFMA and store phases.
 constexpr int FWD_PAIR_LDT = 52;
-#ifndef FWDP_ABL
-#define FWDP_ABL 0        // tools only (results wrong): 1 = no global stores, 2 = no T' MFMA product, 4 = no P2 staging loads
-#endif
-#ifndef FWDP_ST16
-#define FWDP_ST16 1       // q = 6, float output: 16-byte stores shared by lane pairs (two store instructions per row instead of three)
-#endif
-#ifndef FWDP_AREG
-#define FWDP_AREG 1       // A fragments of the wave's 48 rows in registers for the whole column sweep (LDS: 10 KB per wave, 16 waves per CU)
-#endif
-#ifndef FWDP_OVERLAY
-#define FWDP_OVERLAY 1    // T' overlays the P2 image (10 instead of 8 waves per CU) and the next tile's P2 rows are prefetched
-#endif
 #ifndef FWD_PAIR_WGS_
 #define FWD_PAIR_WGS_ (256 * 16)      // probed 4 / 6 / 8 / 12 / 16 / 32 per CU: 207 / 170 / 137 / 133 / 121 / 135 us for K_ZX at C4
 #endif
@@ -340,18 +308,12 @@ constexpr int FWD_PAIR_LDT = 52;
 #ifndef FWDP_MINW
 #define FWDP_MINW 1
 #endif
-#ifndef FWDP_LDS_EXTRA
-#define FWDP_LDS_EXTRA 0  // tools only: unused LDS bytes per wave (30720 -> 4 waves per CU = 1 per SIMD: the occupancy ablation)
-#endif
-#ifndef FWDP_CHUNK
-#define FWDP_CHUNK 1      // consecutive column tiles per wave (87.7 -> 85.7 us)
-#endif
-#ifndef FWDP_LEAN
-#define FWDP_LEAN 1       // tiles inside the matrix are fetched and staged without predicates (needs FWDP_OVERLAY and a 49th LDS row)
-#endif
-#ifndef FWDP_FAST
-#define FWDP_FAST 1       // interior tiles leave through the T' tile as fully coalesced 16-byte stores
-#endif
+// Each of the following was measured against its absence behind a build switch (removed in the build-variant clean-up; last present in 8a953b7):
+// the A fragments of the wave's 48 rows stay in registers for the whole column sweep (FWDP_AREG; LDS: 10 KB per wave, 16 waves per CU); T' overlays
+// the P2 image (10 instead of 8 waves per CU) and the next tile's P2 rows are prefetched (FWDP_OVERLAY); consecutive column tiles per wave
+// (FWDP_CHUNK: 87.7 -> 85.7 us); tiles inside the matrix are fetched and staged without predicates (FWDP_LEAN: a 49th LDS row); interior tiles leave
+// through the T' tile as fully coalesced 16-byte stores (FWDP_FAST); q = 6, float output: 16-byte stores shared by lane pairs, two store
+// instructions per row instead of three (FWDP_ST16).
 // KSM: k-steps of the T' product the A fragments are held for: 8 (packed width DP <= 32: d <= 28, the BASELINE configs 2 and 4) or 16
 // (DP <= 64: d <= 60, BASELINE config 5 at d = 50; round 5 -- more registers: one wave per SIMD instead of two)
 template <typename OutT, int Q, int KSM = 8>
@@ -365,9 +327,8 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
     constexpr int LDT2 = FWD_PAIR_LDT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LDP = K4 + 5;
-    float* P1s = smem;                  // [48][LDP]   (FWDP_AREG: not used, the A fragments of the wave's 48 rows stay in registers)
-    float* P2s = FWDP_AREG ? smem : P1s + 48 * LDP;        // [48][LDP]
-    float* TT = FWDP_OVERLAY ? P2s : P2s + 48 * LDP;         // [48][LDT2] (overlay: T' is written once every P2 fragment is in registers)
+    float* P2s = smem;                  // [48][LDP]   (P1' has no image: the A fragments of the wave's 48 rows stay in registers)
+    float* TT = P2s;                    // [48][LDT2]  T' overlays the P2 image: it is written once every P2 fragment is in registers
     const int lane = threadIdx.x, m16 = lane & 15, kg = lane >> 4;
     const int row0 = blockIdx.y * T;
     const int ncoltiles = (n2q + T - 1) / T;
@@ -377,34 +338,20 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
     const float il = 1.f / ell, il2 = il * il;
 
     float areg[3][KSM];                 // A fragments: areg[i][ks] = P1'[row0 + 16 i + m16][4 ks + kg]  (KS <= KSM since DP <= 4 KSM)
-    if (FWDP_AREG) {
-        for (int e = lane; e < 48 * LDP; e += 64) P2s[e] = 0.f;
+    for (int e = lane; e < 48 * LDP; e += 64) P2s[e] = 0.f;
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int gr = row0 + i * 16 + m16;
-            const bool ok = gr < n1q;
-            const int a = (i * 16 + m16) % Q;
-            const float sf = ok ? self1[gr] : 0.f;
+    for (int i = 0; i < 3; ++i) {
+        const int gr = row0 + i * 16 + m16;
+        const bool ok = gr < n1q;
+        const int a = (i * 16 + m16) % Q;
+        const float sf = ok ? self1[gr] : 0.f;
 #pragma unroll
-            for (int ks = 0; ks < KSM; ++ks) {
-                float v = 0.f;
-                if (ks < K4 / 4) v = ok ? P1[(int64_t)gr * DP + ks * 4 + kg] : 0.f;
-                else if (ks == K4 / 4 && ok) v = (kg == 1) ? (a == 0 ? 1.f : 0.f) : ((kg == 2) ? (a == 0 ? 0.f : -sf) : 0.f);
-                areg[i][ks] = v;
-            }
+        for (int ks = 0; ks < KSM; ++ks) {
+            float v = 0.f;
+            if (ks < K4 / 4) v = ok ? P1[(int64_t)gr * DP + ks * 4 + kg] : 0.f;
+            else if (ks == K4 / 4 && ok) v = (kg == 1) ? (a == 0 ? 1.f : 0.f) : ((kg == 2) ? (a == 0 ? 0.f : -sf) : 0.f);
+            areg[i][ks] = v;
         }
-    } else {
-    for (int e = lane; e < 48 * LDP; e += 64) { P1s[e] = 0.f; P2s[e] = 0.f; }
-    WAVE_SYNC();
-    for (int e = lane; e < T * K4; e += 64) {
-        const int r = e / K4, k = e - r * K4;
-        if (row0 + r < n1q) P1s[r * LDP + k] = P1[(int64_t)(row0 + r) * DP + k];
-    }
-    if (lane < T && row0 + lane < n1q) {
-        const int a = lane % Q;
-        P1s[lane * LDP + K4 + 1] = a == 0 ? 1.f : 0.f;
-        P1s[lane * LDP + K4 + 2] = a == 0 ? 0.f : -self1[row0 + lane];
-    }
     }
     int pr0[PPL], pc0[PPL];
     float s1r0[PPL];
@@ -438,7 +385,6 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
     const bool rows_full = row0 + T <= n1q;
     auto prefetch = [&](int ct_) {
         const int c0_ = ct_ * T;
-#if FWDP_LEAN
         if (c0_ + T <= n2q) {
             const f4* src = reinterpret_cast<const f4*>(P2 + (int64_t)c0_ * DP);
 #pragma unroll
@@ -446,7 +392,6 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
             pselfv = -self2[c0_ + min(lane, T - 1)];
             return;
         }
-#endif
 #pragma unroll
         for (int u = 0; u < NPFP; ++u) {
             const int e = lane + 64 * u;
@@ -459,18 +404,14 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
     // ovec bit 3 (the one-call steps' K_ZZ: ctx->fwd_lower_only): only the column tiles that reach into the 64 x 64 blocks on or below the block
     // diagonal of this row tile's rows -- what the blocked Cholesky factorisation reads
     const int ct_end = (ovec & 8) ? min(ncoltiles, (64 * ((row0 + T - 1) / 64) + 63) / T + 1) : ncoltiles;
-#if FWDP_CHUNK
     // consecutive column tiles per wave: the 192-byte row pieces of neighbouring tiles complete each other's 128-byte lines in ONE L2
     const int cper = (ct_end + (int)gridDim.x - 1) / (int)gridDim.x;
     const int ct_lo = blockIdx.x * cper, ct_hi = min(ct_lo + cper, ct_end), ct_step = 1;
-#else
-    const int ct_lo = blockIdx.x, ct_hi = ct_end, ct_step = gridDim.x;
-#endif
-    if (FWDP_OVERLAY && ct_lo < ct_hi) prefetch(ct_lo);
+    if (ct_lo < ct_hi) prefetch(ct_lo);
     for (int ct = ct_lo; ct < ct_hi; ct += ct_step) {
         const int col0 = ct * T;
         float s2c0[PPL];
-        const bool full = FWDP_LEAN && rows_full && col0 + T <= n2q;       // (wave-uniform)
+        const bool full = rows_full && col0 + T <= n2q;       // (wave-uniform)
         if (full) {
 #pragma unroll
             for (int pp = 0; pp < PPL; ++pp) s2c0[pp] = self2[col0 + min(pc0[pp], T - 1)];
@@ -479,110 +420,61 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
             for (int pp = 0; pp < PPL; ++pp) s2c0[pp] = (prow[pp] && col0 + pc0[pp] < n2q) ? self2[col0 + pc0[pp]] : 0.f;
         }
         WAVE_SYNC();   // single wave: orders the previous tile's LDS reads before the new stores
-        if (FWDP_OVERLAY) {
-#if FWDP_LEAN
 #pragma unroll
-            for (int u = 0; u < NPFP; ++u) {           // (lanes past the end of the tile: the scratch row behind the image)
+        for (int u = 0; u < NPFP; ++u) {           // (lanes past the end of the tile: the scratch row behind the image)
 #pragma unroll
-                for (int t = 0; t < 4; ++t) P2s[pf_lds[u] + t] = pf[u][t];
-            }
-#else
-#pragma unroll
-            for (int u = 0; u < NPFP; ++u) {
-                const int e = lane + 64 * u;
-                if (e < T * pch) {
-                    const int r = e / pch, k = (e - r * pch) * 4;
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) P2s[r * LDP + k + t] = pf[u][t];
-                }
-            }
-#endif
-            WAVE_SYNC();
-            if (lane < T) {
-                P2s[lane * LDP + K4 + 1] = pselfv;
-                P2s[lane * LDP + K4 + 2] = (col0 + lane < n2q && lane % Q == 0) ? 1.f : 0.f;
-            }
-            if (ct + ct_step < ct_hi) prefetch(ct + ct_step);      // in flight under the rest of this tile
-        } else {
-        if (!(FWDP_ABL & 4))
-        for (int e = lane; e < T * pch; e += 64) {
-            const int r = e / pch, k = (e - r * pch) * 4;
-            const int gr = col0 + r;
-            f4 v = {0.f, 0.f, 0.f, 0.f};
-            if (gr < n2q) v = *reinterpret_cast<const f4*>(P2 + (int64_t)gr * DP + k);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) P2s[r * LDP + k + t] = v[t];
+            for (int t = 0; t < 4; ++t) P2s[pf_lds[u] + t] = pf[u][t];
         }
         WAVE_SYNC();
         if (lane < T) {
-            const int gr = col0 + lane;
-            const bool ok = gr < n2q;
-            P2s[lane * LDP + K4 + 1] = ok ? -self2[gr] : 0.f;
-            P2s[lane * LDP + K4 + 2] = (ok && lane % Q == 0) ? 1.f : 0.f;
+            P2s[lane * LDP + K4 + 1] = pselfv;
+            P2s[lane * LDP + K4 + 2] = (col0 + lane < n2q && lane % Q == 0) ? 1.f : 0.f;
         }
-        }
+        if (ct + ct_step < ct_hi) prefetch(ct + ct_step);      // in flight under the rest of this tile
         WAVE_SYNC();
         {
             f4 t[3][3];
-            if (!FWDP_AREG) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) t[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-            }
-            const float* pa = P1s + m16 * LDP + kg;
             const float* pb = P2s + m16 * LDP + kg;
-            if (FWDP_AREG) {
-                // one straight-line copy per K depth: no per-step branches, the first product starts from the inline zero
-                auto product = [&](auto ksc) {
-                    constexpr int KS_ = decltype(ksc)::value;
+            // one straight-line copy per K depth: no per-step branches, the first product starts from the inline zero
+            auto product = [&](auto ksc) {
+                constexpr int KS_ = decltype(ksc)::value;
 #pragma unroll
-                    for (int ks = 0; ks < KS_; ++ks) {
-                        float bv[3];
+                for (int ks = 0; ks < KS_; ++ks) {
+                    float bv[3];
 #pragma unroll
-                        for (int j = 0; j < 3; ++j) bv[j] = pb[j * 16 * LDP + ks * 4];
+                    for (int j = 0; j < 3; ++j) bv[j] = pb[j * 16 * LDP + ks * 4];
 #pragma unroll
-                        for (int i = 0; i < 3; ++i)
+                    for (int i = 0; i < 3; ++i)
 #pragma unroll
-                            for (int j = 0; j < 3; ++j)
-                                t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv[j], ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i][j], 0, 0, 0);
-                    }
-                };
-                switch ((FWDP_ABL & 2) ? 1 : KS) {
-                    case 1: product(std::integral_constant<int, 1>{}); break;
-                    case 2: product(std::integral_constant<int, 2>{}); break;
-                    case 3: product(std::integral_constant<int, 3>{}); break;
-                    case 4: product(std::integral_constant<int, 4>{}); break;
-                    case 5: product(std::integral_constant<int, 5>{}); break;
-                    case 6: product(std::integral_constant<int, 6>{}); break;
-                    case 7: product(std::integral_constant<int, 7>{}); break;
-                    case 8: product(std::integral_constant<int, 8>{}); break;
-                    default:
-                        if constexpr (KSM > 8) {
-                            switch (KS) {
-                                case 9: product(std::integral_constant<int, 9>{}); break;
-                                case 10: product(std::integral_constant<int, 10>{}); break;
-                                case 11: product(std::integral_constant<int, 11>{}); break;
-                                case 12: product(std::integral_constant<int, 12>{}); break;
-                                case 13: product(std::integral_constant<int, 13>{}); break;
-                                case 14: product(std::integral_constant<int, 14>{}); break;
-                                case 15: product(std::integral_constant<int, 15>{}); break;
-                                default: product(std::integral_constant<int, 16>{}); break;
-                            }
-                        } else product(std::integral_constant<int, 8>{});
-                        break;
+                        for (int j = 0; j < 3; ++j)
+                            t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv[j], ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i][j], 0, 0, 0);
                 }
-            } else
-            for (int ks = 0; ks < ((FWDP_ABL & 2) ? 1 : KS); ++ks) {
-                float av[3], bv[3];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) { av[i] = pa[i * 16 * LDP + ks * 4]; bv[i] = pb[i * 16 * LDP + ks * 4]; }
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], t[i][j], 0, 0, 0);
+            };
+            switch (KS) {
+                case 1: product(std::integral_constant<int, 1>{}); break;
+                case 2: product(std::integral_constant<int, 2>{}); break;
+                case 3: product(std::integral_constant<int, 3>{}); break;
+                case 4: product(std::integral_constant<int, 4>{}); break;
+                case 5: product(std::integral_constant<int, 5>{}); break;
+                case 6: product(std::integral_constant<int, 6>{}); break;
+                case 7: product(std::integral_constant<int, 7>{}); break;
+                case 8: product(std::integral_constant<int, 8>{}); break;
+                default:
+                    if constexpr (KSM > 8) {
+                        switch (KS) {
+                            case 9: product(std::integral_constant<int, 9>{}); break;
+                            case 10: product(std::integral_constant<int, 10>{}); break;
+                            case 11: product(std::integral_constant<int, 11>{}); break;
+                            case 12: product(std::integral_constant<int, 12>{}); break;
+                            case 13: product(std::integral_constant<int, 13>{}); break;
+                            case 14: product(std::integral_constant<int, 14>{}); break;
+                            case 15: product(std::integral_constant<int, 15>{}); break;
+                            default: product(std::integral_constant<int, 16>{}); break;
+                        }
+                    } else product(std::integral_constant<int, 8>{});
+                    break;
             }
-            if (FWDP_OVERLAY) WAVE_SYNC();          // every P2 fragment has been read: T' may overlay the image
+            WAVE_SYNC();          // every P2 fragment has been read: T' may overlay the image
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
@@ -591,7 +483,6 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
                     for (int r = 0; r < 4; ++r) TT[(i * 16 + kg * 4 + r) * LDT2 + j * 16 + m16] = t[i][j][r];
         }
         WAVE_SYNC();
-#if FWDP_FAST
         // Interior tile, float output, 16-byte aligned rows: the micro-blocks go back to the T' tile IN PLACE (every lane rewrites
         // only what it read) and the tile leaves as nine fully coalesced store instructions -- every row 192 contiguous bytes,
         // 12 lanes x 16 B.  The per-lane micro-block stores of the general path below write 16-byte pieces 16 bytes apart: each
@@ -650,12 +541,11 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
                 for (int u = 0; u < 9; ++u) {
                     const int id = lane + 64 * u, r = id / 12, c4 = (id - 12 * r) * 4;
                     const f4 x = *reinterpret_cast<const f4*>(TT + r * LDT2 + c4);
-                    if (!(FWDP_ABL & 1)) *reinterpret_cast<f4*>(orow + (int64_t)r * ld + c4) = x;
+                    *reinterpret_cast<f4*>(orow + (int64_t)r * ld + c4) = x;
                 }
                 continue;
             }
         }
-#endif
 #pragma unroll
         for (int pp = 0; pp < PPL; ++pp) {
             const bool mine = prow[pp] && col0 + pc0[pp] < n2q;
@@ -681,7 +571,7 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
             const float k = s * expf(-0.5f * nn);                                  // postprocess_rbf, ScaleKernel
             const float kil = k * il, kil2 = k * il2;
             const int64_t gr0 = (int64_t)row0 + pr0[pp], gc0 = (int64_t)col0 + pc0[pp];
-            OutT* o = out + ((FWDP_ABL & 8) ? (gr0 & 63) : gr0) * ld + gc0;      // (ablation 8: every store lands in the first 64 rows -- L2 hits)
+            OutT* o = out + gr0 * ld + gc0;
             // Q = 6, float: lanes 2j / 2j + 1 hold horizontally adjacent micro-blocks = 12 consecutive floats per row, 48-byte
             // aligned.  The even lane stores floats 0..3 and 4..7 (its last two + the neighbour's first two, fetched with a
             // DPP quad permute), the odd lane floats 8..11: two 16-byte store instructions per row instead of three 8-byte ones
@@ -704,7 +594,6 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
                     for (int b = 1; b < Q; ++b) v[b] = (tq[a][b] + tq[a][0] * tq[0][b]) * kil2;  // (G_ab - u_a w_b) k / ell^2
                 }
                 if (jitter != 0.f && gr0 == gc0) v[a] += jitter;      // diagonal micro-block: global row == global column
-                if ((FWDP_ABL & 1) && v[0] != 123.456f) continue;
                 if constexpr (Q == 6 && sizeof(OutT) == 4) {
                     const float n0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[0]), 0xB1, 0xF, 0xF, false));
                     const float n1 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[1]), 0xB1, 0xF, 0xF, false));
@@ -907,186 +796,10 @@ __global__ __launch_bounds__(64) void kernel_fwd_split_kernel(const float* __res
     }
 }
 
-// ---- forward, "run" variant: 16-byte stores ------------------------------------------------------------------------
-// The pair kernel above is store-ISSUE bound (ablation, K_ZX at C4: 121 us, 89 without the stores, 87 without the MFMA
-// product, 94 without the P2 loads, 49 without stores and MFMA): every lane writes its 6 x 6 micro-block as 18 8-byte pieces.
-// Here a lane owns a RUN of 12 consecutive output columns (two micro-blocks at q = 6, four at q = 3) of its Q rows: 48 bytes
-// per row, 16-byte aligned, three dwordx4 stores -- half the store instructions per byte.  The tile is 48 rows x TC columns
-// (TC = 96 at q = 6, 48 at q = 3: 64 lanes = 48/Q point rows x TC/12 runs), the packed rows of the NEXT column tile travel
-// through registers while the current one is transformed (the global-load latency no longer sits on the per-tile chain), and
-// the T' tile overlays the P2 image it was computed from (the wave is alone in its workgroup: barriers order the phases).
-#ifndef FWD_RUN_WGS_
-#define FWD_RUN_WGS_ (256 * 12)
-#endif
-#ifndef FWD_RUN
-#define FWD_RUN 0           // measured slower than the pair kernel (128-135 vs 87-123 us for K_ZX at C4): kept for the record, not dispatched
-#endif
-template <typename OutT, int Q>
-__global__ __launch_bounds__(64) void kernel_fwd_run_kernel(const float* __restrict__ P1, const float* __restrict__ self1,
-                                                            int n1q, const float* __restrict__ P2,
-                                                            const float* __restrict__ self2, int n2q, int K4, int DP,
-                                                            const float* __restrict__ hyp, float jitter,
-                                                            OutT* __restrict__ out, int64_t ld) {
-    constexpr int R = 48 / Q, NRUN = 64 / R, PPR = 12 / Q, TC = NRUN * 12, NCT = TC / 16;
-    constexpr int LDTT = TC + 4;                        // T' row stride (floats): rows 16-byte aligned
-    constexpr int NPF = (TC * 32 / 4 + 63) / 64;        // float4 per lane that hold a prefetched P2 tile (DP <= 32)
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int LDP = K4 + 5;
-    float* P1s = smem;                                  // [48][LDP]
-    float* P2s = P1s + 48 * LDP;                        // [TC][LDP], later overlaid by TT [48][LDTT]
-    float* TT = P2s;
-    const int lane = threadIdx.x, m16 = lane & 15, kg = lane >> 4;
-    const int row0 = blockIdx.y * 48;
-    const int ncoltiles = (n2q + TC - 1) / TC;
-    const int KS = K4 / 4 + 1;
-    const int pch = DP / 4;                             // float4 chunks per packed row
-    const float ell = hyp[0], s = hyp[1];
-    const float il = 1.f / ell, il2 = il * il;
-
-    for (int e = lane; e < 48 * LDP; e += 64) P1s[e] = 0.f;
-    WAVE_SYNC();
-    for (int e = lane; e < 48 * K4; e += 64) {
-        const int r = e / K4, k = e - r * K4;
-        if (row0 + r < n1q) P1s[r * LDP + k] = P1[(int64_t)(row0 + r) * DP + k];
-    }
-    if (lane < 48 && row0 + lane < n1q) {
-        const int a = lane % Q;
-        P1s[lane * LDP + K4 + 1] = a == 0 ? 1.f : 0.f;
-        P1s[lane * LDP + K4 + 2] = a == 0 ? 0.f : -self1[row0 + lane];
-    }
-    // this lane's run: point row pi (rows pr0 .. pr0 + Q - 1), columns pc0 .. pc0 + 11 of the tile
-    const int pi = lane / NRUN, run = lane - pi * NRUN;
-    const int pr0 = pi * Q, pc0 = run * 12;
-    const bool rowok = row0 + pr0 < n1q;
-    const float s1r0 = rowok ? self1[row0 + pr0] : 0.f;
-    const int nchunk = TC * pch;                        // float4 chunks of one P2 tile
-
-    f4 pf[NPF];
-    float pself = 0.f;                                  // -self2 of tile row `lane` (+ lane + 64 at TC = 96)
-    float pself2 = 0.f;
-    auto prefetch = [&](int ct) {
-        const int col0 = ct * TC;
-#pragma unroll
-        for (int u = 0; u < NPF; ++u) {
-            const int e = lane + 64 * u;
-            const int r = e / pch, k = (e - r * pch) * 4;
-            pf[u] = f4{0.f, 0.f, 0.f, 0.f};
-            if (e < nchunk && col0 + r < n2q) pf[u] = *reinterpret_cast<const f4*>(P2 + (int64_t)(col0 + r) * DP + k);
-        }
-        pself = (lane < TC && col0 + lane < n2q) ? -self2[col0 + lane] : 0.f;
-        if (TC > 64) pself2 = (lane + 64 < TC && col0 + lane + 64 < n2q) ? -self2[col0 + lane + 64] : 0.f;
-    };
-    int ct = blockIdx.x;
-    if (ct < ncoltiles) prefetch(ct);
-    for (; ct < ncoltiles; ct += gridDim.x) {
-        const int col0 = ct * TC;
-        WAVE_SYNC();                                // the previous tile's T' reads are done: the overlay may be rewritten
-#pragma unroll
-        for (int u = 0; u < NPF; ++u) {
-            const int e = lane + 64 * u;
-            if (e < nchunk) {
-                const int r = e / pch, k = (e - r * pch) * 4;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) P2s[r * LDP + k + t] = pf[u][t];
-            }
-        }
-        WAVE_SYNC();
-        if (lane < TC) {
-            P2s[lane * LDP + K4 + 1] = pself;
-            P2s[lane * LDP + K4 + 2] = (col0 + lane < n2q && lane % Q == 0) ? 1.f : 0.f;
-        }
-        if (TC > 64 && lane + 64 < TC) {
-            P2s[(lane + 64) * LDP + K4 + 1] = pself2;
-            P2s[(lane + 64) * LDP + K4 + 2] = (col0 + lane + 64 < n2q && (lane + 64) % Q == 0) ? 1.f : 0.f;
-        }
-        float s2v[PPR];
-#pragma unroll
-        for (int pp = 0; pp < PPR; ++pp) s2v[pp] = (col0 + pc0 + pp * Q < n2q) ? self2[col0 + pc0 + pp * Q] : 0.f;
-        if (ct + (int)gridDim.x < ncoltiles) prefetch(ct + gridDim.x);       // in flight under everything below
-        WAVE_SYNC();
-        f4 t[3][NCT];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < NCT; ++j) t[i][j] = f4{0.f, 0.f, 0.f, 0.f};
-        {
-            const float* pa = P1s + m16 * LDP + kg;
-            const float* pb = P2s + m16 * LDP + kg;
-            for (int ks = 0; ks < KS; ++ks) {
-                float av[3], bv[NCT];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) av[i] = pa[i * 16 * LDP + ks * 4];
-#pragma unroll
-                for (int j = 0; j < NCT; ++j) bv[j] = pb[j * 16 * LDP + ks * 4];
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < NCT; ++j) t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], t[i][j], 0, 0, 0);
-            }
-        }
-        WAVE_SYNC();                                // every P2 fragment has been read: T' may overlay the image
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < NCT; ++j)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) TT[(i * 16 + kg * 4 + r) * LDTT + j * 16 + m16] = t[i][j][r];
-        WAVE_SYNC();
-        if (rowok && col0 + pc0 < n2q) {
-            float tq[Q][12];
-#pragma unroll
-            for (int a = 0; a < Q; ++a)
-#pragma unroll
-                for (int c4 = 0; c4 < 3; ++c4) {
-                    const f4 v = *reinterpret_cast<const f4*>(TT + (pr0 + a) * LDTT + pc0 + 4 * c4);
-                    tq[a][4 * c4] = v[0]; tq[a][4 * c4 + 1] = v[1]; tq[a][4 * c4 + 2] = v[2]; tq[a][4 * c4 + 3] = v[3];
-                }
-            float val[Q][12];
-#pragma unroll
-            for (int pp = 0; pp < PPR; ++pp) {
-                const int o = pp * Q;
-                const float nn = fmaxf(s1r0 - s2v[pp] - 2.f * tq[0][o], 0.f);       // covar_dist clamps at 0
-                const float k = s * expf(-0.5f * nn);                                // postprocess_rbf, ScaleKernel
-                const float kil = k * il, kil2 = k * il2;
-                const bool diag = jitter != 0.f && (int64_t)row0 + pr0 == (int64_t)col0 + pc0 + o;
-#pragma unroll
-                for (int a = 0; a < Q; ++a) {
-                    if (a == 0) {
-                        val[0][o] = k;
-#pragma unroll
-                        for (int b = 1; b < Q; ++b) val[0][o + b] = tq[0][o + b] * kil;                              // w_b k / ell
-                    } else {
-                        val[a][o] = tq[a][o] * kil;                                                                  // -u_a k / ell
-#pragma unroll
-                        for (int b = 1; b < Q; ++b) val[a][o + b] = (tq[a][o + b] + tq[a][o] * tq[0][o + b]) * kil2;  // (G_ab - u_a w_b) k / ell^2
-                    }
-                    if (diag) val[a][o + a] += jitter;
-                }
-            }
-            OutT* op = out + ((int64_t)row0 + pr0) * ld + col0 + pc0;
-            const int vc = min(12, n2q - (col0 + pc0));                  // valid columns of the run (a multiple of Q)
-            if (vc == 12) {
-                using O4 = OutT __attribute__((ext_vector_type(16 / sizeof(OutT))));
-                constexpr int EPV = 16 / sizeof(OutT);
-#pragma unroll
-                for (int a = 0; a < Q; ++a)
-#pragma unroll
-                    for (int c = 0; c < 12; c += EPV) {
-                        O4 v;
-#pragma unroll
-                        for (int e = 0; e < EPV; ++e) v[e] = (OutT)val[a][c + e];
-                        *reinterpret_cast<O4*>(op + a * ld + c) = v;
-                    }
-            } else {
-#pragma unroll
-                for (int a = 0; a < Q; ++a)
-#pragma unroll
-                    for (int c = 0; c < 12; ++c)
-                        if (c < vc) op[a * ld + c] = (OutT)val[a][c];
-            }
-        }
-    }
-}
+// Tried and removed: a "run" variant of the pair kernel above (a lane owns 12 consecutive output columns of its Q rows: three 16-byte
+// stores per row; the pair kernel is store-ISSUE bound -- ablation, K_ZX at C4: 121 us, 89 without the stores, 87 without the MFMA product,
+// 94 without the P2 loads, 49 without stores and MFMA), measured slower than the pair kernel (128-135 vs 87-123 us for K_ZX at C4, FWD_RUN);
+// removed in the build-variant clean-up; last present in 8a953b7.
 
 __global__ void kernel_diag_kernel(int n, int p, const float* __restrict__ hyp, float* __restrict__ out) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1106,9 +819,6 @@ __global__ void kernel_diag_kernel(int n, int p, const float* __restrict__ hyp, 
 //   4. dP1[Tr, NP] += Tbar[Tr, Tc] . P2ext[Tc, NP] on MFMA, accumulators stay in registers over the sweep.
 // Both passes are q-fold parallel within a micro-block with in-thread reductions only (the earlier
 // one-thread-per-point-pair transform was LDS-latency bound at 4 waves per CU).
-#ifndef BWD_ABLATE
-#define BWD_ABLATE 0      // tools only: bit 0 = no row/column passes, bit 1 = no dP1 MFMA, bit 2 = no T MFMA, bit 3 = no Gbar loads
-#endif
 #ifndef BWD_NT_
 #define BWD_NT_ 384
 #endif
@@ -1192,8 +902,7 @@ __global__ __launch_bounds__(BWD_NT) void kernel_bwd_kernel(const GT* __restrict
         for (int i = 0; i < NCH; ++i) {
             const int e = tid + i * NT;
             const int r = e / gch_row, c = (e - r * gch_row) * 4;
-            if (BWD_ABLATE & 8) greg[i] = f4{1.f, 1.f, 1.f, 1.f};
-            else greg[i] = load_g4(G, ldg, (int64_t)row0 + r, (int64_t)col0 + c, r, c, Tr, Tc, n1q, n2q, vec);
+            greg[i] = load_g4(G, ldg, (int64_t)row0 + r, (int64_t)col0 + c, r, c, Tr, Tc, n1q, n2q, vec);
         }
         if (ppre) {
 #pragma unroll
@@ -1244,7 +953,7 @@ __global__ __launch_bounds__(BWD_NT) void kernel_bwd_kernel(const GT* __restrict
         __syncthreads();
 
         // T = P1s P2s^T
-        for (int id = wave; id < ntr * ntc && !(BWD_ABLATE & 4); id += NW) {
+        for (int id = wave; id < ntr * ntc; id += NW) {
             const int tr = id / ntc, tc = id - tr * ntc;
             f4 t4 = {0.f, 0.f, 0.f, 0.f};
             const float* pa = P1s + (tr * 16 + (lane & 15)) * LDP1 + (lane >> 4);
@@ -1256,7 +965,7 @@ __global__ __launch_bounds__(BWD_NT) void kernel_bwd_kernel(const GT* __restrict
         __syncthreads();
 
         // ROW pass: task = (tile row r = (point pi, slot a), point column pj)
-        for (int task = tid; task < Tr * Rc && !(BWD_ABLATE & 1); task += NT) {
+        for (int task = tid; task < Tr * Rc; task += NT) {
             const int r = fdiv_small(task, invRc), pj = task - r * Rc;
             const int pi = fdiv_small(r, invq), a = r - pi * q;
             const int r0 = pi * q, c0 = pj * q;
@@ -1330,7 +1039,7 @@ __global__ __launch_bounds__(BWD_NT) void kernel_bwd_kernel(const GT* __restrict
         __syncthreads();
 
         // COLUMN pass: task = (point row pi, tile column c = (point pj, slot b))
-        for (int task = tid; task < Rr * Tc && !(BWD_ABLATE & 1); task += NT) {
+        for (int task = tid; task < Rr * Tc; task += NT) {
             const int pi = fdiv_small(task, invTc), c = task - pi * Tc;
             const int pj = fdiv_small(c, invq), b = c - pj * q;
             const int r0 = pi * q;
@@ -1360,7 +1069,7 @@ __global__ __launch_bounds__(BWD_NT) void kernel_bwd_kernel(const GT* __restrict
 #pragma unroll
         for (int si = 0; si < BWD_MAXACC; ++si) {
             const int id = wave + NW * si;
-            if (id < ntr * nnp && !(BWD_ABLATE & 2)) {
+            if (id < ntr * nnp) {
                 const int tr = id / nnp, tn = id - tr * nnp;
                 const float* pa = Gs + (tr * 16 + (lane & 15)) * LDT + (lane >> 4);
                 const float* pb = P2s + (lane >> 4) * LDP + tn * 16 + (lane & 15);
@@ -1418,20 +1127,14 @@ constexpr int PAIR_LDT = 52;     // LDS row stride of the 48 x 48 T' / Tbar tile
 #ifndef PAIR_WGS_
 #define PAIR_WGS_ (256 * 8)       // 8 waves per CU (registers: 2 per SIMD; LDS: 16 KB per wave); 7 / 8 / 9 / 10 / 12: 169 / 157 / 262 / 246 / 225 us
 #endif
-#ifndef PAIR_ABLATE
-#define PAIR_ABLATE 0      // tools only: bit 0 = no transform, bit 1 = no dP1 MFMA, bit 2 = no T' MFMA, bit 3 = no Gbar loads
-#endif
 constexpr int PAIR_WGS = PAIR_WGS_;
 
 #ifndef BWDP_MINW
 #define BWDP_MINW 2        // waves per SIMD the register allocation leaves room for: 2 (<= 256 VGPRs; the micro-block transform holds
 #endif                     // 36 upstream + 36 T' + 24 A-fragment + 24 accumulator registers); 3 (<= 168) spills: 270 us instead of 157
-#ifndef BWDP_LEAN
-#define BWDP_LEAN 1        // tiles inside the matrix: packed side-2 rows fetched and staged without predicates (142 -> 138 us; the same for
-#endif                     // the upstream micro-block loads measured SLOWER: 167 us)
-#ifndef BWDP_PREFETCH
-#define BWDP_PREFETCH 0    // 1: the next tile's packed side-2 rows travel through registers under the current tile (36 more registers,
-#endif                     //    same time at 8 waves per CU: 157 us either way)
+// Tiles inside the matrix: packed side-2 rows fetched and staged without predicates (142 -> 138 us; the same for the upstream micro-block loads
+// measured SLOWER: 167 us).  Tried and removed: the next tile's packed side-2 rows travelling through registers under the current tile
+// (BWDP_PREFETCH: 36 more registers, same time at 8 waves per CU, 157 us either way); removed in the build-variant clean-up; last present in 8a953b7.
 // KSM: as for kernel_fwd_pair_kernel (8: DP <= 32, 16: DP <= 64); the dP1 accumulators cover NP = 4 KSM packed columns
 template <typename GT, int Q, int KSM = 8>
 __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_kernel(const GT* __restrict__ G, int64_t ldg,
@@ -1493,7 +1196,7 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
     float pselfv = 0.f;
     auto prefetch = [&](int ct_) {
         const int c0_ = ct_ * T;
-        if (BWDP_LEAN && c0_ + T <= n2q) {               // a tile inside the matrix: no predicates
+        if (c0_ + T <= n2q) {               // a tile inside the matrix: no predicates
             const f4* src = reinterpret_cast<const f4*>(P2 + (int64_t)c0_ * DP);
 #pragma unroll
             for (int u = 0; u < NPFP; ++u) pf[u] = src[pf_e[u]];
@@ -1528,7 +1231,6 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
         for (int j = 0; j < NNP; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
     float sK_sum = 0.f, l_acc = 0.f;
 
-    if (BWDP_PREFETCH && (int)blockIdx.x < ncoltiles) prefetch(blockIdx.x);
     for (int ct = blockIdx.x; ct < ncoltiles; ct += gridDim.x) {
         const int col0 = ct * T;
         // upstream micro-blocks straight into registers (consumed after the T' product)
@@ -1536,7 +1238,7 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
         float s2c0[PPL];
 #pragma unroll
         for (int pp = 0; pp < PPL; ++pp) {
-            const bool ok = prow[pp] && col0 + pc0[pp] < n2q && !(PAIR_ABLATE & 8);
+            const bool ok = prow[pp] && col0 + pc0[pp] < n2q;
             const GT* src = G + (int64_t)(row0 + pr0[pp]) * ldg + col0 + pc0[pp];
             s2c0[pp] = ok ? self2[col0 + pc0[pp]] : 0.f;
 #pragma unroll
@@ -1557,7 +1259,7 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
             }
         }
         WAVE_SYNC();   // (single wave: orders the previous tile's MFMA reads of P2s / TT before the new stores)
-        if (!BWDP_PREFETCH) prefetch(ct);
+        prefetch(ct);
 #pragma unroll
         for (int u = 0; u < NPFP; ++u) {               // (lanes past the end of the tile: the scratch row)
 #pragma unroll
@@ -1568,12 +1270,11 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
             P2s[lane * LDP + K4 + 1] = pselfv;
             P2s[lane * LDP + K4 + 2] = (col0 + lane < n2q && lane % Q == 0) ? 1.f : 0.f;
         }
-        if (BWDP_PREFETCH && ct + (int)gridDim.x < ncoltiles) prefetch(ct + gridDim.x);      // in flight under the rest of this tile
         WAVE_SYNC();
 
         // T' = P1' P2'^T : 3 x 3 tiles of 16 x 16, K = K4 + 4  (one straight-line copy per K depth: no per-step branches, the
         // first product starts from the inline zero)
-        if (!(PAIR_ABLATE & 4)) {
+        {
             f4 t[3][3];
             const float* pb = P2s + m16 * LDP + kg;
             auto product = [&](auto ksc) {
@@ -1626,7 +1327,7 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
         // micro-block transform in registers
 #pragma unroll
         for (int pp = 0; pp < PPL; ++pp) {
-            if (lane + 64 * pp < NPAIR && !(PAIR_ABLATE & 1)) {
+            if (lane + 64 * pp < NPAIR) {
                 float* blk = TT + pr0[pp] * LDT2 + pc0[pp];
                 float tq[Q][Q];
 #pragma unroll
@@ -1699,8 +1400,7 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
         }
         WAVE_SYNC();
 
-        // dP1[48, NP] += Tbar[48, 48] . P2ext[48, NP]
-        if (!(PAIR_ABLATE & 2)) {
+        {   // dP1[48, NP] += Tbar[48, 48] . P2ext[48, NP]
             const float* pa = TT + m16 * LDT2 + kg;
             const float* pb = P2s + kg * LDP + m16;
 #pragma unroll
@@ -1757,14 +1457,8 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
 // register prefetch of the next tile), 93 at 1024 waves; phase ablations at 1024 waves: no transform 75, no dP1 product 61, no T'
 // product 83, no upstream loads 79, none of them 23 -- the phases ADD UP (one wave per SIMD: nothing overlaps them), which is what
 // keeps it at 0.10 of the HBM roof.  Kept because it is the fastest of the three; the backward of wide micro-blocks is an open item.
-#ifndef BWDS_PREFETCH
-#define BWDS_PREFETCH 0
-#endif
 #ifndef BWDS_WGS
 #define BWDS_WGS (256 * 4)
-#endif
-#ifndef BWDS_ABL
-#define BWDS_ABL 0         // tools only (wrong results): bit 0 = no transform, 1 = no dP1 MFMA, 2 = no T' MFMA, 3 = no upstream loads
 #endif
 template <typename GT, int Q, int KSM>
 __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restrict__ G, int64_t ldg, const float* __restrict__ P1,
@@ -1827,7 +1521,7 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
         for (int u = 0; u < NGF; ++u) {
             const int id = lane + 64 * u, r = id / C4, c = (id - C4 * r) * 4;
             f4 v = {0.f, 0.f, 0.f, 0.f};
-            if (id < T * C4 && !(BWDS_ABL & 8)) {
+            if (id < T * C4) {
                 const GT* src = G + (int64_t)(row0 + r) * ldg + c0_ + c;
                 if (interior && gvec) {
                     if constexpr (sizeof(GT) == 4) {
@@ -1852,13 +1546,12 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
             if (e < T * pch && c0_ + r < n2q) pf[u] = *reinterpret_cast<const f4*>(P2 + (int64_t)(c0_ + r) * DP + k);
         }
     };
-    if (BWDS_PREFETCH && (int)blockIdx.x < ncoltiles) prefetch(blockIdx.x);
     for (int ct = blockIdx.x; ct < ncoltiles; ct += gridDim.x) {
         const int col0 = ct * T;
         const bool colok = prow && col0 + pc0 < n2q;
         const float s2c0 = colok ? self2[col0 + pc0] : 0.f;
         WAVE_SYNC();                                   // (single wave: the previous tile's MFMA reads of P2s / TT are done)
-        if (!BWDS_PREFETCH) prefetch(ct);
+        prefetch(ct);
 #pragma unroll
         for (int u = 0; u < NGF; ++u) {
             const int id = lane + 64 * u, r = id / C4, c = (id - C4 * r) * 4;
@@ -1872,7 +1565,6 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
                 for (int t = 0; t < 4; ++t) P2s[r * LDP + k + t] = pf[u][t];
             }
         }
-        if (BWDS_PREFETCH && ct + (int)gridDim.x < ncoltiles) prefetch(ct + gridDim.x);
         WAVE_SYNC();
         if (lane < T) {
             const bool ok = col0 + lane < n2q;
@@ -1880,7 +1572,7 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
             P2s[lane * LDP + K4 + 2] = (ok && lane % Q == 0) ? 1.f : 0.f;
         }
         WAVE_SYNC();
-        if (!(BWDS_ABL & 4)) {   // T' = P1' P2'^T
+        {   // T' = P1' P2'^T
             f4 t[3][3];
             const float* pb = P2s + m16 * LDP + kg;
 #pragma unroll
@@ -1907,7 +1599,6 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
         // ---- micro-block transform (kernel_bwd_pair_kernel's arithmetic), rows split over the four lanes of a pair
         float* blk = TT + pr0 * LDT2 + pc0;
         const float* gb = GG + pr0 * LDG + pc0;
-        if (!(BWDS_ABL & 1)) {
         float t0[Q], g0[Q], ta[RPL][Q], ga[RPL][Q];
 #pragma unroll
         for (int b = 0; b < Q; ++b) { t0[b] = blk[b]; g0[b] = colok ? gb[b] : 0.f; }
@@ -1972,9 +1663,8 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
             sK_sum += t00;
             l_acc += k * (e1 + 2.f * e2) - t00 * nn + dots;
         }
-        }
         WAVE_SYNC();
-        if (!(BWDS_ABL & 2)) {   // dP1[48, NP] += Tbar[48, 48] . P2ext[48, NP]
+        {   // dP1[48, NP] += Tbar[48, 48] . P2ext[48, NP]
             const float* pa = TT + m16 * LDT2 + kg;
             const float* pb = P2s + kg * LDP + m16;
 #pragma unroll
@@ -2281,11 +1971,7 @@ inline int finish_points(dsvgp_ctx* ctx, const Geom& g, const float* slab, int n
 }
 
 inline bool bwd_use_pair(const Geom& g) { return (g.q == 6 || g.q == 3) && g.NP <= 64; }     // (NP <= 32: KSM = 8; <= 64: KSM = 16)
-#ifdef BWD_NO_SPLIT
-inline bool bwd_use_split(const Geom&) { return false; }
-#else
 inline bool bwd_use_split(const Geom& g) { return g.q == 11 && g.NP <= 16; }                  // (full-gradient SVGP at d <= 12: BASELINE config 3)
-#endif
 // row-tile height / column-tile width / workgroup budget of the backward variant that will run
 inline void bwd_tiles(const Geom& g, int& tr, int& tc, int& wgs) {
     if (bwd_use_split(g)) { tr = tc = (48 / g.q) * g.q; wgs = BWDS_WGS; }
@@ -2317,9 +2003,7 @@ inline void dispatch_bwd(hipStream_t st, dim3 grid, size_t lds, const GT* G, int
     const int Trp = (g.Tr + 15) & ~15;
     if (Trp > 48) launch_bwd<GT, 0, BWD_GCH_MAX>(st, grid, lds, G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);
     else if (g.q == 4) launch_bwd<GT, 4, BWD_GCH>(st, grid, lds, G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);
-#ifndef BWD_NO_Q11
     else if (g.q == 11) launch_bwd<GT, 11, BWD_GCH>(st, grid, lds, G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);   // (full-gradient SVGP at d = 10: BASELINE config 3)
-#endif
     else launch_bwd<GT, 0, BWD_GCH>(st, grid, lds, G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);
 }
 
@@ -2346,24 +2030,8 @@ constexpr int CAN_LDT = 52;            // row stride of the 48 x 48 output / ups
 #ifndef CAN_BWD_WGS
 #define CAN_BWD_WGS (256 * 8)
 #endif
-#ifndef CAN_BWD_DMA
-#define CAN_BWD_DMA 1                  // 0: the backward kernel reads the upstream micro-blocks straight into registers (tools: the A/B)
-#endif
-#ifndef CAN_FWD_NT
-#define CAN_FWD_NT 1                   // a result larger than the memory-side cache leaves as NON-TEMPORAL stores (ovec bit 2, set by the launcher from 192 MB up): written
-                                       // once, read by the forward solve a millisecond later, whatever of it is cached by then (cold result buffer: 77 -> 69 us at C4)
-#endif
-#ifndef CAN_BWD_NT
-#define CAN_BWD_NT 0                   // 1: the upstream tile's LDS-DMA loads with the nt bit (probe)
-#endif
-#ifndef CAN_FWD_STRIDED
-#define CAN_FWD_STRIDED 1
-#endif
 #ifndef CAN_FWD_MINW
 #define CAN_FWD_MINW 2                 // waves per SIMD the forward kernel's registers are budgeted for
-#endif
-#ifndef CAN_ABL
-#define CAN_ABL 0                      // tools only (results wrong): 1 = no global stores (forward), 2 = no U product, 4 = whole cache lines only (2/3 of the bytes)
 #endif
 
 // what both kernels share: the A fragments of the wave's 48 side-1 rows (self terms folded as in the pair kernels: column K4 + 2 of P1' =
@@ -2432,15 +2100,14 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
     const int pch = DP / 4;                 // float4 per packed row
     const bool rows_full = row0 + T <= n1q;
 
-    // Column tiles of a workgroup: blockIdx.x, + gridDim.x, ... (CAN_FWD_STRIDED = 1: at any moment the workgroups of a row tile write
+    // Column tiles of a workgroup: blockIdx.x, + gridDim.x, ... (at any moment the workgroups of a row tile write
     // ADJACENT 192-byte pieces of the same 48 rows -- whole cache lines and DRAM pages fill up together; in contiguous chunks per workgroup
     // the pieces written at one time lie 2 KB apart, which costs nothing while the result is still in the memory-side cache from the launch
     // before (what a probe that rewrites one buffer sees: 62 us) and a third of the rate when it is not (the step: 87 us) --
     // profiles/r06_c_canon_assembly.txt)
-    const int cper = (ncoltiles + (int)gridDim.x - 1) / (int)gridDim.x;
-    const int ct_step = CAN_FWD_STRIDED ? (int)gridDim.x : 1;
-    const int ct_lo = CAN_FWD_STRIDED ? (int)blockIdx.x : (int)blockIdx.x * cper;
-    const int ct_hi = CAN_FWD_STRIDED ? ncoltiles : min(ct_lo + cper, ncoltiles);
+    const int ct_step = (int)gridDim.x;
+    const int ct_lo = (int)blockIdx.x;
+    const int ct_hi = ncoltiles;
     // the tile's R value rows of P2: float4 number e = lane (< R pch <= 128: two per lane at most) of [R][DP]
     f4 pf[2];
     float pnrm = 0.f;
@@ -2498,7 +2165,7 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
                         t[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv, ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i], 0, 0, 0);
                 }
             };
-            switch ((CAN_ABL & 2) ? 1 : KS) {
+            switch (KS) {
                 case 1: product(std::integral_constant<int, 1>{}); break;
                 case 2: product(std::integral_constant<int, 2>{}); break;
                 case 3: product(std::integral_constant<int, 3>{}); break;
@@ -2566,9 +2233,7 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
             for (int u = 0; u < 9; ++u) {   // the tile leaves as nine fully coalesced 16-byte store instructions (rows of 192 bytes)
                 const int id = lane + 64 * u, r = id / 12, c4 = (id - 12 * r) * 4;
                 const f4 x = *reinterpret_cast<const f4*>(TT + r * CAN_LDT + c4);
-                if ((CAN_ABL & 4) && ((ct & 1) ? c4 < 16 : c4 >= 32)) continue;   // (tools: only the whole 128-byte line of each row piece)
-                if (CAN_ABL & 1) continue;
-                if (CAN_FWD_NT && (ovec & 4)) __builtin_nontemporal_store(x, reinterpret_cast<f4*>(orow + (int64_t)r * ld + c4));
+                if (ovec & 4) __builtin_nontemporal_store(x, reinterpret_cast<f4*>(orow + (int64_t)r * ld + c4));
                 else *reinterpret_cast<f4*>(orow + (int64_t)r * ld + c4) = x;
             }
         } else {
@@ -2595,13 +2260,8 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
 // set and restored inside the statement.
 __device__ __forceinline__ void can_dma16(const float* gsrc, unsigned lds_byte_addr) {
     unsigned keep;
-#if CAN_BWD_NT
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr) : "memory");
-#else
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_byte_addr) : "memory");
-#endif
 }
 
 // backward: upstream micro-blocks HBM -> registers, the pair kernel's transform with (w_b, -u_a, G_ab) from the canonical sources;
@@ -2973,7 +2633,7 @@ extern "C" int dsvgp_kernel_fwd_canon(dsvgp_ctx* ctx, const float* P1, const flo
     if (ns > ctiles) ns = ctiles;
     const size_t lds = sizeof(float) * (((16 * (size_t)(g.K4 + 5) + 3) & ~(size_t)3) + 48 * (size_t)CAN_LDT);
     const int ovec = ((ld % 4 == 0 && (uintptr_t)out % 16 == 0) ? 2 : 0) |
-                     ((size_t)n1q * (size_t)n2 * g.q * sizeof(float) >= ((size_t)192 << 20) ? 4 : 0);      // (bit 2: non-temporal stores, CAN_FWD_NT)
+                     ((size_t)n1q * (size_t)n2 * g.q * sizeof(float) >= ((size_t)192 << 20) ? 4 : 0);      // (bit 2: non-temporal stores: a result larger than the memory-side cache is written once and read by the forward solve a millisecond later, whatever of it is cached by then -- cold result buffer: 77 -> 69 us at C4)
     dim3 grid(ns, rt);
     if (g.q == 6)
         hipLaunchKernelGGL((kernel_fwd_canon_kernel<6>), grid, dim3(64), lds, ctx->stream, P1, self1, n1q, P2, self2, n2, g.K4, g.DP, dir_idx,
@@ -3006,7 +2666,7 @@ extern "C" int dsvgp_kernel_bwd_canon(dsvgp_ctx* ctx, const void* G, int64_t ldg
     float* partials = slab + (size_t)bwd_nsplit(n1, n2, g) * n1q * g.NP;
     const int esz = g_is_double ? 8 : 4;
     const int gvec = (ldg % 2 == 0) && ((uintptr_t)G % (2 * esz) == 0);
-    const bool dma = CAN_BWD_DMA && !g_is_double && ldg % 4 == 0 && (uintptr_t)G % 16 == 0;       // (16-byte pieces of the upstream rows)
+    const bool dma = !g_is_double && ldg % 4 == 0 && (uintptr_t)G % 16 == 0;       // (16-byte pieces of the upstream rows)
     const size_t lds = sizeof(float) * (((16 * (size_t)(g.NP + 1) + 3) & ~(size_t)3) + 16 * (size_t)CAN_LDT + 48 * 8 + (dma ? 48 * 48 : 0));
     dim3 grid(ns, rt);
 #define DSVGP_CANON_BWD(GT_, Q_, DMA_)                                                                                                  \
@@ -3136,7 +2796,7 @@ __global__ __launch_bounds__(64) void kernel_bwd_canon2_kernel(const GT* __restr
     const bool lane_on = i < RP;            // (double upstream: 32 pairs per tile)
     const int ii = lane_on ? i : 0;
     const int p0 = blockIdx.y * RP;
-    const int64_t n1q = (int64_t)n1 * Q, n2q = (int64_t)n2 * Q;
+    const int64_t n1q = (int64_t)n1 * Q;
     const int ncoltiles = (n2 + CP - 1) / CP;
     const float ell = hyp[0], s = hyp[1];
     const float il = 1.f / ell, il2 = il * il;
@@ -3453,30 +3113,6 @@ extern "C" int dsvgp_kernel_fwd(dsvgp_ctx* ctx, const float* P1, const float* se
     const int n1q = n1 * g.q, n2q = n2 * g.q;
     if (ld < n2q) return DSVGP_EINVAL;
     if (geom_wide(g)) return launch_kernel_fwd_wide(ctx->stream, P1, self1, n1q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
-    if (FWD_RUN && (g.q == 6 || g.q == 3) && g.NP <= 32 && n1q % g.q == 0) {
-        // "run" kernel (16-byte stores): needs 16-byte aligned rows of the output
-        const int esz = out_is_double ? 8 : 4;
-        const bool aligned = (ld * esz) % 16 == 0 && (uintptr_t)out % 16 == 0;
-        if (aligned) {
-            const int TC = g.q == 6 ? 96 : 48;
-            const int rt = cdiv(n1q, 48), ctiles = cdiv(n2q, TC);
-            int ns = FWD_RUN_WGS_ / rt;
-            if (ns < 1) ns = 1;
-            if (ns > ctiles) ns = ctiles;
-            const size_t p2w = (size_t)TC * (g.K4 + 5), ttw = (size_t)48 * (TC + 4);
-            const size_t lds = sizeof(float) * (48 * (size_t)(g.K4 + 5) + (p2w > ttw ? p2w : ttw));
-            dim3 grid(ns, rt);
-#define DSVGP_FWD_RUN(OT_, Q_)                                                                                       \
-            hipLaunchKernelGGL((kernel_fwd_run_kernel<OT_, Q_>), grid, dim3(64), lds, ctx->stream, P1, self1, n1q, P2, self2, \
-                               n2q, g.K4, g.DP, hyp, jitter, (OT_*)out, ld)
-            if (out_is_double) { if (g.q == 6) DSVGP_FWD_RUN(double, 6); else DSVGP_FWD_RUN(double, 3); }
-            else { if (g.q == 6) DSVGP_FWD_RUN(float, 6); else DSVGP_FWD_RUN(float, 3); }
-#undef DSVGP_FWD_RUN
-            DSVGP_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-#ifndef FWD_NO_SPLIT
     if (g.q == 11 && g.K4 <= 12) {      // full-gradient SVGP at d <= 12 (BASELINE config 3): the split-row kernel
         const int T = 44;
         const int rt = cdiv(n1q, T), ctiles = cdiv(n2q, T);
@@ -3496,7 +3132,6 @@ extern "C" int dsvgp_kernel_fwd(dsvgp_ctx* ctx, const float* P1, const float* se
         DSVGP_LAUNCH_CHECK();
         return 0;
     }
-#endif
     if ((g.q == 6 || g.q == 3) && g.NP <= 64) {
         const int T = (48 / g.q) * g.q;
         const int rt = cdiv(n1q, T), ctiles = cdiv(n2q, T);
@@ -3504,12 +3139,11 @@ extern "C" int dsvgp_kernel_fwd(dsvgp_ctx* ctx, const float* P1, const float* se
         if (ns < 1) ns = 1;
         if (ns > ctiles) ns = ctiles;
         const size_t p2w_ = 49 * (size_t)(g.K4 + 5), ttw_ = 48 * (size_t)FWD_PAIR_LDT;        // (49: the scratch row of the predicate-free staging)
-        const size_t lds = FWDP_LDS_EXTRA + sizeof(float) * (FWDP_OVERLAY ? (FWDP_AREG ? 0 : 48 * (size_t)(g.K4 + 5)) + (p2w_ > ttw_ ? p2w_ : ttw_)
-                                                         : 2 * 48 * (size_t)(g.K4 + 5) + 48 * (size_t)FWD_PAIR_LDT);
+        const size_t lds = sizeof(float) * (p2w_ > ttw_ ? p2w_ : ttw_);        // (T' overlays the P2 image)
         const int esz = out_is_double ? 8 : 4;
         // bit 0: 2-wide stores of the micro-block rows; bit 1: 16-byte stores of lane pairs (float output, 16-byte aligned rows)
         const int ovec = (((ld % 2 == 0) && ((uintptr_t)out % (2 * esz) == 0)) ? 1 : 0) |
-                         ((!out_is_double && ld % 4 == 0 && (uintptr_t)out % 16 == 0 && FWDP_ST16) ? 2 : 0) |
+                         ((!out_is_double && ld % 4 == 0 && (uintptr_t)out % 16 == 0) ? 2 : 0) |
                          ((ctx->fwd_lower_only && P1 == P2 && n1 == n2) ? 8 : 0);       // (bit 3: the block triangle the Cholesky factorisation reads)
         dim3 grid(ns, rt);
 #define DSVGP_FWD_PAIR(OT_, Q_, KSM_)                                                                                \

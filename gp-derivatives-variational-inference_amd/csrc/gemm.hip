@@ -17,9 +17,6 @@
 #include "common.h"
 
 // tuning / ablation knobs for tools/gemm_probe (defaults = the shipped configuration)
-#ifndef GEMM_ABLATE
-#define GEMM_ABLATE 0      // 1: no MFMA (loads + LDS only), 2: no global loads inside the K loop
-#endif
 #ifndef GEMM_BK_F32
 #define GEMM_BK_F32 32      // 32-deep fp32 stages: twice the MFMA work behind every fetch (dense 101.8 -> 108.9 TF; 16 for the ablation probes)
 #endif
@@ -34,18 +31,6 @@
 #endif
 #ifndef GEMM_MIN_CHUNK
 #define GEMM_MIN_CHUNK 16     // smallest XCD dealing unit (workgroups)
-#endif
-#ifndef GEMM_XCD
-#define GEMM_XCD 1
-#endif
-#ifndef GEMM_PIPE
-#define GEMM_PIPE 0         // 1: next stage's LDS stores + the following global fetch are issued BEFORE the MFMA block
-#endif
-#ifndef GEMM_FRAGPF
-#define GEMM_FRAGPF 0       // 1: fragments of k-step kk+1 are read from LDS before the MFMAs of k-step kk
-#endif
-#ifndef GEMM_PRIO
-#define GEMM_PRIO 1         // 1: raise the wave priority for the MFMA block of a stage (inter-wave phase separation: +1-2 % on the fp32 products, neutral on fp64); 0 off
 #endif
 #ifndef GEMM_MINW
 #define GEMM_MINW 0         // tools: override the min-waves-per-SIMD launch bound (0 = NTH / 128)
@@ -64,17 +49,9 @@ extern "C" int dsvgp_debug_gemm_clock(unsigned long long* out) {
 namespace {
 
 constexpr int BM_MAX = 128;  // BN (128 or 64) and BM (128 or 64) are template parameters
-#ifndef GEMM_BM64
-#define GEMM_BM64 0         // tools: 1 = 64-row tiles on 4-wave workgroups for products without OUT_LOWER
-#endif
 #ifndef GEMM_SMALL_LIMIT
 #define GEMM_SMALL_LIMIT 384   // (128 x 128 tiles) x (coarse split-K slices) below which a product counts as small
 #endif
-#ifndef GEMM_SMALL
-#define GEMM_SMALL 1        // 64 x 64 tiles on 4-wave workgroups (+ finer split-K) for products too small to fill the chip with
-                            // 128 x 128 tiles (M' of a few hundred: the reference's own test sizes)
-#endif
-constexpr int S_MN = 144;
 
 template <typename T> struct Mfma;
 template <> struct Mfma<float> {
@@ -180,7 +157,7 @@ __global__ __launch_bounds__(NTH, GEMM_MINW ? GEMM_MINW : NTH / 128) void gemm_k
     // stage out of its private 4 MiB L2 instead of 64 + 64 from HBM / Infinity Cache.
     const int gx = g.tiles_n, gy = g.tiles_m;
     int tm, tn, zz;
-    if (g.supertile && GEMM_XCD) {
+    if (g.supertile) {
         // The ACTIVE tiles (all of them, or for OUT_LOWER on a square grid the T(T+1)/2 on / below the diagonal) x
         // batch x split-K slices are enumerated supertile-major -- 64 consecutive entries share ~8 + 8 operand panels --
         // and dealt to the XCDs in chunks of g.chunk entries, so every XCD gets the same number of workgroups
@@ -320,14 +297,6 @@ __global__ __launch_bounds__(NTH, GEMM_MINW ? GEMM_MINW : NTH / 128) void gemm_k
         for (int k0 = klo; k0 < khi; k0 += BK) {
             const TC* as = As[cur];
             const TC* bs = Bs[cur];
-            if (GEMM_PIPE && k0 + BK < khi) {
-                // stage k0+BK (in registers since one MFMA block ago) goes to the other buffer now -- all waves passed
-                // the barrier after their last reads of it -- and the loads of stage k0+2BK are issued, so that
-                // nothing but the barrier separates this stage's MFMA block from the next one
-                store_stage<TC, TC, AKC, BK, BM, NTH>(As[cur ^ 1], ra, ks);
-                store_stage<TB, TC, BKC, BK, BN, NTH>(Bs[cur ^ 1], rb, TC(1));
-                if (GEMM_ABLATE != 2 && k0 + 2 * BK < khi) fetch(k0 + 2 * BK);
-            }
             auto frag = [&](int kk, TC (&a)[MI], TC (&b)[NJ]) {
                 const int kq = kk * 4 + (lane >> 4);
 #pragma unroll
@@ -341,33 +310,26 @@ __global__ __launch_bounds__(NTH, GEMM_MINW ? GEMM_MINW : NTH / 128) void gemm_k
                     b[j] = BKC ? bs[nn * SK + kq] : bs[kq * SB + nn];
                 }
             };
+            // (two-deep arrays of which half is used: what is left of a fragment prefetch that lost, GEMM_FRAGPF.  Single-deep arrays compile
+            //  to the same instructions in another order and with other registers in all 30 instances, so the shape stays)
             TC a[2][MI], b[2][NJ];
-            if (GEMM_PRIO == 1) __builtin_amdgcn_s_setprio(1);
-            if (GEMM_PRIO == 2) { if ((blockIdx.x >> 3) & 1) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1); }
-            if (GEMM_FRAGPF) frag(0, a[0], b[0]);
+            __builtin_amdgcn_s_setprio(1);      // inter-wave phase separation: +1-2 % on the fp32 products, neutral on fp64
 #pragma unroll
             for (int kk = 0; kk < BK / 4; ++kk) {
-                const int cb = GEMM_FRAGPF ? (kk & 1) : 0;
-                if (GEMM_FRAGPF) { if (kk + 1 < BK / 4) frag(kk + 1, a[cb ^ 1], b[cb ^ 1]); }
-                else frag(kk, a[0], b[0]);
+                frag(kk, a[0], b[0]);
 #pragma unroll
                 for (int i = 0; i < MI; ++i)
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        if (GEMM_ABLATE == 1) { asm volatile("" :: "v"(a[cb][i]), "v"(b[cb][j])); }
-                        else acc[i][j] = M::mma(a[cb][i], b[cb][j], acc[i][j]);
-                    }
+                    for (int j = 0; j < NJ; ++j) acc[i][j] = M::mma(a[0][i], b[0][j], acc[i][j]);
             }
-            if (GEMM_PRIO) __builtin_amdgcn_s_setprio(0);
+            __builtin_amdgcn_s_setprio(0);
             if (k0 + BK < khi) {
-                if (!GEMM_PIPE) {
-                    // stage k0+BK (already in registers) goes to the other buffer: nobody reads it any more,
-                    // all waves passed the previous barrier after their last reads of it
-                    store_stage<TC, TC, AKC, BK, BM, NTH>(As[cur ^ 1], ra, ks);
-                    store_stage<TB, TC, BKC, BK, BN, NTH>(Bs[cur ^ 1], rb, TC(1));
-                }
+                // stage k0+BK (already in registers) goes to the other buffer: nobody reads it any more,
+                // all waves passed the previous barrier after their last reads of it
+                store_stage<TC, TC, AKC, BK, BM, NTH>(As[cur ^ 1], ra, ks);
+                store_stage<TB, TC, BKC, BK, BN, NTH>(Bs[cur ^ 1], rb, TC(1));
                 __syncthreads();
-                if (!GEMM_PIPE && GEMM_ABLATE != 2 && k0 + 2 * BK < khi) fetch(k0 + 2 * BK);
+                if (k0 + 2 * BK < khi) fetch(k0 + 2 * BK);
                 cur ^= 1;
             }
         }
@@ -412,13 +374,11 @@ __global__ __launch_bounds__(NTH, GEMM_MINW ? GEMM_MINW : NTH / 128) void gemm_k
 template <typename TC, typename TB, bool AKC, bool BKC, int BN>
 int launch_one(hipStream_t st, const GemmArgs& g, dim3 grid) {
     constexpr int NTH = (sizeof(TC) == 8 && AKC && BKC) ? 256 : GEMM_THREADS;
-#if GEMM_BM64 || GEMM_SMALL
     if (g.bm == 64) {
         hipLaunchKernelGGL((gemm_kernel<TC, TB, AKC, BKC, BN, 256, 64>), grid, dim3(256), 0, st, g);
         DSVGP_LAUNCH_CHECK();
         return 0;
     }
-#endif
     size_t pad = 0;
     if (g.flags & DSVGP_GEMM_BACKGROUND) {
         // filler product next to a latency-bound chain on another stream: ONE workgroup per CU (dynamic LDS padding up to
@@ -515,17 +475,8 @@ hipError_t zero_block(void* C, size_t esz, int64_t ld, int M, int N, hipStream_t
     return hipGetLastError();
 }
 
-#ifndef GEMM64
-#define GEMM64 1            // 1: fp64 products with two mn-contiguous operands and >= GEMM64_MIN_TILES 64 x 64 tiles go to gemm64.hip
-#endif
-#ifndef GEMM32
-#define GEMM32 1            // 1: plain fp32 products (no triangular operands / Cin / kscale) go to gemm32.hip (32x32x2 MFMA)
-#endif
 #ifndef GEMM64_MIN_TILES
 #define GEMM64_MIN_TILES 1024      // (below: 128 x 128 tiles + split-K of this file)
-#endif
-#ifndef GEMM64_SMALL
-#define GEMM64_SMALL 1
 #endif
 #ifndef GEMM64_SMALL_MIN_TILES
 #define GEMM64_SMALL_MIN_TILES 200     // (from 200 tiles: the forward solve of a small problem, 240 tiles at C2, 48 -> 37 us; the 100-tile M'^3 products are FASTER on split-K here: C2 0.545 -> 0.574 ms with them on the pipelined form)
@@ -537,14 +488,11 @@ hipError_t zero_block(void* C, size_t esz, int64_t ld, int M, int N, hipStream_t
 int launch_gemm(hipStream_t st, int is_double, const GemmArgs& g) {
     if (g.M <= 0 || g.N <= 0) return 0;
     if (g.batch < 1 || g.splitk < 1) return DSVGP_EINVAL;
-#if GEMM64
     if (is_double && (g.C || g.C32) && (int64_t)cdiv(g.M, 64) * cdiv(g.N, 64) >= GEMM64_MIN_TILES && g.K >= GEMM64_MIN_K) {
         const int rc = launch_gemm64(st, g);
         if (rc == 1) return 0;
         if (rc > 1) return rc;
     }
-#endif
-#if GEMM64 && GEMM64_SMALL
     // small problems (M' of a few hundred): 64 .. 1023 tiles with a K chain of >= 256 -- the four-buffer pipelined kernel of gemm64.hip (the chain runs at
     // the pace of its MFMAs) instead of split-K over fp64 atomics + a conversion pass here
     if (is_double && (g.C || g.C32) && !g.slab && !g.tri_off && !g.wide64 && (int64_t)cdiv(g.M, 64) * cdiv(g.N, 64) >= GEMM64_SMALL_MIN_TILES &&
@@ -555,23 +503,19 @@ int launch_gemm(hipStream_t st, int is_double, const GemmArgs& g) {
         if (rc == 1) return 0;
         if (rc > 1) return rc;
     }
-#endif
     if (g.tri_off || g.wide64) return DSVGP_EINVAL;                 // (row-range pieces exist on gemm64.hip's wide kernel only)
-#if GEMM32
     if (!is_double) {
         const int rc = launch_gemm32(st, g);
         if (rc == 1) return 0;
         if (rc > 1) return rc;
     }
-#endif
     GemmArgs a = g;
     const bool out_lower_ = g.flags & DSVGP_GEMM_OUT_LOWER;
-    a.bm = (GEMM_BM64 && !out_lower_ && g.batch == 1) ? 64 : 128;
+    a.bm = 128;
     // tile width: 128 x 64 tiles were measured SLOWER than 128 x 128 + split-K for the M' x M' products
     // (chol. backward 2.9 vs 2.3 ms, Gram 4.1 vs 3.8 ms per step at M'=3000), so 128 is used throughout
     a.bn = g.bn == 64 ? 64 : 128;
     int sk_div = 256, sk_min_k = 512;       // split-K granularity: slices of >= 256 k, only for K >= 512
-#if GEMM_SMALL
     {   // too few 128 x 128 tiles to occupy the 256 CUs even with the coarse split: quarter tiles, slices of >= 128 k
         const int64_t t128 = (int64_t)cdiv(g.M, 128) * cdiv(g.N, 128) * g.batch;
         const int64_t coarse = t128 * (g.K >= 512 ? (g.K / 256 < 32 ? g.K / 256 : 32) : 1);
@@ -582,7 +526,6 @@ int launch_gemm(hipStream_t st, int is_double, const GemmArgs& g) {
             sk_min_k = 256;
         }
     }
-#endif
     const int BM = a.bm;
     a.tiles_m = cdiv(g.M, BM);
     a.tiles_n = cdiv(g.N, a.bn);

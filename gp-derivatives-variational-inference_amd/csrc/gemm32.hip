@@ -32,20 +32,11 @@ constexpr int TM = 128, TN = 128;
 #ifndef G32_BAND
 #define G32_BAND 8          // tile columns per XCD-local band of the dense walk
 #endif
-#ifndef G32_PRIO
-#define G32_PRIO 0
-#endif
 #ifndef G32_DMA_BK
 #define G32_DMA_BK 32       // stage depth of the LDS-DMA kernel (32: two workgroups per CU; 16: three)
 #endif
-#ifndef G32_DMA
-#define G32_DMA 1           // 1: stages by LDS-DMA (gemm32_dma_kernel) where eligible, 0: register staging only
-#endif
 #ifndef G32_MF
 #define G32_MF 32           // MFMA shape of the LDS-DMA kernel: 32 (32x32x2) or 16 (16x16x4)
-#endif
-#ifndef G32_DMAPRIO
-#define G32_DMAPRIO 0
 #endif
 #ifndef G32_SK_BELOW
 #define G32_SK_BELOW 4096   // tile count below which the split-K cost model is consulted (few rounds: a ragged last round costs most)
@@ -55,18 +46,6 @@ constexpr int TM = 128, TN = 128;
 #endif
 #ifndef G32_SK_SLOTS
 #define G32_SK_SLOTS 256    // work units per round in the split-K cost model: one per CU (a CU's matrix pipe is shared by its resident workgroups)
-#endif
-#ifndef G32_SK_MINT
-#define G32_SK_MINT 0
-#endif
-#ifndef G32_TRI_SB
-#define G32_TRI_SB 1        // lower-triangular outputs: super-block edge (tiles) of the walk; 1 = plain row-major triangle.  Measured
-#endif                      // (round 4, tools/gemm32_variants.sh, same box): Gram at C4 2.169 (1) / 2.193 (8) / 2.222 ms (4) -- no gain
-#ifndef G32_XCDK
-#define G32_XCDK 0          // 1: (probe) lower-triangular split-K products in eight K slices, one per XCD -- measured, not kept
-#endif
-#ifndef G32_ABL
-#define G32_ABL 0           // timing ablations (results are WRONG): 1 no global fetch in the loop, 2 no LDS stores, 4 no LDS fragment reads, 8 no barriers
 #endif
 
 struct G32 {
@@ -140,60 +119,24 @@ struct FetchMC {
 };
 
 // which (tile, K slice) this workgroup takes: consecutive blocks of one XCD (b, b + 8, ...) get consecutive units
+// Tried and removed (build-variant clean-up; last present in 8a953b7): the lower triangle walked in SB x SB super-blocks (G32_TRI_SB; round 4,
+// same box: Gram at C4 2.169 (1) / 2.193 (8) / 2.222 ms (4) -- no gain); lower-triangular split-K products in eight K slices, one per XCD
+// (G32_XCDK; round 6, profiles/r06_b_gemm32_gram_xcd.txt: 2.29 -> 2.33-2.35 ms, the launch is not bound by its traffic).
 __device__ __forceinline__ bool pick_unit(const G32& g, int& m0, int& n0, int& kbeg, int& kend) {
-#if G32_XCDK
-    // probe (round 6, profiles/r06_b_gemm32_gram_xcd.txt): a lower-triangular split-K product with EIGHT K slices, slice = the XCD the workgroup
-    // lands on (blocks b, b + 8, ... share one): every XCD's L2 then sees one K slice of the operands only
-    const bool xk = (g.flags & DSVGP_GEMM_OUT_LOWER) && g.splitk == 8;
-    const int u = xk ? 0 : (blockIdx.x >> 3) + (blockIdx.x & 7) * ((gridDim.x + 7) >> 3);
-    if (xk ? (int)(blockIdx.x >> 3) >= g.ntiles : u >= g.ntiles * g.splitk) return false;
-    const int slice = xk ? (int)(blockIdx.x & 7) : u / g.ntiles;
-    const int t = xk ? (int)(blockIdx.x >> 3) : u - slice * g.ntiles;
-#else
     const int u = (blockIdx.x >> 3) + (blockIdx.x & 7) * ((gridDim.x + 7) >> 3);
     if (u >= g.ntiles * g.splitk) return false;
     const int slice = u / g.ntiles;
     const int t = u - slice * g.ntiles;
-#endif
     int tm, tn;
     if (g.flags & DSVGP_GEMM_OUT_LOWER) {
         // tiles with tn <= tm, row by row: the triangle t = tm (tm + 1) / 2 + tn while tm < tiles_n, full rows of
         // tiles_n tiles below it (tiles_m > tiles_n: e.g. the extra row b^T of [G ; b^T] opening a tile row of its own)
         const int tri = min(g.tiles_m, g.tiles_n), t0 = tri * (tri + 1) / 2;
         if (t < t0) {
-#if G32_TRI_SB > 1
-            // the triangle in SB x SB super-blocks, row by row (the 64 workgroups an XCD holds at a time then share SB row panels
-            // and SB column panels -- the walk of the dense product -- instead of 2-3 whole tile rows: 3 + 21 panels)
-            constexpr int SB = G32_TRI_SB;
-            int q = t, I = 0, J = 0, rI = 0, cJ = 0;
-            const int nsb = (tri + SB - 1) / SB;
-            bool found = false;
-            for (I = 0; I < nsb && !found; ++I) {
-                rI = min(SB, tri - SB * I);
-                for (J = 0; J <= I; ++J) {
-                    cJ = min(SB, tri - SB * J);
-                    const int cnt = (J < I) ? rI * cJ : rI * (rI + 1) / 2;
-                    if (q < cnt) { found = true; break; }
-                    q -= cnt;
-                }
-                if (found) break;
-            }
-            if (J < I) {
-                tm = SB * I + q / cJ;
-                tn = SB * J + q % cJ;
-            } else {
-                int a = (int)((sqrtf(8.f * (float)q + 1.f) - 1.f) * 0.5f);
-                while ((a + 1) * (a + 2) / 2 <= q) ++a;
-                while (a * (a + 1) / 2 > q) --a;
-                tm = SB * I + a;
-                tn = SB * J + q - a * (a + 1) / 2;
-            }
-#else
             tm = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
             while ((tm + 1) * (tm + 2) / 2 <= t) ++tm;
             while (tm * (tm + 1) / 2 > t) --tm;
             tn = t - tm * (tm + 1) / 2;
-#endif
         } else {
             tm = tri + (t - t0) / g.tiles_n;
             tn = (t - t0) % g.tiles_n;
@@ -212,11 +155,7 @@ __device__ __forceinline__ bool pick_unit(const G32& g, int& m0, int& n0, int& k
 // C/D layout of the 32 x 32 MFMA: col = lane & 31, row = (c & 3) + 8 (c >> 2) + 4 (lane >> 5)
 __device__ __forceinline__ void store_tile(const G32& g, const acc16 (&acc)[2][2], int m0, int n0, int wr, int wc, int h, int r,
                                            float* Cb, int64_t ldcb, bool atomic_) {
-#ifdef G32_ABL_NOATOMIC          // (timing ablation only: wrong results under split-K)
-    const bool atomic = false, out_lower = g.flags & DSVGP_GEMM_OUT_LOWER;
-#else
     const bool atomic = atomic_, out_lower = g.flags & DSVGP_GEMM_OUT_LOWER;
-#endif
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -306,15 +245,12 @@ __global__ __launch_bounds__(256, G32_MINW) void gemm32_kernel(const G32 g) {
     if (kbeg < kend) {
         fetch(kbeg);
         for (int k0 = kbeg; k0 < kend; k0 += BK) {
-            if (!(G32_ABL & 2)) commit();
-            if (!(G32_ABL & 8)) __syncthreads();
-            if (!(G32_ABL & 1) && k0 + BK < kend) fetch(k0 + BK);                 // in flight under the MFMAs of this stage
-            if (G32_PRIO) __builtin_amdgcn_s_setprio(1);
+            commit();
+            __syncthreads();
+            if (k0 + BK < kend) fetch(k0 + BK);                 // in flight under the MFMAs of this stage
 #pragma unroll
             for (int kk = 0; kk < BK / 4; ++kk) {
                 float2 a[2], b[2];
-                const int kr_ = (G32_ABL & 4) ? 0 : kk;        // (ablation: the same fragment every step -> reads hoisted)
-#define kk kr_
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     if constexpr (A_KC) a[i] = *reinterpret_cast<const float2*>(af + i * 32 * SKC + 4 * kk);
@@ -325,7 +261,6 @@ __global__ __launch_bounds__(256, G32_MINW) void gemm32_kernel(const G32 g) {
                     if constexpr (B_KC) b[j] = *reinterpret_cast<const float2*>(bf + j * 32 * SKC + 4 * kk);
                     else b[j] = float2{bf[(4 * kk) * SMC + j * 32], bf[(4 * kk + 1) * SMC + j * 32]};
                 }
-#undef kk
 #pragma unroll
                 for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -334,8 +269,7 @@ __global__ __launch_bounds__(256, G32_MINW) void gemm32_kernel(const G32 g) {
                         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i].y, b[j].y, acc[i][j], 0, 0, 0);
                     }
             }
-            if (G32_PRIO) __builtin_amdgcn_s_setprio(0);
-            if (!(G32_ABL & 8)) __syncthreads();
+            __syncthreads();
         }
     }
 
@@ -508,7 +442,6 @@ __global__ __launch_bounds__(256, BK == 16 ? 3 : 2) void gemm32_dma_kernel(const
             G32_T(t1);
             const float* As = &lds[buf][0];
             const float* Bs = As + OPW;
-            if (G32_PRIO) __builtin_amdgcn_s_setprio(1);
             // the fragments of chunk group j + 1 are requested before the MFMAs of group j: the LDS latency rides under them
             Frag f[2];
             load_frag(As, Bs, 0, f[0]);
@@ -530,7 +463,6 @@ __global__ __launch_bounds__(256, BK == 16 ? 3 : 2) void gemm32_dma_kernel(const
                         }
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (G32_PRIO) __builtin_amdgcn_s_setprio(0);
             G32_T(t2);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of the next stage has landed ...
             G32_T(t3);
@@ -626,12 +558,6 @@ int launch_gemm32(hipStream_t st, const GemmArgs& g) {
             if (tcost < best * 0.999) { best = tcost; sk = c; }
         }
     }
-#if G32_XCDK
-    if (out_lower && sk > 1 && g.K >= 8 * 512) sk = 8;
-#endif
-#ifdef G32_SK      // probe: fixed slice count for the products of G32_SK_MINT..G32_SK_BELOW tiles
-    if (a.ntiles < G32_SK_BELOW && a.ntiles >= G32_SK_MINT && g.K >= 1024 && g.K < 16384) sk = G32_SK;
-#endif
     sk = slab_slices(g, sk, sizeof(float));         // deterministic mode: as many slices as the caller's scratch holds
     a.splitk = sk;
     a.kslice = cdiv(cdiv(g.K, sk), 32) * 32;
@@ -645,7 +571,6 @@ int launch_gemm32(hipStream_t st, const GemmArgs& g) {
     }
     const dim3 grid(cdiv((int64_t)a.ntiles * a.splitk, 8) * 8);
     const bool akc = !(fl & DSVGP_GEMM_TRANS_A), bkc = (fl & DSVGP_GEMM_TRANS_B) != 0;
-#if G32_DMA
     // LDS-DMA kernel: a k-contiguous operand needs K % 4 == 0 or caller-zeroed padding up to it (the chunk that straddles K
     // is read as it lies in memory)
     if (!((akc || bkc) && g.K % 4 != 0 && !(g.flags & DSVGP_GEMM_K_PADDED))) {
@@ -656,7 +581,6 @@ int launch_gemm32(hipStream_t st, const GemmArgs& g) {
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return 1000 + (int)e;
     } else
-#endif
     {
         const int rc = dispatch32<G32_BK>(st, a, grid, akc, bkc);
         if (rc != 1) return rc;

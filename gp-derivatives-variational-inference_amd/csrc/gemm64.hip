@@ -39,9 +39,6 @@ struct G64 {
 #ifndef G64_MINW
 #define G64_MINW 6
 #endif
-#ifndef G64_PRIO
-#define G64_PRIO 0
-#endif
 #ifndef G64_CHUNK
 #define G64_CHUNK 8
 #endif
@@ -51,15 +48,6 @@ struct G64 {
 #ifndef G64_KCHUNK
 #define G64_KCHUNK 768      // split-K chunk (512 / 768 / 1024 measured within 0.3 %) of the few-tile (M' x M' x M') products: the longest tile's 188 dependent stages (K = 3000) set
 #endif                      // the duration of a launch whose ~1100-2200 tiles are all resident at once
-#ifndef G64_STORE_SWZ
-#define G64_STORE_SWZ 0     // 1: bank-conflict-free order of the two 16-byte LDS stores of a staged thread (probe)
-#endif
-#ifndef G64_KC
-#define G64_KC 1            // k-contiguous operands taken (A_KC / B_KC staging)
-#endif
-#if G64_STORE_SWZ && G64_KC
-#error "G64_STORE_SWZ=1 stores ra / rb in the mn-contiguous [k][m] layout only: build the probe with -DG64_KC=0"
-#endif
 #ifndef G64_BAND
 #define G64_BAND 16         // tile columns per band (probed 2 / 4 / 8 / 12 / 16 / 20 / 24 / 32: 56.5 / 57.1 / 60.8 / 62.8 / 63.4 / 57.0 / 62.6 / 54.2 TF) of the XCD-local walk
 #endif
@@ -136,7 +124,6 @@ __global__ __launch_bounds__(256, G64_MINW) void gemm64_kernel(const G64 g) {
 
     // staging: thread -> (k = tid / 16, 4 consecutive columns at 4 (tid % 16)) of the 16 x 64 stage of each operand
     const int sk = tid >> 4, sc = (tid & 15) * 4;
-    const bool hs = (tid >> 2) & 1;
     const int kr = tid >> 2, kq = (tid & 3) * 4;           // k-contiguous operand: row kr of the tile, k = kq .. kq + 3 of the stage
     const double* __restrict__ Ap = A_KC ? g.A + (int64_t)min(m0 + kr, g.M - 1) * g.lda + kq : g.A + m0 + sc;
     const TB* __restrict__ Bp = B_KC ? (const TB*)g.B + (int64_t)min(n0 + kr, g.N - 1) * g.ldb + kq : (const TB*)g.B + n0 + sc;
@@ -222,17 +209,6 @@ __global__ __launch_bounds__(256, G64_MINW) void gemm64_kernel(const G64 g) {
         for (int k0 = klo; k0 < khi; k0 += BK) {
             double* as = As + sk * LDS_STRIDE + sc;
             double* bs = Bs + sk * LDS_STRIDE + sc;
-#if G64_STORE_SWZ
-            // a thread's 32 bytes go out as two 16-byte stores; with every lane storing its first half first, lanes L and L + 4 of
-            // an 8-lane store group hit the same four banks (lane stride 32 B): lanes 4..7 store their halves in the opposite order
-            {
-                const int o0 = hs ? 2 : 0, o1 = hs ? 0 : 2;
-                *reinterpret_cast<double2*>(as + o0) = hs ? double2{ra[2], ra[3]} : double2{ra[0], ra[1]};
-                *reinterpret_cast<double2*>(as + o1) = hs ? double2{ra[0], ra[1]} : double2{ra[2], ra[3]};
-                *reinterpret_cast<double2*>(bs + o0) = hs ? double2{rb[2], rb[3]} : double2{rb[0], rb[1]};
-                *reinterpret_cast<double2*>(bs + o1) = hs ? double2{rb[0], rb[1]} : double2{rb[2], rb[3]};
-            }
-#else
             if constexpr (A_KC) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) As[(kq + e) * LDS_STRIDE + kr] = ra[e];
@@ -247,10 +223,8 @@ __global__ __launch_bounds__(256, G64_MINW) void gemm64_kernel(const G64 g) {
                 *reinterpret_cast<double2*>(bs) = double2{rb[0], rb[1]};
                 *reinterpret_cast<double2*>(bs + 2) = double2{rb[2], rb[3]};
             }
-#endif
             __syncthreads();
             if (k0 + BK < khi) fetch(k0 + BK);               // in flight under the 16 MFMAs of this stage
-            if (G64_PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
             for (int kk = 0; kk < BK / 4; ++kk) {
                 const int kq = kk * 4 + (lane >> 4);
@@ -265,7 +239,6 @@ __global__ __launch_bounds__(256, G64_MINW) void gemm64_kernel(const G64 g) {
                     for (int j = 0; j < 2; ++j)
                         acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i], b[j], acc[i][j], 0, 0, 0);
             }
-            if (G64_PRIO) __builtin_amdgcn_s_setprio(0);
             __syncthreads();
         }
     }
@@ -282,11 +255,7 @@ __global__ __launch_bounds__(256, G64_MINW) void gemm64_kernel(const G64 g) {
                 if (g.kchunk) {
                     if (out_lower && n > m) continue;
                     if (g.slab) g.slab[((int64_t)blockIdx.y * g.M + m) * g.N + n] = v;    // deterministic mode (summed in order afterwards)
-#ifdef G64_ABL_NOATOMIC      // (timing ablation only: wrong results)
-                    else g.C[(int64_t)m * g.ldc + n] = v;
-#else
                     else atomicAdd(&g.C[(int64_t)m * g.ldc + n], v);
-#endif
                     continue;
                 }
                 if (out_lower && n > m) v = 0.0;
@@ -305,9 +274,6 @@ __global__ __launch_bounds__(256, G64_MINW) void gemm64_kernel(const G64 g) {
 // CU) 4.3-4.9; bands of 8 tile columns per XCD (4: +0.03-0.1, 10: +0.4, 16: +0.7).  A float right operand uses TW = 192, a double
 // one (float64 model mode; 168 VGPRs would spill) TW = 128.
 // -------------------------------------------------------------------------------------------------
-#ifndef G64_WIDE
-#define G64_WIDE 1
-#endif
 #ifndef G64W_BAND
 #define G64W_BAND 8
 #endif
@@ -440,9 +406,6 @@ __global__ __launch_bounds__(256, TW > 128 ? 3 : 4) void gemm64w_kernel(const G6
 // swapped (column c ^ 16); B image [16][192] floats, the odd k rows rotated by 48 columns -- in both, the two k rows that one
 // 32-lane read group touches then fall on disjoint halves of the banks.
 // -------------------------------------------------------------------------------------------------
-#ifndef G64_PIPE
-#define G64_PIPE 1
-#endif
 typedef __attribute__((address_space(3))) void* g64_lds_ptr_t;
 __device__ __forceinline__ void g64_dma16(const void* gsrc, unsigned lds_byte_addr) {
     unsigned keep;
@@ -647,21 +610,6 @@ __global__ __launch_bounds__(256, sizeof(TB) == 4 ? 2 : 3) void gemm64p_kernel(c
 // ones at the diagonal of a triangular A -- at the END of the range for a lower A, at its START for an upper one -- and a ragged
 // K end.
 // -------------------------------------------------------------------------------------------------
-#ifndef G64_LEAN_PIPE
-#define G64_LEAN_PIPE 1
-#endif
-#ifndef G64_SMALL_PIPE
-#define G64_SMALL_PIPE 1            // 1: products with 64 .. 1023 tiles (small problems) on the four-buffer form of gemm64l_kernel instead of gemm.hip's split-K
-#endif
-#ifndef G64_LEAN_PIPE_KC
-#define G64_LEAN_PIPE_KC 1          // 1: k-contiguous operands too (double right operand; the float64 model mode's Gram / dense products)
-#endif
-#ifndef G64_LEAN_PIPE_D
-#define G64_LEAN_PIPE_D 1           // 1: a double right operand too (the Cholesky backward's products; the float64 model mode)
-#endif
-#ifndef G64_LEAN_PIPE_UPPER
-#define G64_LEAN_PIPE_UPPER 1       // 0: an upper-triangular A (the [Q' | a] solve) stays on gemm64_kernel
-#endif
 // TB = double (round 5, the Cholesky backward's products and the float64 model mode): the B image is built like the A image (16 KB per stage, 32 KB:
 // five workgroups per CU).  A triangular B trims / masks the K range by the tile COLUMN the same way; split-K (kchunk) walks its chunk of the range
 // and accumulates with fp64 atomics (or stores to the deterministic slab) as gemm64_kernel does.
@@ -1002,9 +950,6 @@ int launch_gemm64(hipStream_t st, const GemmArgs& g) {
     const bool a_kc = !(fl & DSVGP_GEMM_TRANS_A), b_kc = fl & DSVGP_GEMM_TRANS_B;
     if (a_kc && (fl & (DSVGP_GEMM_A_LOWER | DSVGP_GEMM_A_UPPER))) return 0;
     if (b_kc && (fl & (DSVGP_GEMM_B_LOWER | DSVGP_GEMM_B_UPPER))) return 0;
-#if !G64_KC
-    if (a_kc || b_kc) return 0;
-#endif
     if (g.batch != 1 || g.splitk != 1 || g.Cin || g.kscale || (fl & DSVGP_GEMM_KEEP_UPPER)) return 0;
     if (g.small64 && (a_kc || b_kc || g.N < 4 || g.M < 2 || g.slab)) return 0;            // (the few-tile form: mn-contiguous operands only, not in deterministic mode)
     const bool bf = fl & DSVGP_GEMM_B_IS_FLOAT;
@@ -1018,7 +963,6 @@ int launch_gemm64(hipStream_t st, const GemmArgs& g) {
     a.tri_off = g.tri_off;
     const int total = a.tiles_m * a.tiles_n;
     a.balanced = total < G64_BALANCED_BELOW;
-#if G64_WIDE
     if ((total >= G64W_MIN_TILES || g.wide64) && !a_kc && !b_kc && !(fl & (DSVGP_GEMM_B_LOWER | DSVGP_GEMM_B_UPPER | DSVGP_GEMM_OUT_LOWER)) &&      // (no split-K, no atomics: also in deterministic mode)
         (bf ? g.ldb % 4 == 0 : true)) {
         constexpr int TWD = G64W_TW > 128 ? 128 : G64W_TW;          // (double right operand)
@@ -1030,7 +974,7 @@ int launch_gemm64(hipStream_t st, const GemmArgs& g) {
                                      : hipFuncSetAttribute((const void*)gemm64w_kernel<double, TWD>, hipFuncAttributeMaxDynamicSharedMemorySize, pad);
             if (ea != hipSuccess) return 1000 + (int)ea;
         }
-#if G64_PIPE && G64W_TW == 192
+#if G64W_TW == 192
         // (the pipelined form: rows of both operands addressable as 16-byte pieces -- checked above; N >= 4 and M >= 2 for its clamped edge
         //  addresses; not as a row-range piece with LDS padding)
         if (!pad && g.N >= 4 && g.M >= 2) {
@@ -1043,7 +987,6 @@ int launch_gemm64(hipStream_t st, const GemmArgs& g) {
         hipError_t ew = hipGetLastError();
         return ew == hipSuccess ? 1 : 1000 + (int)ew;
     }
-#endif
     if (g.tri_off || g.wide64) return DSVGP_EINVAL;                 // (only the wide kernel takes row-range pieces)
     // split-K for the few-tile products with a long K: every tile is resident at once, so the launch lasts as long as its
     // longest tile's chain of K / 16 dependent stages; chunks of G64_KCHUNK accumulate with fp64 atomics onto a zeroed output
@@ -1063,17 +1006,15 @@ int launch_gemm64(hipStream_t st, const GemmArgs& g) {
         }
     }
     const dim3 grid(a.balanced ? 8 * G64_CHUNK * cdiv(a.tiles_m * cdiv(a.tiles_n, G64_CHUNK), 8) : cdiv(total, 8) * 8, ysplit);
-#if G64_SMALL_PIPE
     if (g.small64) {          // (few tiles: the four-buffer form; the caller -- launch_gemm -- has checked the layouts it takes)
         if (bf) hipLaunchKernelGGL((gemm64l_kernel<float, false, false, 4>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((gemm64l_kernel<double, false, false, 4>), grid, dim3(256), 0, st, a);
         hipError_t es = hipGetLastError();
         return es == hipSuccess ? 1 : 1000 + (int)es;
     }
-#endif
-    // (k-contiguous operands: the pipelined form takes them when the right operand is double -- G64_LEAN_PIPE_KC -- and the rows are
+    // (k-contiguous operands: the pipelined form takes them when the right operand is double and the rows are
     //  16-byte addressable: even leading dimensions and aligned bases, checked above)
-    const bool lkc = G64_LEAN_PIPE && G64_LEAN_PIPE_KC && !g.lean_classic && g.N >= 4 && g.M >= 2;
+    const bool lkc = !g.lean_classic && g.N >= 4 && g.M >= 2;
     if (a_kc && b_kc) {
         if (bf) hipLaunchKernelGGL((gemm64_kernel<float, true, true>), grid, dim3(256), 0, st, a);
         else if (lkc) hipLaunchKernelGGL((gemm64l_kernel<double, true, true>), grid, dim3(256), 0, st, a);
@@ -1088,13 +1029,11 @@ int launch_gemm64(hipStream_t st, const GemmArgs& g) {
         else if (lkc) hipLaunchKernelGGL((gemm64l_kernel<double, false, true>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((gemm64_kernel<double, false, true>), grid, dim3(256), 0, st, a);
     }
-#if G64_LEAN_PIPE
-    // (the pipelined form of the lean kernel: mn-contiguous operands, N >= 4 and M >= 2 for its clamped edge addresses; G64_LEAN_PIPE_D: a double B too)
-    else if (g.N >= 4 && g.M >= 2 && !g.lean_classic && (bf || G64_LEAN_PIPE_D) && (G64_LEAN_PIPE_UPPER || !(fl & DSVGP_GEMM_A_UPPER))) {
+    // (the pipelined form of the lean kernel: mn-contiguous operands, N >= 4 and M >= 2 for its clamped edge addresses; a double B too)
+    else if (g.N >= 4 && g.M >= 2 && !g.lean_classic) {
         if (bf) hipLaunchKernelGGL(gemm64l_kernel<float>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(gemm64l_kernel<double>, grid, dim3(256), 0, st, a);
     }
-#endif
     else if (bf) hipLaunchKernelGGL(gemm64_kernel<float>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(gemm64_kernel<double>, grid, dim3(256), 0, st, a);
     if (a.slab) {

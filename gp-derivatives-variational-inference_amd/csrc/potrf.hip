@@ -3,11 +3,25 @@
 //
 // rocSOLVER's dpotrf takes 8.1 ms at M' = 3000 (serial single-workgroup panel kernels + many small launches); a first
 // blocked version here (diagonal-block kernel + panel GEMM + trailing GEMM per block column, 141 launches) took 4.5 ms.
-// This version: 48 launches, 1.355 ms at M' = 3000 for the factor WITH the fused inverse (1.62 at 3300, 0.222 at 600; 1.41 / 1.67 / 0.252 with the
-// column-by-column chain of the 16 x 16 diagonal sub-blocks, POTRF_F16_BLK = 0; tools/potrf_inv_probe.py; per-launch
-// trace tools/potrf_inv_trace.sh; in-kernel stamps of the diagonal workgroup tools/potrf_clock.sh; anatomy in DESIGN.md section 5).
-// Measured without effect on the chain (+-1 %, removed again): one Newton step behind v_rsq_f64 instead of two, multipliers folded
-// once per column of the 16-column chain, operand reads of the 64^3 products pipelined in chunks, 8-wave workgroups (POTRF_NW).
+// What is here: one launch per block column (chol_step_kernel) + one batched panel launch, the factor WITH the fused inverse,
+// 1.085 ms at M' = 3000 and 0.174 ms at 600 (tools/potrf_inv_probe.py).  In every step launch
+//   * workgroup 0 is the CRITICAL workgroup: it updates the next diagonal tile and factors it with the tile in registers, one
+//     16-row strip per wave, hand-offs through LDS flag words (crit_strips_update + factor64_strips);
+//   * the other workgroups take strips of update / inverse tiles: two LDS tiles and two workgroups per CU, or -- launches from
+//     `pipe_from` on with more than POTRF_PIPE_MIN_TILES tiles -- the PIPE instantiation, one workgroup per CU with the strip
+//     software-pipelined (strip_pipe).
+// Tools: per-launch trace tools/potrf_inv_trace.sh; in-kernel stamps of the critical workgroup tools/potrf_clock.sh (-DPOTRF_DEBUG);
+// per-workgroup phases tools/potrf_wgtrace.sh (-DPOTRF_TRACE).
+// Tried, measured and removed in the build-variant clean-up (last present in 8a953b7), each behind a build switch until then:
+//   * round 5's critical workgroup with the diagonal tile in LDS (POTRF_CRIT_STRIPS = 0):
+//     see the record above factor64_strips; its column-by-column 16-column chain (POTRF_F16_BLK = 0): 1.41 / 1.67 / 0.252 ms at
+//     n = 3000 / 3300 / 600 against 1.355 / 1.62 / 0.222 for the four-column blocks (round 2); both rank-1 updates of that chain
+//     through w = a_ij / a_jj (POTRF_FOLD, round 4): n = 3000 1.400 / 1.406 -> 1.396 / 1.414 ms, n = 600 0.250 -> 0.252 -- latency-,
+//     not issue-bound;
+//   * the timing ablations POTRF_ABL_NOC / NOP / P1 (wrong numbers by construction) and the A/B switches POTRF_PIPE, POTRF_PIPE_LATE0,
+//     POTRF_PIPE_FROM of the pipelined strips, which had served their measurements.
+// Measured without effect on the chain (+-1 %, removed again): multipliers folded once per column of the 16-column chain, operand
+// reads of the 64^3 products pipelined in chunks.
 #include "common.h"
 
 #include <type_traits>
@@ -16,15 +30,6 @@ namespace {
 
 constexpr int NBC = 64;
 
-#ifndef POTRF_NW
-#define POTRF_NW 4          // waves per workgroup of the step launches: 4; 8 (each 64 x 64 tile product split 32 x 16 per wave) measured slower at M' = 3000 (1.78-1.93 vs 1.70 ms); at 600 5 % faster in round 2, 28 % slower on the round-4 kernel (0.319 vs 0.249 ms)
-#endif
-#ifndef POTRF_NEWTON
-#define POTRF_NEWTON 2
-#endif
-#ifndef POTRF_FOLD
-#define POTRF_FOLD 0        // 1: both rank-1 updates of factor16_wave through w = a_ij / a_jj (10 instead of 16 fp64 operations per column).
-#endif                      // Measured (round 4): n = 3000 1.400 / 1.406 -> 1.396 / 1.414 ms, n = 600 0.250 -> 0.252: the column is latency-, not issue-bound
 // Update / inverse tiles of one tile row are dealt to workgroups in STRIPS of up to `strip` block columns: T = A_ik W_k is formed
 // once per strip (1 + strip products for strip tiles instead of 2 per tile, A_ik and W_k loaded once).  The launcher picks the
 // strip length per launch from the tile count: long strips only where the launch is bound by its tiles, not by the diagonal
@@ -47,16 +52,6 @@ constexpr int NBC = 64;
 #ifndef POTRF_STRIP_V2
 #define POTRF_STRIP_V2 2
 #endif
-__device__ __forceinline__ double rsqrt_nr(double d) {
-    double y = __builtin_amdgcn_rsq(d);
-#pragma unroll
-    for (int it = 0; it < POTRF_NEWTON; ++it) {      // y += (y / 2) (1 - d y^2): three dependent operations per step (y / 2 runs beside d y)
-        const double h = 0.5 * y;
-        y = fma(h, fma(-(d * y), y, 1.0), y);
-    }
-    return y;
-}
-
 // -------------------------------------------------------------------------------------------------
 // ONE launch per block column.
 //   With X_k = inv(L_kk) and W_k = X_k^T X_k = inv(A_kk) the rank-64 update of step k needs no solved panel:
@@ -64,32 +59,21 @@ __device__ __forceinline__ double rsqrt_nr(double d) {
 //   so kernel k does, per 64 x 64 trailing tile, T = A_ik W_k and A_ij -= T A_jk^T out of LDS (column k of A is
 //   read-only in that launch: no in-place hazard), and the workgroup of tile (k+1, k+1) goes on to factor its
 //   updated tile: L_{k+1,k+1}, X_{k+1}, W_{k+1}.  The solved panels L_ik = A_ik X_k^T are formed afterwards by ONE
-//   batched launch.  Critical path per block column: load + 2 products + the in-LDS factorisation.
-//
-//   In-LDS factorisation of a 64 x 64 tile by 256 threads: 4 x 4 grid of 16 x 16 sub-blocks; the diagonal
-//   sub-block is factored AND inverted by ONE wave out of registers (lane = row i, column group g; columns /
-//   rows exchanged through 16-entry LDS vectors, pivot by v_readlane: no workgroup barrier on the 16-column
-//   chain), the sub-panel, the trailing sub-blocks and the running inverse [L | I] -> [I | X] are 16x16x16
-//   fp64 MFMA products.
+//   batched launch.  Critical path per block column: load + update + the factorisation of one 64 x 64 tile by the critical
+//   workgroup (the section above factor64_strips).
 // -------------------------------------------------------------------------------------------------
 using acc4 = double __attribute__((ext_vector_type(4)));
 #ifdef POTRF_DEBUG
 #ifndef POTRF_DEBUG_K
 #define POTRF_DEBUG_K 20      // block column whose critical workgroup is stamped
 #endif
-#if !defined(POTRF_CRIT_STRIPS) || POTRF_CRIT_STRIPS
-#define CHOL_STRIPS_STAMPS 1  // (slots 16 .. 27 belong to the strips chain's own stamps)
-#else
-#define CHOL_STRIPS_STAMPS 0
-#endif
 __device__ unsigned long long chol_dbg[64];
 // stamps pinned in place (the scalar s_memtime would otherwise be scheduled ahead of the MFMAs it is meant to follow) and kept
 // in registers until the end of the kernel (a global store per stamp would sit in vmcnt and stretch the waits that follow it)
-#define CHOL_STAMP_DECL unsigned long long st_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
+#define CHOL_STAMP_DECL unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0}
 #define CHOL_STAMP(slot) do { __builtin_amdgcn_sched_barrier(0); \
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_[slot]) :: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
-#define CHOL_STAMP_FLUSH do { if (b == 0 && k == POTRF_DEBUG_K) { if (tid == 0) { for (int q_ = 0; q_ < 8; ++q_) chol_dbg[q_] = st_[q_]; } \
-        if ((tid & 63) == 0 && !CHOL_STRIPS_STAMPS) { chol_dbg[16 + (tid >> 6)] = st_[8]; chol_dbg[20 + (tid >> 6)] = st_[9]; chol_dbg[24 + (tid >> 6)] = st_[10]; } } } while (0)
+#define CHOL_STAMP_FLUSH do { if (b == 0 && k == POTRF_DEBUG_K && tid == 0) { for (int q_ = 0; q_ < 8; ++q_) chol_dbg[q_] = st_[q_]; } } while (0)
 #else
 #define CHOL_STAMP_DECL
 #define CHOL_STAMP(slot) do { } while (0)
@@ -165,50 +149,9 @@ __device__ __forceinline__ void tile_product(const double (*As)[LDT], const doub
                 acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[i][ks], b[j][ks], acc[i][j], 0, 0, 0);
 }
 
-#ifndef POTRF_IL
-#define POTRF_IL 0          // 1: the strip products of the update / inverse tiles issue the NEXT block column's global loads between their MFMAs.
-#endif                      // Measured (round 5, profiles/r05_b_potrf_tile_roles.txt): needs POTRF_MINW = 1 (at two waves per SIMD it spills 23 registers:
-                            // 1.48 ms); with it n = 3000 1.33 -> 1.27 ms, n = 3300 1.60 -> 1.54, but the STEP does not move (C4 12.81 / 12.78 against
-                            // 12.83 / 12.79, C3 7.055 against 7.06: beside the side stream's kernels the launches are bound elsewhere).  Off.
-// The same 64 x 64 x 64 product by 4 waves (acc += / = A B), scheduled for a wave that is ALONE on its SIMD (the tile-bound
-// launches run one strip workgroup per CU): operand fragments are read two k-steps ahead of the MFMAs that use them, and after
-// every k-step (4 MFMAs = 256 cycles of the matrix pipe, of which the SIMD's issue port is busy for ~32) the caller's hook
-// pf(ks), ks = 0 .. 15, issues one sixteenth of the NEXT tile's global loads.  With those 32 loads issued in front of the product
-// (round 2 .. 4) a strip column cost 7.0k cycles against 4.8k for the last column of a strip, which prefetches nothing
-// (profiles/r05_b_potrf_wgtrace_before.txt): the vector-memory issue of one wave, ~70 cycles per load, ran with the matrix pipe idle.
-template <bool B_NK, bool ACC_INIT, typename F>
-__device__ __forceinline__ void tile_product_il(const double (*As)[LDT], const double (*Bs)[LDT], int lane, int wr, int wc,
-                                                acc4 (&acc)[2][2], F&& pf) {
-    if constexpr (!ACC_INIT) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = acc4{0, 0, 0, 0};
-    }
-    const int g = lane >> 4, m = lane & 15;
-    double a[16][2], b[16][2];
-    auto rd = [&](int ks) {
-        const int kq = 4 * ks + g;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) a[ks][i] = As[wr * 32 + i * 16 + m][kq];
-#pragma unroll
-        for (int j = 0; j < 2; ++j) b[ks][j] = B_NK ? Bs[wc * 32 + j * 16 + m][kq] : Bs[kq][wc * 32 + j * 16 + m];
-    };
-    rd(0);
-    rd(1);
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        if (ks + 2 < 16) rd(ks + 2);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks][i], b[ks][j], acc[i][j], 0, 0, 0);
-        pf(ks);
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);      // the four fragment reads of k-step ks + 2
-        __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);      // the four MFMAs of k-step ks
-        __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);      // two of the next tile's global loads
-    }
-}
+// Tried and removed: the same product issuing the NEXT block column's global loads between its MFMAs (POTRF_IL;
+// round 5, profiles/r05_b_potrf_tile_roles.txt: n = 3000 1.33 -> 1.27 ms, n = 3300 1.60 -> 1.54 at one wave per SIMD, 1.48 ms with 23 spilled
+// registers at two, the STEP unmoved: C4 12.81 / 12.78 against 12.83 / 12.79, C3 7.055 against 7.06); removed in the build-variant clean-up; last present in 8a953b7.
 
 // -------------------------------------------------------------------------------------------------
 // Software-pipelined strip (round 5; the PIPE instantiation of chol_step_kernel: ONE workgroup per CU, three LDS tiles).
@@ -226,7 +169,7 @@ __device__ __forceinline__ void tile_product_il(const double (*As)[LDT], const d
 // vmcnt(0); selects on loaded values became branches around the loads and cut the scheduling regions.)
 // An LDS-DMA instruction writes 64 x 16 bytes CONTIGUOUSLY (two rows of a tile), so B's LDS image is rows in PAIRS with a stride of
 // 132 doubles per pair, and the 16-byte granules of the odd row of a pair are stored at column c ^ 18 (applied to the SOURCE
-// address): bsw() below; the fragment reads of both operand orientations are then conflict-free (32 lanes, 32 distinct bank pairs).
+// address): bsw below; the fragment reads of both operand orientations are then conflict-free (32 lanes, 32 distinct bank pairs).
 // B_NK: B_c given as [n][k] (update role: rows of A_jk) or [k][n] (inverse role: R_kj).  ident_after: the block column BEHIND the
 // ncols pipelined ones has B = I and old C = 0 (inverse role, j == k: always the strip's last): its result is -T itself, stored from
 // LDS at the end, no product.  last_diag: the last column is a diagonal tile (only n <= m is stored).  All 64 rows of every C tile
@@ -236,7 +179,7 @@ __device__ __forceinline__ void tile_product_il(const double (*As)[LDT], const d
 // -------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* potrf_lds_ptr_t;
 constexpr int BPAIR = 132;                                  // doubles per row pair of a DMA-filled B image (64 x 66 = 32 x 132)
-__device__ __forceinline__ int bsw(int row, int col) { return (row >> 1) * BPAIR + (row & 1) * 64 + (col ^ ((row & 1) * 18)); }
+// bsw(row, col) = (row >> 1) * BPAIR + (row & 1) * 64 + (col ^ ((row & 1) * 18)): offset (doubles) of element (row, col) in a B image
 // One LDS-DMA instruction as an asm statement: no VGPR destination, and WE count it (s_waitcnt vmcnt(0) before the barrier that
 // ends the stage) -- through the builtin hipcc parks a vmcnt(0) in front of the next LDS read (see gemm32.hip).  M0 (the LDS
 // destination base) is compiler-reserved: saved, set and restored inside the statement.
@@ -410,348 +353,6 @@ __device__ __forceinline__ void strip_pipe(double (*S)[64][LDT], const double* _
     }
 }
 
-#ifndef POTRF_F16_BLK
-#define POTRF_F16_BLK 1     // 1: the 16-column chain of the diagonal sub-block in four 4-column blocks, rank-4 updates on the fp64 MFMA; 0: column by column
-#endif
-#if POTRF_F16_BLK
-// one wave: Cholesky factor L_d (in place, upper part zeroed) and inverse Xd = L_d^-1 of the 16 x 16 block at F[o.., o..], FOUR
-// COLUMNS PER EXCHANGE, the updates as two v_mfma_f64_16x16x4 per block.
-//   The column-by-column form (POTRF_F16_BLK = 0) publishes one column and one row through LDS per column and applies a rank-1
-//   update from VALU code: 16 write -> read round trips and ~35 instructions per column on the single wave whose chain bounds
-//   every launch of the factorisation.  Here, per block of four columns j0 .. j0+3:
-//     * every lane publishes ONE element of D (column j0 + g of its row) and one of Y', reads the 4 x 4 pivot block (the same ten
-//       numbers in every lane), the four block entries of its own row and the four block rows of Y' in its own column;
-//     * factors the pivot block (four dependent rsqrt), substitutes its own row against it -> M[i][0..3] = L[i][j0..j0+3], and
-//       eliminates the four rows of Y' inside the block -> Z[0..3];
-//     * D -= M M^T and Y' -= (M diag(1/L_kk), strictly below the diagonal) Z are ONE MFMA each, and both take their operands from
-//       the lane's own registers: with a[t] = D[i][4t+g] (i = lane & 15, g = lane >> 4) the 16x16x4 A operand wants lane (m, k)
-//       to hold M[m][k] and the B operand lane (n, k) to hold M[n][k] -- the same register, M[i][g]; its C/D layout (lane (c, g'),
-//       register q <-> element (g' + 4q, c)) is the transposed position of D[c][4q+g'], which a SYMMETRIC update term leaves
-//       correct; Y' is kept as yt[t] = Y'[4t+g][i] (row in (t, g), column on the lane), the C/D layout itself.
-//   Y': forward elimination of the identity with UNSCALED rows (Y'[r] = L_rr X[r]); scaled by 1 / L_rr at the end.
-//   colblk = [16][4] (columns j0 .. j0+3 of D), rowblk = [4][16] (rows j0 .. j0+3 of Y').
-//   from_regs (wave-uniform): the block arrives in a_in, a_in[t] = D[i][4t+g] (the critical tile's leading block comes straight out of
-//   the MFMA accumulators of its rank-64 update, see crit_tile_update) instead of from F.
-__device__ __forceinline__ void factor16_wave(double (*F)[LDT], int o, double (*Xd)[17], double* colblk, double* rowblk,
-                                              int lane, int* info, int gidx0, int nvalid, bool from_regs = false,
-                                              acc4 a_in = acc4{0, 0, 0, 0}) {
-    const int i = lane & 15, g = lane >> 4;
-    acc4 a, yt;
-    if (from_regs) a = a_in;
-    else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) a[t] = F[o + i][o + 4 * t + g];
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) yt[t] = (4 * t + g == i) ? 1.0 : 0.0;
-    double rrow[4];                  // 1 / L_rr of rows r = 4t + g
-    int bad = -1;                    // first non-positive pivot (wave-uniform)
-#pragma unroll
-    for (int jb = 0; jb < 4; ++jb) {
-        const int j0 = 4 * jb;
-        colblk[i * 4 + g] = a[jb];                      // D[i][j0 + g]
-        rowblk[g * 16 + i] = yt[jb];                    // Y'[j0 + g][i]
-        __builtin_amdgcn_wave_barrier();
-        const double P00 = colblk[(j0 + 0) * 4 + 0];    // (the same addresses in every lane: broadcast reads)
-        const double P10 = colblk[(j0 + 1) * 4 + 0], P11 = colblk[(j0 + 1) * 4 + 1];
-        const double P20 = colblk[(j0 + 2) * 4 + 0], P21 = colblk[(j0 + 2) * 4 + 1], P22 = colblk[(j0 + 2) * 4 + 2];
-        const double P30 = colblk[(j0 + 3) * 4 + 0], P31 = colblk[(j0 + 3) * 4 + 1], P32 = colblk[(j0 + 3) * 4 + 2],
-                     P33 = colblk[(j0 + 3) * 4 + 3];
-        const double p0 = colblk[i * 4 + 0], p1 = colblk[i * 4 + 1], p2 = colblk[i * 4 + 2], p3 = colblk[i * 4 + 3];
-        const double y0 = rowblk[0 * 16 + i], y1 = rowblk[1 * 16 + i], y2 = rowblk[2 * 16 + i], y3 = rowblk[3 * 16 + i];
-        __builtin_amdgcn_wave_barrier();
-        // the 4 x 4 pivot block
-        const double r0 = rsqrt_nr(P00);
-        const double l10 = P10 * r0, l20 = P20 * r0, l30 = P30 * r0;
-        const double d1 = fma(-l10, l10, P11);
-        const double r1 = rsqrt_nr(d1);
-        const double l21 = fma(-l20, l10, P21) * r1, l31 = fma(-l30, l10, P31) * r1;
-        const double d2 = fma(-l21, l21, fma(-l20, l20, P22));
-        const double r2 = rsqrt_nr(d2);
-        const double l32 = fma(-l31, l21, fma(-l30, l20, P32)) * r2;
-        const double d3 = fma(-l32, l32, fma(-l31, l31, fma(-l30, l30, P33)));
-        const double r3 = rsqrt_nr(d3);
-        bad = (bad < 0 && !(P00 > 0.0)) ? j0 : bad;
-        bad = (bad < 0 && !(d1 > 0.0)) ? j0 + 1 : bad;
-        bad = (bad < 0 && !(d2 > 0.0)) ? j0 + 2 : bad;
-        bad = (bad < 0 && !(d3 > 0.0)) ? j0 + 3 : bad;
-        // this lane's row against the pivot block: M[i][0..3] = L[i][j0 .. j0+3]; it keeps column g (zero above the diagonal)
-        const double m0 = p0 * r0;
-        const double m1 = fma(-m0, l10, p1) * r1;
-        const double m2 = fma(-m1, l21, fma(-m0, l20, p2)) * r2;
-        const double m3 = fma(-m2, l32, fma(-m1, l31, fma(-m0, l30, p3))) * r3;
-        const double mraw = (g == 0) ? m0 : ((g == 1) ? m1 : ((g == 2) ? m2 : m3));
-        const double rg = (g == 0) ? r0 : ((g == 1) ? r1 : ((g == 2) ? r2 : r3));
-        const double mg = (i >= j0 + g) ? mraw : 0.0;
-        const double sg = (i > j0 + g) ? mraw * rg : 0.0;       // L[i][j0+g] / L[j0+g][j0+g], strictly below the diagonal
-        // rows j0 .. j0+3 of Y' after the elimination inside the block, in this lane's column; it keeps row g
-        const double w10 = l10 * r0, w20 = l20 * r0, w30 = l30 * r0, w21 = l21 * r1, w31 = l31 * r1, w32 = l32 * r2;
-        const double z1 = fma(-w10, y0, y1);
-        const double z2 = fma(-w21, z1, fma(-w20, y0, y2));
-        const double z3 = fma(-w32, z2, fma(-w31, z1, fma(-w30, y0, y3)));
-        const double zg = (g == 0) ? y0 : ((g == 1) ? z1 : ((g == 2) ? z2 : z3));
-        a = __builtin_amdgcn_mfma_f64_16x16x4f64(-mg, mg, a, 0, 0, 0);          // D -= M M^T (every column; the block's own ...
-        a[jb] = mg;                                                              // ... is final: L)
-        yt = __builtin_amdgcn_mfma_f64_16x16x4f64(-sg, zg, yt, 0, 0, 0);        // Y' -= S Z (rows of the block end up as Z)
-        rrow[jb] = rg;
-    }
-    if (lane == 0 && bad >= 0 && o + bad < nvalid && *info == 0) *info = gidx0 + o + bad + 1;   // LAPACK convention
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int c = 4 * t + g;                                    // column of D held in a[t]; row of Y' held in yt[t]
-        F[o + i][o + c] = (c > i) ? 0.0 : a[t];
-        Xd[c][i] = (i > c) ? 0.0 : yt[t] * rrow[t];
-    }
-}
-#else
-// one wave: Cholesky factor L_d (in place, upper part zeroed) and inverse Xd = L_d^-1 of the 16 x 16 block at F[o.., o..].
-// Lane (i = lane & 15, g = lane >> 4) holds a[t] = D[i][4g+t] and y[t] = Y[i][4g+t] (Y: forward elimination of the
-// identity, row i scaled by 1/L_ii at the end).  The single wave is instruction-issue bound, so per-element predicates
-// are replaced by zeros in the exchanged vectors: column j is published with rows < j zeroed, hence
-//   li = L[i][j] = 0 for i < j  and  lc = L[c][j] = 0 for c < j,   a[i][c] -= li * lc   needs no mask
-// (rows <= j only collect junk above the diagonal, which is never read), likewise Y[i][:] -= ls * Y[j][:] / L_jj with
-// ls = li for i > j, 0 otherwise.
-__device__ __forceinline__ void factor16_wave(double (*F)[LDT], int o, double (*Xd)[17], double* colbuf, double* rowbuf,
-                                              int lane, int* info, int gidx0, int nvalid, bool = false, acc4 = acc4{0, 0, 0, 0}) {
-    const int i = lane & 15, g = lane >> 4;
-    double a[4], y[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        a[t] = F[o + i][o + 4 * g + t];
-        y[t] = (i == 4 * g + t) ? 1.0 : 0.0;
-    }
-    double ri = 1.0;                 // 1 / L_ii of this lane's row
-    int bad = -1;                    // first non-positive pivot (wave-uniform)
-    // lanes that do not own the published column / row write to a dummy slot (no exec-mask branches)
-    double* const cdst = colbuf + i;
-    double* const cdummy = colbuf + 16 + (lane & 15);
-#pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        const int gj = j >> 2, tj = j & 3;
-        const double d = readlane_f64(a[tj], j + 16 * gj);          // pivot a_jj
-        *((g == gj) ? cdst : cdummy) = (i >= j) ? a[tj] : 0.0;
-        {
-            double* rdst = (i == j) ? (rowbuf + 4 * g) : (rowbuf + 16 + 4 * g);
-#pragma unroll
-            for (int t = 0; t < 4; ++t) rdst[t] = y[t];
-        }
-        __builtin_amdgcn_wave_barrier();
-        const double ci = colbuf[i];
-        double cc[4], rr[4];
-#pragma unroll
-        for (int t = 0; t < 4; ++t) { cc[t] = colbuf[4 * g + t]; rr[t] = rowbuf[4 * g + t]; }
-        __builtin_amdgcn_wave_barrier();
-        bad = (bad < 0 && !(d > 0.0)) ? j : bad;
-        const double rinv = rsqrt_nr(d);
-        const double li = ci * rinv;                                // L[i][j]  (0 above the diagonal, sqrt(a_jj) on it)
-        ri = (i == j) ? rinv : ri;
-#if POTRF_FOLD
-        // both rank-1 updates through w = L[i][j] / L[j][j] = a_ij / a_jj: ten fp64 operations per column instead of sixteen (the
-        // multiplier is folded once per lane instead of once per element)
-        const double w = li * rinv;
-        const double ws = (i == j) ? 0.0 : w;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            a[t] = fma(-w, cc[t], a[t]);
-            y[t] = fma(-ws, rr[t], y[t]);
-        }
-#else
-        const double ls = (i == j) ? 0.0 : li;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            a[t] = fma(-li, cc[t] * rinv, a[t]);
-            y[t] = fma(-ls, rr[t] * rinv, y[t]);
-        }
-#endif
-        if (g == gj) a[tj] = li;
-    }
-    if (lane == 0 && bad >= 0 && o + bad < nvalid && *info == 0) *info = gidx0 + o + bad + 1;   // LAPACK convention
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int c = 4 * g + t;
-        F[o + i][o + c] = (c > i) ? 0.0 : a[t];
-        Xd[i][c] = (c > i) ? 0.0 : y[t] * ri;
-    }
-}
-
-#endif      // POTRF_F16_BLK
-
-// 16 x 16 x 16 product on one wave:  P[m][n] = sum_q Aop(m, q) Bop(q, n);  operands through pointers + strides
-//   Aop(m, q) = Ab[m * lda_ + q];   Bop(q, n) = B_NK ? Bb[n * ldb_ + q] : Bb[q * ldb_ + n]
-#ifndef POTRF_CRIT_PFORM
-#define POTRF_CRIT_PFORM 1     // 1: the critical tile's rank-64 update through P = A_ik X_k^T (40 + 16 MFMAs on wave 0's path instead of 64 + 16)
-#endif
-#ifndef POTRF_PROD16_SPLIT
-#define POTRF_PROD16_SPLIT 1
-#endif
-template <bool B_NK>
-__device__ __forceinline__ acc4 prod16(const double* Ab, int lda_, const double* Bb, int ldb_, int lane) {
-#if POTRF_PROD16_SPLIT
-    // two accumulators: one dependent chain of four fp64 MFMAs waits out every instruction's latency (these 16 x 16 x 16 products sit on the
-    // serial path of factor64_lds: the panel block and the next diagonal block's update of wave 0)
-    acc4 acc0{0, 0, 0, 0}, acc1{0, 0, 0, 0};
-    double a[4], b[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int kq = 4 * t + (lane >> 4), r = lane & 15;
-        a[t] = Ab[r * lda_ + kq];
-        b[t] = B_NK ? Bb[r * ldb_ + kq] : Bb[kq * ldb_ + r];
-    }
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0], b[0], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1], b[1], acc1, 0, 0, 0);
-    acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[2], b[2], acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[3], b[3], acc1, 0, 0, 0);
-    return acc0 + acc1;
-#else
-    acc4 acc{0, 0, 0, 0};
-#pragma unroll
-    for (int kk = 0; kk < 16; kk += 4) {
-        const int kq = kk + (lane >> 4), r = lane & 15;
-        const double a = Ab[r * lda_ + kq];
-        const double b = B_NK ? Bb[r * ldb_ + kq] : Bb[kq * ldb_ + r];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc, 0, 0, 0);
-    }
-    return acc;
-#endif
-}
-
-// Factor F (64 x 64, lower, in LDS) -> L in place; Y <- X = L^-1.  256 threads.  While wave 0 runs the serial 16-column
-// chain of the next diagonal sub-block, waves 1..3 do everything that is already final: the other trailing sub-blocks,
-// the global stores of row-block kb of X and column-block kb of L, and the running sum W = X^T X = sum_kb X_kb^T X_kb
-// (lower blocks, mirrored on store) -- so the critical path is 4 x (factor16 + one panel product + one update product).
-//
-// Y is never initialised: its 16 x 16 blocks are ASSIGNED at their first touch (block (ib, kb) of the elimination of the identity
-// starts as -L_{ib,kb} X_{kb,kb}: the identity has nothing there), blocks above the diagonal are never touched and leave as zeros
-// in the stores to Xg.  So Y may alias a tile that other waves are still reading until the barrier behind the first chain
-// (the critical tile's update keeps A_ik there, crit_tile_update).
-// first_from_regs: wave 0 starts the first 16-column chain from a0 (see factor16_wave) instead of from F.
-__device__ __forceinline__ void factor64_lds(double (*F)[LDT], double (*Y)[LDT], double (*Xd)[17], double* colbuf,
-                                             double* rowbuf, int tid, int* info, int gidx0, int nvalid,
-                                             double* __restrict__ Ag, int64_t lda, double* __restrict__ Xg,
-                                             double* __restrict__ Wg, bool first_from_regs = false,
-                                             acc4 a0 = acc4{0, 0, 0, 0}) {
-    const int lane = tid & 63, wave = tid >> 6;
-    const int mrow = (lane >> 4), ncol = lane & 15;
-    // (written for waves 0..3; in an 8-wave workgroup waves 4..7 only take part in the barriers)
-    // No barrier between the caller's writes of F and the first 16-column chain: wave 0 wrote the 16 x 16 block it starts
-    // with ITSELF (the caller guarantees that) or holds it in registers, so it goes straight on while waves 1..3 finish their
-    // parts of F; the barrier behind the first chain closes that.
-    acc4 wacc[4];                        // waves 1..3: lower blocks idx = (wave - 1) + 3 s of W
-#pragma unroll
-    for (int sI = 0; sI < 4; ++sI) wacc[sI] = acc4{0, 0, 0, 0};
-#pragma unroll 1      // one copy of the 16-column chain: trips 2..4 hit the instruction cache
-    for (int kb = 0; kb < 4; ++kb) {
-        const int o = kb * 16;
-#ifdef POTRF_DEBUG
-        if (tid == 0 && kb == 0 && gidx0 == (POTRF_DEBUG_K + 1) * 64) chol_dbg[8] = __builtin_amdgcn_s_memtime();
-#endif
-        if (wave == 0) factor16_wave(F, o, Xd, colbuf, rowbuf, lane, info, gidx0, nvalid, first_from_regs && kb == 0, a0);
-#ifdef POTRF_DEBUG
-        if (tid == 0 && kb == 0 && gidx0 == (POTRF_DEBUG_K + 1) * 64) chol_dbg[9] = __builtin_amdgcn_s_memtime();
-#endif
-        __syncthreads();
-        // (b) 4 tasks, one per wave: panel blocks ib > kb, row-block kb of X (cb < kb), and X_{kb,kb} = Xd
-        if (wave < 4) {
-            const int t = wave;
-            if (t < 3 - kb) {                    // L_{ib,kb} = F_{ib,kb} Xd^T
-                const int ib = kb + 1 + t;
-                acc4 r = prod16<true>(&F[ib * 16][o], LDT, &Xd[0][0], 17, lane);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) F[ib * 16 + mrow + 4 * q][o + ncol] = r[q];
-            } else if (t < 3) {                  // X_{kb,cb} = Xd Y_{kb,cb},  cb = t - (3 - kb)  in [0, kb)
-                const int cb = t - (3 - kb);
-                acc4 r = prod16<false>(&Xd[0][0], 17, &Y[o][cb * 16], LDT, lane);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) Y[o + mrow + 4 * q][cb * 16 + ncol] = r[q];
-            } else {                             // X_{kb,kb} = Xd
-#pragma unroll
-                for (int q = 0; q < 4; ++q) Y[o + mrow + 4 * q][o + ncol] = Xd[mrow + 4 * q][ncol];
-            }
-        }
-        __syncthreads();
-#ifdef POTRF_DEBUG
-        if (tid == 0 && kb == 0 && gidx0 == (POTRF_DEBUG_K + 1) * 64) chol_dbg[10] = __builtin_amdgcn_s_memtime();
-#endif
-        // (c) trailing sub-blocks:  F_{ib,jb} -= L_{ib,kb} L_{jb,kb}^T (kb < jb <= ib),  Y_{ib,cb} -= L_{ib,kb} X_{kb,cb} (cb <= kb).
-        // Look-ahead: wave 0 updates only the NEXT diagonal sub-block (from the panel block it produced itself) and goes
-        // straight on to factor it; waves 1..3 touch neither that sub-block nor Xd / colbuf / rowbuf; the barrier after
-        // the next factor16 closes the phase.
-        if (wave >= 4) {
-        } else if (wave == 0) {
-            if (kb < 3) {
-                const int ib = kb + 1;
-                acc4 r = prod16<true>(&F[ib * 16][o], LDT, &F[ib * 16][o], LDT, lane);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) F[ib * 16 + mrow + 4 * q][ib * 16 + ncol] -= r[q];
-            }
-        } else {
-            int task = 0;
-            for (int ib = kb + 1; ib < 4; ++ib) {
-                for (int jb = kb + 1; jb <= ib; ++jb) {
-                    if (ib == kb + 1 && jb == kb + 1) continue;          // wave 0
-                    if (1 + (task++ % 3) != wave) continue;
-                    acc4 r = prod16<true>(&F[ib * 16][o], LDT, &F[jb * 16][o], LDT, lane);
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) F[ib * 16 + mrow + 4 * q][jb * 16 + ncol] -= r[q];
-                }
-                for (int cb = 0; cb <= kb; ++cb) {
-                    if (1 + (task++ % 3) != wave) continue;
-                    acc4 r = prod16<false>(&F[ib * 16][o], LDT, &Y[o][cb * 16], LDT, lane);
-                    if (cb == kb) {                  // first touch of block (ib, kb): the identity is zero there
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) Y[ib * 16 + mrow + 4 * q][cb * 16 + ncol] = -r[q];
-                    } else {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) Y[ib * 16 + mrow + 4 * q][cb * 16 + ncol] -= r[q];
-                    }
-                }
-            }
-            // final data of this sub-block step: rows o..o+15 of X, columns o..o+15 of L -> global
-            const int t3 = tid - 64;
-            for (int e = t3; e < 16 * 64; e += 192) {
-                const int r = o + (e >> 6), c = e & 63;
-                Xg[r * 64 + c] = (c < o + 16) ? Y[r][c] : 0.0;            // (blocks above the diagonal: never touched)
-            }
-            for (int e = t3; e < (64 - o) * 16; e += 192) {
-                const int r = o + (e >> 4), c = o + (e & 15);
-                if (r < nvalid && c <= r) Ag[(int64_t)r * lda + c] = F[r][c];
-            }
-            // W += X_kb^T X_kb on the lower blocks (mb >= nb) owned by this wave; X_{kb,cb} = 0 for cb > kb
-#pragma unroll
-            for (int sI = 0; sI < 4; ++sI) {
-                const int idx = (wave - 1) + 3 * sI;
-                const int mb = (idx >= 6) ? 3 : ((idx >= 3) ? 2 : ((idx >= 1) ? 1 : 0)), nb = idx - mb * (mb + 1) / 2;
-                if (idx < 10 && mb <= kb) {
-#pragma unroll
-                    for (int kq0 = 0; kq0 < 16; kq0 += 4) {
-                        const int kq = o + kq0 + (lane >> 4);
-                        wacc[sI] = __builtin_amdgcn_mfma_f64_16x16x4f64(Y[kq][mb * 16 + ncol], Y[kq][nb * 16 + ncol], wacc[sI], 0, 0, 0);
-                    }
-                }
-            }
-        }
-#ifdef POTRF_DEBUG
-        if (tid == 0 && kb == 0 && gidx0 == (POTRF_DEBUG_K + 1) * 64) chol_dbg[11] = __builtin_amdgcn_s_memtime();
-        if (tid == 0 && gidx0 == (POTRF_DEBUG_K + 1) * 64) chol_dbg[12 + kb] = __builtin_amdgcn_s_memtime();      // end of sub-step kb
-#endif
-    }
-    if (wave > 0 && wave < 4) {
-#pragma unroll
-        for (int sI = 0; sI < 4; ++sI) {
-            const int idx = (wave - 1) + 3 * sI;
-            const int mb = (idx >= 6) ? 3 : ((idx >= 3) ? 2 : ((idx >= 1) ? 1 : 0)), nb = idx - mb * (mb + 1) / 2;
-            if (idx < 10) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int m = mb * 16 + mrow + 4 * q, nn = nb * 16 + ncol;
-                    Wg[m * 64 + nn] = wacc[sI][q];
-                    Wg[nn * 64 + m] = wacc[sI][q];
-                }
-            }
-        }
-    }
-}
-
 // Fused inverse (Rw != nullptr): the same launches also run the forward elimination of the identity, block row by
 // block row, so that Y = L^-1 is complete when the factorisation is (no separate trtri recursion):
 //   R-tiles  (i > k, j <= k):  R_ij -= (A_ik W_k) R_kj,  R_kk = I     (the W_k form of  R_i -= L_ik Y_k,  Y_k = X_k R_k)
@@ -796,13 +397,6 @@ __device__ __forceinline__ void chol_inverse_tile(double (*S)[64][LDT], const do
                     ra[u] = A[((i0 + r < n) ? arow0 + u * astep : alast) + k0 + c];
                     rw[u] = Lk[r * 64 + c];
                 }
-#if !POTRF_PIPE_LATE0
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) cs[0][t >> 2][jj][t & 3] = Cg[t * rstep + jj * 16];
-                pipe_dma_tile(S[2], Bg, ldr);                      // B_0 = R_kj of the strip's first column (np == 0: unused); issued last, as above
-#endif
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
                     const int r = (tid >> 6) + 4 * u;
@@ -811,13 +405,11 @@ __device__ __forceinline__ void chol_inverse_tile(double (*S)[64][LDT], const do
                 }
             }
             __syncthreads();
-#if POTRF_PIPE_LATE0
             pipe_dma_tile(S[2], Bg, ldr);
 #pragma unroll
             for (int t = 0; t < 8; ++t)
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) cs[0][t >> 2][jj][t & 3] = Cg[t * rstep + jj * 16];
-#endif
             acc4 acc[2][2];
 #ifdef POTRF_TRACE
             if (trs_) { TR(1); TR_VAL(20, (ncols << 16) | (e / spr)); }
@@ -855,11 +447,7 @@ __device__ __forceinline__ void chol_inverse_tile(double (*S)[64][LDT], const do
 #pragma unroll
                 for (int jj = 0; jj < NJ; ++jj)
 #pragma unroll
-#ifdef POTRF_ABL_NOC
-                    for (int q = 0; q < 4; ++q) ro[i][jj][q] = 1e-3 * q;
-#else
                     for (int q = 0; q < 4; ++q) ro[i][jj][q] = rdst[(int64_t)(i * 16 + 4 * q) * ldr + jj * 16];
-#endif
         } else {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
@@ -881,18 +469,7 @@ __device__ __forceinline__ void chol_inverse_tile(double (*S)[64][LDT], const do
 #endif
     acc4 acc[2][NJ];
     if (!ytile) {
-#if defined(POTRF_ABL_P1) || defined(POTRF_ABL_NOP)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int jj = 0; jj < NJ; ++jj) acc[i][jj] = acc4{1e-3, 1e-3, 1e-3, 1e-3};
-#else
-#if POTRF_IL
-        if constexpr (NW == 4) tile_product_il<true, false>(S[0], S[1], lane, wr, wc, acc, [](int) {});
-        else
-#endif
         tile_product<true, NW>(S[0], S[1], lane, wr, wc, acc);          // T = A_ik W_k
-#endif
 #ifdef POTRF_TRACE
         if (trs_) TR(2);
 #endif
@@ -923,39 +500,6 @@ __device__ __forceinline__ void chol_inverse_tile(double (*S)[64][LDT], const do
             if (trs_ && cc < 5) TR(3 + 3 * cc);
 #endif
             double* const rcur = rdst;
-#if POTRF_IL && !defined(POTRF_ABL_NOP) && !defined(POTRF_ABL_NOC)
-            if constexpr (NW == 4) {
-                if (cc + 1 < ncols) {                // next block column: its loads go out BETWEEN the MFMAs of this product
-                    ++j; j0 += 64; rdst += 64;
-                    if (j == k) {                    // (the identity block of R's row k: nothing to load)
-#pragma unroll
-                        for (int u = 0; u < NU; ++u) rc[u] = (((tid >> 6) + NW * u) == (tid & 63)) ? 1.0 : 0.0;
-#pragma unroll
-                        for (int i = 0; i < 2; ++i)
-#pragma unroll
-                            for (int jj = 0; jj < NJ; ++jj)
-#pragma unroll
-                                for (int q = 0; q < 4; ++q) ro[i][jj][q] = 0.0;
-                        tile_product_il<false, true>(S[0], S[1], lane, wr, wc, acc, [](int) {});
-                    } else {
-                        const double* prc = Rw + (int64_t)(k0 + (tid >> 6)) * ldr + j0 + (tid & 63);
-                        const double* pro = rdst;
-                        const int64_t step4 = (int64_t)4 * ldr;
-                        auto pf = [&](int ks) {
-                            rc[ks] = *prc;
-                            prc += step4;
-                            const int t = ks & 7;
-                            ro[t >> 2][ks >> 3][t & 3] = pro[(ks >> 3) * 16];
-                            pro += (t == 7) ? -7 * step4 : step4;
-                        };
-                        tile_product_il<false, true>(S[0], S[1], lane, wr, wc, acc, pf);
-                    }
-                } else {
-                    tile_product_il<false, true>(S[0], S[1], lane, wr, wc, acc, [](int) {});
-                }
-                goto inv_product_done;
-            }
-#endif
             if (cc + 1 < ncols) {                    // next block column: requested now, consumed after this product
                 ++j; j0 += 64; rdst += 64;
 #pragma unroll
@@ -969,27 +513,15 @@ __device__ __forceinline__ void chol_inverse_tile(double (*S)[64][LDT], const do
                     for (int jj = 0; jj < NJ; ++jj)
 #pragma unroll
                         for (int q = 0; q < 4; ++q)
-#ifdef POTRF_ABL_NOC
-                            ro[i][jj][q] = 1e-3 * q;
-#else
                             ro[i][jj][q] = (j == k) ? 0.0 : rdst[(int64_t)(i * 16 + 4 * q) * ldr + jj * 16];
-#endif
             }
-#ifndef POTRF_ABL_NOP
             tile_product<false, NW, true>(S[0], S[1], lane, wr, wc, acc);   // R_ij - T R_kj
-#endif
-#if POTRF_IL && !defined(POTRF_ABL_NOP) && !defined(POTRF_ABL_NOC)
-inv_product_done:
-#endif
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
                 for (int jj = 0; jj < NJ; ++jj)
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-#ifdef POTRF_ABL_NOC
-                        if (acc[i][jj][q] == 123.456)
-#endif
                         rcur[(int64_t)(i * 16 + 4 * q) * ldr + jj * 16] = acc[i][jj][q];
 #ifdef POTRF_TRACE
             if (trs_ && cc < 5) TR(4 + 3 * cc);
@@ -1000,10 +532,6 @@ inv_product_done:
             if (cc + 1 < ncols) __syncthreads();     // every wave is done reading R_kj out of S[1]
         }
     } else {
-#if POTRF_IL
-        if constexpr (NW == 4) tile_product_il<false, false>(S[0], S[1], lane, wr, wc, acc, [](int) {});
-        else
-#endif
         tile_product<false, NW>(S[0], S[1], lane, wr, wc, acc);         // X_k R_kj
         if (YT == nullptr) {
 #pragma unroll
@@ -1037,141 +565,10 @@ inv_product_done:
     }
 }
 
-#ifndef POTRF_CRIT_SLIVER
-#define POTRF_CRIT_SLIVER 1     // 1: the critical tile's rank-64 update in 16-row strips out of registers (crit_tile_update); 0: as every other tile
-#endif
-// The critical workgroup's rank-64 update  D = C - (A W) A^T  of the NEXT diagonal tile (A = A_{k+1,k}, W = W_k, C = A_{k+1,k+1}),
-// ordered for the serial chain that follows it instead of for throughput.  Every other tile forms T = A W with four waves of
-// 32 x 32, sends -T through LDS and runs a second 64^3 product (two barriers, ~10.6k cycles + 3.3k of LDS moves) before the
-// factorisation can start.  Here wave w owns the 16-row strip w of the tile:
-//   * U = T_w^T = W A_w^T (64 x 16: four accumulator blocks, K = 64).  Its C/D register layout (lane (c, g), register q <->
-//     U[g + 4q][c] = T_w[c][g + 4q]) IS the A-operand layout of T_w for the next product -- T never goes through LDS;
-//   * D[w][nb] = C[w][nb] - T_w A_nb^T only for the blocks nb <= w on or below the diagonal (16 / 32 / 48 / 64 MFMAs for wave 0..3);
-//   * wave 0 therefore holds the leading 16 x 16 block after 64 + 16 MFMAs and starts the 16-column chain OUT OF ITS REGISTERS
-//     (it loads C transposed, C[n][g + 4q]: the accumulator then holds D^T, whose register layout is the one factor16_wave wants,
-//     lower triangle from valid data); waves 1..3 finish their strips in the shadow of that chain and meet it at its barrier.
-// LDS: S[0] = A (read until the end of the second product, then the inverse's work tile Y -- never initialised, see factor64_lds),
-// S[1] = W (dead after the one barrier between the two products, then F).  Returns wave 0's leading block in a0.
-__device__ __forceinline__ void crit_tile_update(double (*S)[64][LDT], const double* __restrict__ A, int64_t lda, int n, int k,
-                                                 const double* __restrict__ Wk, int tid, acc4& a0
-#ifdef POTRF_DEBUG
-                                                 , unsigned long long* st_
-#endif
-                                                 ) {
-    const int lane = tid & 63, wave = tid >> 6, i = lane & 15, g = lane >> 4;
-    const int k0 = k * 64, i0 = (k + 1) * 64;
-    const int64_t alast = (int64_t)(n - 1) * lda;
-    acc4 cacc[4];
-    {
-        double ra[16], rw[16];
-        const int64_t arow0 = (int64_t)(i0 + (tid >> 6)) * lda, astep = (int64_t)4 * lda;
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int r = (tid >> 6) + 4 * u, c = tid & 63;
-            rw[u] = Wk[r * 64 + c];
-            ra[u] = A[((i0 + r < n) ? arow0 + u * astep : alast) + k0 + c];
-        }
-        // this strip's blocks of C, requested behind the operands and consumed after the first product
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            if (nb > wave) { cacc[nb] = acc4{0, 0, 0, 0}; continue; }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                // wave 0 (its one block is the tile's leading diagonal block): transposed, element (row g + 4q, column i) <- C[i][g + 4q]
-                const int rr = (wave == 0) ? i : 16 * wave + g + 4 * q, cc = (wave == 0) ? g + 4 * q : 16 * nb + i;
-                const int gr = min(i0 + rr, n - 1), gc = min(i0 + cc, n - 1);
-                cacc[nb][q] = A[(int64_t)gr * lda + gc];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            const int r = (tid >> 6) + 4 * u, c = tid & 63;
-            S[0][r][c] = (i0 + r < n) ? ra[u] : 0.0;
-            S[1][r][c] = rw[u];
-        }
-    }
-    __syncthreads();
-    CHOL_STAMP(1);
-    // U = W A_w^T: A operand W[16 cb + m][k] (lane (m, k)), B operand A_w[n][k] (lane (n, k)); four independent accumulators
-    // (POTRF_CRIT_PFORM: S[1] holds X_k instead -- A_ik W_k A_ik^T = (A_ik X_k^T)(A_ik X_k^T)^T -- and U = X A_w^T = P_w^T: X_k is lower
-    //  triangular, so column block cb of P needs the k blocks 0 .. cb only: 40 MFMAs instead of 64)
-    acc4 U[4];
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb) U[cb] = acc4{0, 0, 0, 0};
-#pragma unroll
-    for (int ks = 0; ks < 16; ++ks) {
-        const int kq = 4 * ks + g;
-        const double bop = S[0][16 * wave + i][kq];
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            if (POTRF_CRIT_PFORM && cb < (ks >> 2)) continue;
-            U[cb] = __builtin_amdgcn_mfma_f64_16x16x4f64(S[1][16 * cb + i][kq], bop, U[cb], 0, 0, 0);
-        }
-    }
-    CHOL_STAMP(4);
-    __syncthreads();                 // W is dead: S[1] becomes F
-#if POTRF_CRIT_PFORM
-    // P replaces A in S[0] (every wave is done with A): strip w's rows from this wave's accumulators (register q of lane (i, g) = P[16 w + i][16 cb + 4 q + g]);
-    // the second products below then read P_nb where they read A_nb
-#pragma unroll
-    for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) S[0][16 * wave + i][16 * cb + 4 * q + g] = U[cb][q];
-    __syncthreads();
-#endif
-    CHOL_STAMP(5);
-    // D[w][nb] = C[w][nb] - T_w A_nb^T, T_w from the registers of U; the leading block (wave 0) on two accumulators (one
-    // dependent chain of 16 fp64 MFMAs would wait out every instruction's latency)
-    if (wave == 0) {
-        acc4 d0 = cacc[0], d1 = acc4{0, 0, 0, 0};
-#pragma unroll
-        for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const double bop = S[0][i][16 * cb + 4 * q + g];
-                if (q & 1) d1 = __builtin_amdgcn_mfma_f64_16x16x4f64(-U[cb][q], bop, d1, 0, 0, 0);
-                else d0 = __builtin_amdgcn_mfma_f64_16x16x4f64(-U[cb][q], bop, d0, 0, 0, 0);
-            }
-        CHOL_STAMP(7);
-        // (symmetric update term: the transposed C makes this D^T) a0[t] = D[i][4t + g] for 4t + g <= i, zero above, identity padding
-        // of a ragged last block
-        const int nr = n - i0;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int c = 4 * t + g;
-            const bool in = i < nr && c <= i;
-            a0[t] = in ? d0[t] + d1[t] : ((i == c && i >= nr) ? 1.0 : 0.0);
-        }
-    } else {
-        double (*F)[LDT] = S[1];
-        const int nr = n - i0;
-#pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
-            if (nb > wave) continue;
-            acc4 d = cacc[nb];
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    d = __builtin_amdgcn_mfma_f64_16x16x4f64(-U[cb][q], S[0][16 * nb + i][16 * cb + 4 * q + g], d, 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int ml = 16 * wave + g + 4 * q, nl = 16 * nb + i;
-                const bool in = ml < nr && nl <= ml;
-                F[ml][nl] = in ? d[q] : ((ml == nl) ? 1.0 : 0.0);
-            }
-        }
-    }
-}
-
-#ifndef POTRF_CRIT_STRIPS
-#define POTRF_CRIT_STRIPS 1     // 1: the critical workgroup keeps the diagonal tile in REGISTERS, one 16-row strip per wave (factor64_strips below); 0: round 5's factor64_lds
-#endif
-#if POTRF_CRIT_STRIPS
 // -------------------------------------------------------------------------------------------------
 // Round 6: the critical workgroup's factorisation with the diagonal tile in registers and the inverse OFF the serial chain.
 //
-// Round 5 (factor64_lds): per 16-column block, ONE wave factors AND inverts the 16 x 16 diagonal block (factor16_wave, 4.4-4.7k cycles),
+// Round 5 (the tile in LDS; removed in the build-variant clean-up, last present in 8a953b7): per 16-column block, ONE wave factors AND inverts the 16 x 16 diagonal block (4.4-4.7k cycles),
 // then two barrier phases form the panel L_{ib,kb} = F_{ib,kb} X_d^T and the next diagonal block's update -- 6.7k cycles per block,
 // 26.5k for the tile (of the critical workgroup's 37.6k).  The panel needed X_d only because it was written as an MFMA product.
 // Here wave w owns rows 16 w .. 16 w + 15 of the tile for the WHOLE factorisation, in the register image
@@ -1179,7 +576,7 @@ __device__ __forceinline__ void crit_tile_update(double (*S)[64][LDT], const dou
 // and block column kb is processed by all waves w >= kb together, four columns at a time:
 //   * the DIAGONAL wave (w = kb) publishes the 16 x 4 column block of its strip, factors the 4 x 4 pivot block (four dependent
 //     rsqrt), substitutes its rows against it and applies the rank-4 update D -= M M^T with ONE MFMA out of its own registers
-//     (as factor16_wave did) -- but runs no forward elimination of the identity beside it: L only;
+//     (as round 5's one-wave chain did) -- but runs no forward elimination of the identity beside it: L only;
 //   * the FOLLOWERS (w > kb) read the published block, redo the pivot factorisation (the same ten numbers in every lane), substitute
 //     their own rows AND the diagonal block's rows (the B / A operands of the update D_w -= M_w M_d^T, computed transposed so that the
 //     accumulator IS the a image), one block behind the diagonal wave and never waited for by it: the panel L_{w,kb} comes out of
@@ -1241,23 +638,17 @@ __device__ __forceinline__ void fl_wait(LVI* f, int v, int* info) {
     asm volatile("" ::: "memory");
 }
 struct Piv4 { double r0, r1, r2, r3, l10, l20, l30, l21, l31, l32; };
-#ifndef POTRF_RSQ_HALLEY
-#define POTRF_RSQ_HALLEY 1      // 1: v_rsq_f64 + ONE third-order step (5 instructions); 0: two Newton steps (8 instructions, rsqrt_nr)
-#endif
 // 1 / sqrt(d) for the serial chain.  A single wave issues one fp64 instruction per ~5 cycles and a dependent one waits no longer than that
 // (tools/lat_probe.cpp: dependent v_fma_f64 5.3, v_rsq_f64 16 cycles): the chain is bound by its INSTRUCTION COUNT.  v_rsq_f64 is good to
 // 2.5e-8, so with e = 1 - d y^2 the step y (1 + e / 2 + 3 e^2 / 8) leaves 5 e^3 / 16 ~ 5e-24: full accuracy from five instructions.
+// (Two Newton steps instead, POTRF_RSQ_HALLEY = 0 with POTRF_NEWTON = 2: 8 instructions; removed in the build-variant clean-up; last present in 8a953b7.)
 __device__ __forceinline__ double rsqrt_chain(double d) {
-#if POTRF_RSQ_HALLEY
     const double y = __builtin_amdgcn_rsq(d);
     const double gq = d * y;
     const double e = fma(-gq, y, 1.0);
     const double pq = fma(e, 0.375, 0.5);
     const double ye = y * e;
     return fma(ye, pq, y);
-#else
-    return rsqrt_nr(d);
-#endif
 }
 // the 4 x 4 pivot block (lower entries P_rc): reciprocal square roots of the pivots and the block's L entries
 template <bool CHECK>
@@ -1444,7 +835,7 @@ __device__ __forceinline__ acc4 strips_invfollow(const CritLds& S, int kb, int w
     return x;
 }
 // X_ww = L_ww^-1 from the register image of L_ww (a[t] = L[i][4 t + g], zero above the diagonal; rr[t] = 1 / L_cc, c = 4 t + g):
-// forward elimination of the identity with unscaled rows, four rows per exchange (the Y' half of factor16_wave); returns
+// forward elimination of the identity with unscaled rows, four rows per exchange (the Y' half of round 5's one-wave chain); returns
 // x[t] = X[4 t + g][i], the MFMA result layout
 __device__ __forceinline__ acc4 invert16_regs(LD* own, const acc4& a, const acc4& rr, int lane) {
     const int i = lane & 15, g = lane >> 4;
@@ -1760,7 +1151,7 @@ __device__ __forceinline__ void factor64_strips(const CritLds& S, acc4 (&a)[4], 
 #endif
 }
 
-// The update phase for factor64_strips: as crit_tile_update (P = A X_k^T strip by strip, P back to LDS, D = C - P P^T), but EVERY wave's
+// The update phase for factor64_strips: as round 5's update (P = A X_k^T strip by strip, P back to LDS, D = C - P P^T), but EVERY wave's
 // blocks come out in the a image: block (w, nb) as the transposed product  D^T = C^T - P_nb P_w^T  (A operand: P_nb out of LDS, B operand:
 // the registers of U = P_w^T), C loaded in the a image.  k < 0: the first tile of the matrix, loaded as it is.
 __device__ __forceinline__ void crit_strips_update(double (*S)[64][LDT], const double* __restrict__ A, int64_t lda, int n, int k,
@@ -1871,8 +1262,8 @@ __device__ __forceinline__ void crit_strips_update(double (*S)[64][LDT], const d
         a[nb] = mv;
     }
 }
-#endif      // POTRF_CRIT_STRIPS
 
+constexpr int POTRF_NW = 4;         // waves per workgroup of the step launches.  8 (each 64 x 64 tile product split 32 x 16 per wave) measured slower at M' = 3000 (1.78-1.93 vs 1.70 ms); at 600 5 % faster in round 2, 28 % slower on the round-4 kernel (0.319 vs 0.249 ms)
 #ifndef POTRF_MINW
 #define POTRF_MINW (POTRF_NW / 2)
 #endif
@@ -1882,18 +1273,9 @@ __device__ __forceinline__ void crit_strips_update(double (*S)[64][LDT], const d
 #ifndef POTRF_PIPE_WGS
 #define POTRF_PIPE_WGS 250          // workgroups of a PIPE launch (one per CU; the critical workgroup is one of them)
 #endif
-#ifndef POTRF_PIPE_LATE0
-#define POTRF_PIPE_LATE0 1          // 1: column 0 of a pipelined strip (B_0 by LDS-DMA, C_0) is requested behind the barrier in front of the T product
-#endif
-#ifndef POTRF_PIPE_FROM
-#define POTRF_PIPE_FROM 0           // (A/B builds) first block column that may use the PIPE kernel, on top of the caller's pipe_from
-#endif
 #ifndef POTRF_PIPE_MINW
 #define POTRF_PIPE_MINW 1           // the PIPE instantiation: 101 KB of LDS, one workgroup per CU whatever the registers (asking for 2 here to get a
                                     // 256-register budget does not take: the compiler sees the LDS size and budgets for one wave per SIMD anyway)
-#endif
-#ifndef POTRF_PIPE
-#define POTRF_PIPE 1        // 1: launches from `pipe_from` on (launch_potrf_blocked) use the PIPE instantiation: software-pipelined strips (strip_pipe)
 #endif
 // PIPE: three LDS tiles and up to 512 registers -- ONE workgroup per CU -- with the strips of both tile roles software-pipelined
 // (strip_pipe above); strip_e: strip length of the ragged last tile row of the update role, which keeps the two-barrier strip loop
@@ -1909,7 +1291,10 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
     // registers while the first product runs.
     __shared__ double S[PIPE ? 3 : 2][64][LDT];
     __shared__ double Xd[16][17];
-    __shared__ double colbuf[64], rowbuf[64];      // column-by-column chain: [16..31] dummy slots of the non-owner lanes; 4-column blocks: [16][4] / [4][16]
+    __shared__ double colbuf[64];                  // the critical workgroup's flag words (CritLds::fl)
+#ifdef POTRF_DEBUG
+    __shared__ double rowbuf[64];                  // ... and its stamp words
+#endif
     constexpr int WC = NW / 2, NJ = 8 / NW, NU = 64 / NW;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave / WC, wc = wave % WC;
     const int b = blockIdx.x;
@@ -1925,8 +1310,10 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
 #endif
         return;
     }
-#if POTRF_CRIT_STRIPS && POTRF_CRIT_PFORM
-    if (NW == 4 && b == 0) {                       // the critical workgroup (k = -1: the matrix's first tile, a launch of its own)
+    static_assert(NW == 4, "the critical workgroup's register-strip path is written for four waves");
+    // Workgroup 0 is ALWAYS the critical workgroup and returns inside this block; k = -1 (the matrix's first tile) is launched with
+    // one workgroup.  So everything below runs with b != 0 and k >= 0.
+    if (b == 0) {
         CHOL_STAMP_DECL;
         CHOL_STAMP(0);
         acc4 a[4];
@@ -1960,30 +1347,6 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
         TR_FLUSH;
         return;
     }
-#elif POTRF_CRIT_SLIVER
-    if (NW == 4 && b == 0 && k >= 0) {             // the critical workgroup: update of the next diagonal tile ordered for the chain
-        CHOL_STAMP_DECL;
-        CHOL_STAMP(0);
-        acc4 a0;
-#ifdef POTRF_DEBUG
-        crit_tile_update(S, A, lda, n, k, (POTRF_CRIT_PFORM ? Xws : Wws) + (size_t)k * 4096, tid, a0, st_);
-        st_[6] = st_[5];
-#else
-        crit_tile_update(S, A, lda, n, k, (POTRF_CRIT_PFORM ? Xws : Wws) + (size_t)k * 4096, tid, a0);
-#endif
-        CHOL_STAMP(2);
-        TR(1);
-        const int kk = k + 1, r0 = kk * 64, nr = (n - r0 < 64) ? (n - r0) : 64;
-        factor64_lds(S[1], S[0], Xd, colbuf, rowbuf, tid, info, r0, nr, A + (int64_t)r0 * lda + r0, lda, Xws + (size_t)kk * 4096,
-                     Wws + (size_t)kk * 4096, true, a0);
-        CHOL_STAMP(3);
-        CHOL_STAMP_FLUSH;
-        TR(2);
-        TR_VAL(22, 0);
-        TR_FLUSH;
-        return;
-    }
-#endif
     // tile row ti holds ti + 1 update tiles, dealt to workgroups in strips of strip block columns (block 0: the diagonal tile
     // of row 0, alone: the critical workgroup)
     int ti = 0, first = 0;
@@ -1994,7 +1357,6 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
     const int ncols = min(strip, ti + 1 - tj);
     const int i0 = (k + 1 + ti) * 64;
     int j0 = (k + 1 + tj) * 64;
-    double (*F)[LDT] = S[0];
     if constexpr (PIPE && NW == 4) {
         if (k >= 0 && b != 0 && i0 + 64 <= n) {        // interior tile row (its strip's columns lie left of it: inside too)
             const int k0 = k * 64;
@@ -2010,24 +1372,15 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
                 const double* pa = A + (int64_t)(i0 + (tid >> 6)) * lda + k0 + (tid & 63);
 #pragma unroll
                 for (int u = 0; u < 16; ++u) { ra[u] = pa[u * astep]; rw[u] = Wk[((tid >> 6) + 4 * u) * 64 + (tid & 63)]; }
-#if !POTRF_PIPE_LATE0
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) cs[0][t >> 2][j][t & 3] = Cg[t * astep + j * 16];
-                pipe_dma_tile(S[2], Bg, lda);              // B_0 = A_jk of the strip's first column
-#endif
 #pragma unroll
                 for (int u = 0; u < 16; ++u) { S[0][(tid >> 6) + 4 * u][tid & 63] = ra[u]; S[1][(tid >> 6) + 4 * u][tid & 63] = rw[u]; }
             }
             __syncthreads();
-#if POTRF_PIPE_LATE0
             pipe_dma_tile(S[2], Bg, lda);                  // B_0, C_0 requested behind the barrier: in flight under the T product
 #pragma unroll
             for (int t = 0; t < 8; ++t)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) cs[0][t >> 2][j][t & 3] = Cg[t * astep + j * 16];
-#endif
             acc4 acc[2][2];
             TR(1);
             tile_product<true, 4>(S[0], S[1], lane, wr, wc, acc);            // T = A_ik W_k (W symmetric: [n][k] == [k][n])
@@ -2042,8 +1395,6 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
             return;
         }
     }
-    CHOL_STAMP_DECL;
-    CHOL_STAMP(0);
     if (k >= 0) {
         const int k0 = k * 64;
         const double* Wk = Wws + (size_t)k * 4096;
@@ -2074,11 +1425,7 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int dm = i * 16 + 4 * q;
-#ifdef POTRF_ABL_NOC
-                        cv[i][j][q] = 1e-3 * dm;
-#else
                         cv[i][j][q] = A[((m0 + dm < n) ? crow0 + (int64_t)dm * lda : alast) + nn];
-#endif
                     }
                 }
 #pragma unroll
@@ -2089,28 +1436,11 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
             }
         }
         __syncthreads();
-        CHOL_STAMP(1);
         TR(1);
         acc4 acc[2][NJ];
-#if defined(POTRF_ABL_P1) || defined(POTRF_ABL_NOP)     // timing ablation (wrong numbers): every tile but the critical one skips its first product
-        if (b == 0) tile_product<true, NW>(S[0], S[1], lane, wr, wc, acc);
-        else {
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < NJ; ++j) acc[i][j] = acc4{1e-3, 1e-3, 1e-3, 1e-3};
-        }
-#else
-#if POTRF_IL
-        if constexpr (NW == 4) tile_product_il<true, false>(S[0], S[1], lane, wr, wc, acc, [](int) {});
-        else
-#endif
         tile_product<true, NW>(S[0], S[1], lane, wr, wc, acc);          // T = A_ik W_k   (W symmetric: [n][k] == [k][n])
-#endif
-        CHOL_STAMP(4);
         TR(2);
         __syncthreads();
-        CHOL_STAMP(5);
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -2137,39 +1467,9 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
                 S[1][r][c] = (j0 + r < n) ? rb[u] : 0.0;
             }
             __syncthreads();
-            CHOL_STAMP(6);
             if (cc < 5) TR(3 + 3 * cc);
             const bool diag = ti == tj;
             const int jcur = j0;
-#if POTRF_IL && !defined(POTRF_ABL_NOP) && !defined(POTRF_ABL_NOC)
-            if constexpr (NW == 4) {
-                if (b != 0) {
-                    if (cc + 1 < ncols) {            // next block column of the strip: its loads go out BETWEEN the MFMAs of this product
-                        ++tj; j0 += 64;
-                        // two pointers walking down 4 rows per k-step (no per-load 64-bit multiplies in the MFMA stream); in the ragged
-                        // last block row the walk stops at the matrix's last row (those values are never used), and a strip's columns
-                        // lie left of its rows: inside the matrix
-                        const int64_t step4 = (int64_t)4 * lda;
-                        const double* pr = A + (int64_t)min(j0 + (tid >> 6), n - 1) * lda + k * 64 + (tid & 63);
-                        const int cc0 = min(j0 + nl0, n - 1), dc1 = min(j0 + nl0 + 16, n - 1) - cc0;     // (columns clamped like the rows)
-                        const double* pc = A + (int64_t)min(i0 + ml0, n - 1) * lda + cc0;
-                        const int rrow = j0 + (tid >> 6), crow = i0 + ml0;
-                        auto pf = [&](int ks) {
-                            rb[ks] = *pr;
-                            pr += (rrow + 4 * (ks + 1) < n) ? step4 : 0;
-                            const int t = ks & 7;                // rows 4 t of this wave's 32: cv[t >> 2][.][t & 3]
-                            cv[t >> 2][ks >> 3][t & 3] = pc[(ks >> 3) ? dc1 : 0];
-                            if (t == 7) pc = A + (int64_t)min(crow, n - 1) * lda + cc0;
-                            else pc += (crow + 4 * (t + 1) < n) ? step4 : 0;
-                        };
-                        tile_product_il<true, true>(S[0], S[1], lane, wr, wc, acc, pf);
-                    } else {
-                        tile_product_il<true, true>(S[0], S[1], lane, wr, wc, acc, [](int) {});
-                    }
-                    goto product_done;
-                }
-            }
-#endif
             if (cc + 1 < ncols) {                    // next block column of the strip: requested now, consumed after this product
                 ++tj; j0 += 64;
                 const int64_t alast = (int64_t)(n - 1) * lda, astep = (int64_t)NW * lda;
@@ -2189,45 +1489,13 @@ __global__ __launch_bounds__(64 * NW, PIPE ? POTRF_PIPE_MINW : POTRF_MINW) void 
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const int dm = i * 16 + 4 * q;
-#ifdef POTRF_ABL_NOC
-                            cv[i][j][q] = 1e-3 * dm;
-#else
                             cv[i][j][q] = A[((m0 + dm < n) ? crow0 + (int64_t)dm * lda : alast) + nn];
-#endif
                         }
                     }
             }
-#ifdef POTRF_ABL_NOP
-            if (b == 0)
-#endif
-#if POTRF_IL
-            if constexpr (NW == 4) tile_product_il<true, true>(S[0], S[1], lane, wr, wc, acc, [](int) {});
-            else
-#endif
             tile_product<true, NW, true>(S[0], S[1], lane, wr, wc, acc);    // C - T A_jk^T
-#if POTRF_IL && !defined(POTRF_ABL_NOP) && !defined(POTRF_ABL_NOC)
-product_done:
-#endif
-            CHOL_STAMP(7);
-            CHOL_STAMP(8);
             if (cc < 5) TR(4 + 3 * cc);
-            if (b == 0) break;                                          // (the critical tile: a strip of one, kept in LDS below)
             double* const cdst = A + (int64_t)(i0 + ml0) * lda + jcur + nl0;
-#ifndef POTRF_ABL_NOC
-            if (POTRF_IL && NW == 4 && !diag) {      // off-diagonal tile (its columns are inside the matrix): one pointer walking down 4 rows per pair of stores
-                double* pd = cdst;
-                const int64_t step4 = (int64_t)4 * lda;
-                const int crow = i0 + ml0;
-#pragma unroll
-                for (int t = 0; t < 8; ++t) {
-                    if (crow + 4 * t < n) {
-#pragma unroll
-                        for (int j = 0; j < NJ; ++j) pd[j * 16] = acc[t >> 2][j][t & 3];
-                    }
-                    pd += step4;
-                }
-            } else
-#endif
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -2235,57 +1503,16 @@ product_done:
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int ml = ml0 + i * 16 + 4 * q, nl = nl0 + j * 16;
-#ifdef POTRF_ABL_NOC
-                        if (acc[i][j][q] == 123.456)
-#endif
                         if (i0 + ml < n && jcur + nl < n && !(diag && nl > ml))
                             cdst[(int64_t)(i * 16 + 4 * q) * lda + j * 16] = acc[i][j][q];
                     }
             if (cc < 5) TR(5 + 3 * cc);
             if (cc + 1 < ncols) __syncthreads();     // every wave is done reading A_jk out of S[1]
         }
-        if (b != 0) {
-            TR_VAL(20, (ncols << 16) | ti);
-            TR_VAL(22, 1);
-            TR_FLUSH;
-            return;
-        }
-        __syncthreads();                                            // F aliases the T tile: every wave is done reading it
-        CHOL_STAMP(10);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int ml = ml0 + i * 16 + 4 * q, nl = nl0 + j * 16;
-                    const bool in = i0 + ml < n && j0 + nl < n && nl <= ml;
-                    F[ml][nl] = in ? acc[i][j][q] : ((ml == nl) ? 1.0 : 0.0);   // identity padding of a ragged last block
-                }
-        CHOL_STAMP(9);
-    } else {
-        double ra[NU];
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int r = (tid >> 6) + NW * u, c = tid & 63;
-            ra[u] = A[(int64_t)min(r, n - 1) * lda + min(c, n - 1)];
-        }
-#pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int r = (tid >> 6) + NW * u, c = tid & 63;
-            F[r][c] = (r < n && c <= r) ? ra[u] : ((r == c) ? 1.0 : 0.0);
-        }
-        __syncthreads();        // (row-wise fill: the leading 16 x 16 block comes from several waves)
+        TR_VAL(20, (ncols << 16) | ti);
+        TR_VAL(22, 1);
+        TR_FLUSH;
     }
-    // (update path: wave 0 owns rows / columns 0..31 of F, so the block its first chain reads is its own -- no barrier here)
-    CHOL_STAMP(2);
-    // ---- factor the diagonal tile kk = k + 1 ----
-    const int kk = k + 1, r0 = kk * 64, nr = (n - r0 < 64) ? (n - r0) : 64;
-    double (*Y)[LDT] = S[1];
-    factor64_lds(F, Y, Xd, colbuf, rowbuf, tid, info, r0, nr, A + (int64_t)r0 * lda + r0, lda, Xws + (size_t)kk * 4096,
-                 Wws + (size_t)kk * 4096);
-    CHOL_STAMP(3);
-    CHOL_STAMP_FLUSH;
 }
 
 // the last block row of L^-1 (its X is produced by the last step launch): Y_kj = X_k R_kj, j <= k = nblk - 1
@@ -2376,8 +1603,7 @@ int launch_potrf_blocked(hipStream_t st, double* A, int n, int64_t lda, int* inf
             for (int ti = 0; ti < nt; ++ti) nA += (ti + strip) / strip;
         }
         const int nI = (k >= 0 && Yinv) ? nt * ((k + strip) / strip) + (k + 1) : 0;     // R strips + Y tiles
-#if POTRF_PIPE && POTRF_NW == 4
-        if (k >= 0 && k >= pipe_from && k >= POTRF_PIPE_FROM && tiles > POTRF_PIPE_MIN_TILES && lda % 2 == 0 && ((uintptr_t)A % 16) == 0 &&
+        if (k >= 0 && k >= pipe_from && tiles > POTRF_PIPE_MIN_TILES && lda % 2 == 0 && ((uintptr_t)A % 16) == 0 &&
             (!Rw || ((uintptr_t)Rw % 16) == 0)) {      // (the B tiles arrive by 16-byte LDS-DMA pieces: base and row stride 16-byte aligned)
             // one workgroup per CU: the shortest strips that keep the launch within one round of the 256 CUs (the pipelined strip
             // costs ~13k cycles + 4.7k per column; a second round would cost a whole strip)
@@ -2393,7 +1619,6 @@ int launch_potrf_blocked(hipStream_t st, double* A, int n, int64_t lda, int* inf
             hipLaunchKernelGGL((chol_step_kernel<4, true>), dim3(nAp + nIp), dim3(256), 0, st, A, lda, n, k, Xws, Wws, info, Rw, ldr, Yinv,
                                ldy, nAp, YinvT, sp, se);
         } else
-#endif
         hipLaunchKernelGGL((chol_step_kernel<POTRF_NW, false>), dim3(nA + nI), dim3(64 * POTRF_NW), 0, st, A, lda, n, k, Xws, Wws, info, Rw,
                            ldr, Yinv, ldy, nA, YinvT, strip, strip);
         DSVGP_LAUNCH_CHECK();

@@ -73,9 +73,6 @@ struct dsvgp_step_plan {
 };
 
 // workspace layout of one (M, d, p, B); returns the total byte count (0: unsupported shape)
-#ifndef STEP_KZZ_LOWER
-#define STEP_KZZ_LOWER 1            // K_ZZ assembled on and below its 64-wide block diagonal only (what potrf.hip reads)
-#endif
 #ifndef STEP_S_LATE
 #define STEP_S_LATE 2               // [S - I | m'] behind the chain, beside the forward solve: 1 as a one-workgroup-per-CU filler, 2 at full grid
 #define STEP_S_LATE_MP 1024         // ... from this M' up (below: under the chain, as in rounds 2-5)
@@ -136,7 +133,6 @@ static size_t step_layout(int M, int d, int p, int B, dsvgp_step_plan* pl, int w
         pl->wq = ((Mp + 1 + world - 1) / world + 3) / 4 * 4;
         pl->wr = ((Mp + world - 1) / world + 1) / 2 * 2;            // (even: 16-byte aligned column offsets into the fp64 [S - I ; m^T])
         const int wc = ((M + world - 1) / world) * q1;              // widest column block of K_ZZ-bar
-        const int ldQ64 = (Mp + 2) / 2 * 2;
         pl->o_Qfull = c.take((size_t)Mp * world * pl->wq * 4);
         pl->o_qcol64 = c.take((size_t)Mp * pl->wq * 8);
         pl->o_lrow64 = c.take((size_t)pl->wr * Mp * 8);
@@ -293,11 +289,8 @@ extern "C" int dsvgp_elbo_step_status(dsvgp_step_plan* pl, float* hyp4, int* inf
     return 0;
 }
 
-#ifndef STEP_VAR_LATE
-#define STEP_VAR_LATE 2             // 1: (B' >= STEP_Q_CLASSIC_BP) / 2: (always) the variational block behind the dense product, see dsvgp_elbo_step_f32
-#endif
 #ifndef STEP_VAR_LATE_MP
-#define STEP_VAR_LATE_MP 1536       // ... from this M' on (at M' = 600 the Cholesky backward is too short to hide it: 0.549 -> 0.560 ms)
+#define STEP_VAR_LATE_MP 1536       // the variational block runs behind the dense product (see dsvgp_elbo_step_f32) from this M' on (at M' = 600 the Cholesky backward is too short to hide it: 0.549 -> 0.560 ms)
 #endif
 #ifndef STEP_Q_CLASSIC_BP
 #define STEP_Q_CLASSIC_BP 16384     // minibatch columns B' from which the [Q' | a] solve of the one-call step keeps the register-staged lean kernel
@@ -306,9 +299,6 @@ extern "C" int dsvgp_elbo_step_status(dsvgp_step_plan* pl, float* hyp4, int* inf
 #define STEP_PIPE_K1 450    // forward solve under the chain (flag 128): the side stream starts rows [0, r1) after launch k1 = 45 % of the block rows,
 #define STEP_PIPE_K2 750    // rows [r1, r2) after launch k2 = 75 %
 #define STEP_PIPE_PAD 49152 // unused dynamic LDS of the side-stream pieces: one 36 KB + 48 KB workgroup per CU beside one 70 KB chain workgroup
-#endif
-#ifndef STEP_PHI64
-#define STEP_PHI64 0        // 1: tril(L^T L-bar) always with fp64 accumulation (probes; flag 64 of the step does the same at run time)
 #endif
 #define STEP_CALL(expr)                 \
     do {                                \
@@ -342,7 +332,7 @@ static int zz_fwd(dsvgp_ctx* ctx, const dsvgp_elbo_step_io* io, const float* PZ,
     //  the assembly skips the rest -- common.h: fwd_lower_only)
     struct LowerOnly {
         dsvgp_ctx* c; bool prev;
-        LowerOnly(dsvgp_ctx* c_) : c(c_), prev(c_->fwd_lower_only) { c->fwd_lower_only = STEP_KZZ_LOWER != 0; }
+        LowerOnly(dsvgp_ctx* c_) : c(c_), prev(c_->fwd_lower_only) { c->fwd_lower_only = 1; }      // K_ZZ assembled on and below its 64-wide block diagonal only (what potrf.hip reads)
         ~LowerOnly() { c->fwd_lower_only = prev; }
     } lower_only(ctx);
     if (zz_canon2(io, d, p))
@@ -387,36 +377,36 @@ static int step_validate(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const dsvgp_elbo_s
 }
 
 #define STEP_LOCALS \
-    const int M = pl->M, d = pl->d, p = pl->p, B = pl->B, Mp = pl->Mp, Bp = pl->Bp, nb = pl->nb; \
-    char* w = (char*)workspace; \
-    int* info = (int*)(w + pl->o_info); \
-    float* sums = (float*)(w + pl->o_sums); \
-    float* kl_buf = (float*)(w + pl->o_klbuf); \
-    float* scal = (float*)(w + pl->o_scal); \
-    float* hyp = (float*)(w + pl->o_hyp); \
-    float* center = (float*)(w + pl->o_center); \
-    float *PZ = (float*)(w + pl->o_PZ), *sZ = (float*)(w + pl->o_sZ), *vZ = (float*)(w + pl->o_vZ); \
-    float *PX = (float*)(w + pl->o_PX), *sX = (float*)(w + pl->o_sX), *vX = (float*)(w + pl->o_vX); \
-    double* L = (double*)(w + pl->o_L); \
-    void* trsm_ws = w + pl->o_trsm; \
-    void* potrf_ws = w + pl->o_potrf; \
-    float* Kzx = (float*)(w + pl->o_Kzx); \
-    float* A32e = (float*)(w + pl->o_A32e); \
-    float* S32e = (float*)(w + pl->o_S32e); \
-    float* var0 = (float*)(w + pl->o_var0); \
-    void* stats_ws = w + pl->o_stats; \
-    float* Ge = (float*)(w + pl->o_Ge); \
-    double* Qe64 = (double*)(w + pl->o_Qe64); \
-    double* S64e = (double*)(w + pl->o_S64e); \
-    float* Qe32 = (float*)(w + pl->o_Qe32); \
-    float* Kb32 = (float*)(w + pl->o_Kb32); \
-    double* G1 = (double*)(w + pl->o_G1); \
-    double* Yt = (double*)(w + pl->o_Yt); \
-    double* Kbar = (double*)(w + pl->o_Kbar); \
-    void* kbwd_ws = w + pl->o_kbwd; \
-    void* kbwd_ws2 = w + pl->o_kbwd2; \
-    const int ldS = pl->ldS, ldQ32 = pl->ldQ32, ldQ64 = (Mp + 2) / 2 * 2, ldST = (Mp + 1) / 2 * 2; \
-    const double rows = io->global_rows;
+    [[maybe_unused]] const int M = pl->M, d = pl->d, p = pl->p, B = pl->B, Mp = pl->Mp, Bp = pl->Bp, nb = pl->nb; \
+    [[maybe_unused]] char* w = (char*)workspace; \
+    [[maybe_unused]] int* info = (int*)(w + pl->o_info); \
+    [[maybe_unused]] float* sums = (float*)(w + pl->o_sums); \
+    [[maybe_unused]] float* kl_buf = (float*)(w + pl->o_klbuf); \
+    [[maybe_unused]] float* scal = (float*)(w + pl->o_scal); \
+    [[maybe_unused]] float* hyp = (float*)(w + pl->o_hyp); \
+    [[maybe_unused]] float* center = (float*)(w + pl->o_center); \
+    [[maybe_unused]] float *PZ = (float*)(w + pl->o_PZ), *sZ = (float*)(w + pl->o_sZ), *vZ = (float*)(w + pl->o_vZ); \
+    [[maybe_unused]] float *PX = (float*)(w + pl->o_PX), *sX = (float*)(w + pl->o_sX), *vX = (float*)(w + pl->o_vX); \
+    [[maybe_unused]] double* L = (double*)(w + pl->o_L); \
+    [[maybe_unused]] void* trsm_ws = w + pl->o_trsm; \
+    [[maybe_unused]] void* potrf_ws = w + pl->o_potrf; \
+    [[maybe_unused]] float* Kzx = (float*)(w + pl->o_Kzx); \
+    [[maybe_unused]] float* A32e = (float*)(w + pl->o_A32e); \
+    [[maybe_unused]] float* S32e = (float*)(w + pl->o_S32e); \
+    [[maybe_unused]] float* var0 = (float*)(w + pl->o_var0); \
+    [[maybe_unused]] void* stats_ws = w + pl->o_stats; \
+    [[maybe_unused]] float* Ge = (float*)(w + pl->o_Ge); \
+    [[maybe_unused]] double* Qe64 = (double*)(w + pl->o_Qe64); \
+    [[maybe_unused]] double* S64e = (double*)(w + pl->o_S64e); \
+    [[maybe_unused]] float* Qe32 = (float*)(w + pl->o_Qe32); \
+    [[maybe_unused]] float* Kb32 = (float*)(w + pl->o_Kb32); \
+    [[maybe_unused]] double* G1 = (double*)(w + pl->o_G1); \
+    [[maybe_unused]] double* Yt = (double*)(w + pl->o_Yt); \
+    [[maybe_unused]] double* Kbar = (double*)(w + pl->o_Kbar); \
+    [[maybe_unused]] void* kbwd_ws = w + pl->o_kbwd; \
+    [[maybe_unused]] void* kbwd_ws2 = w + pl->o_kbwd2; \
+    [[maybe_unused]] const int ldS = pl->ldS, ldQ32 = pl->ldQ32, ldQ64 = (Mp + 2) / 2 * 2, ldST = (Mp + 1) / 2 * 2; \
+    [[maybe_unused]] const double rows = io->global_rows;
 
 // Everything up to and including the Gram product [tril(G) ; b^T] = tril([A ; mu_bar^T] A^T) of this rank's rows (shared by the
 // one-GPU step and by phase 0 of a data-parallel rank)
@@ -433,7 +423,7 @@ struct ZeroedScope {                          // ctx->prezeroed = true around a 
 static int step_front(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const dsvgp_elbo_step_io* io, void* workspace, int flags, bool preclear = false) {
     STEP_LOCALS
     const bool overlap = (flags & 1) && !ctx->det_slab;           // (deterministic mode: the scratch serves one stream)
-    const bool include_kl = flags & 2, timed = flags & 4;
+    const bool timed = flags & 4;
     pl->timed = timed;
     if (timed) { pl->tm = pl->tm_ring[pl->timed_steps % dsvgp_step_plan::TM_RING]; ++pl->timed_steps; }
 #define STEP_TIME(slot) do { if (timed) STEP_HIP(hipEventRecord(pl->tm[slot], ctx->stream)); } while (0)
@@ -644,7 +634,6 @@ extern "C" int dsvgp_elbo_step_f32(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const ds
         ~PrezeroGuard() { c->prezeroed = prev; }
     } prezero_guard(ctx, pl->arena_bytes <= ((size_t)48 << 20) && !ctx->det_slab);
     STEP_CALL(step_front(ctx, pl, io, workspace, flags, true));
-    float* A32 = A32e;
     STEP_CALL(dsvgp_mirror_lower_f32(ctx, Ge, Mp, Mp));
     // ---- variational block (needs only G): L_S-bar = 2 vbar tril(G L_S) + KL gradient, m-bar = b + KL gradient, trace terms, scalars
     auto variational = [&]() -> int {
@@ -660,7 +649,7 @@ extern "C" int dsvgp_elbo_step_f32(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const ds
                                         1.f, kl_buf, sums, Ge + (size_t)Mp * Mp, io->dm, io->dLS, io->lddls, B, p, scal);
     };
     // ---- [Q' | a / (2 vbar)] = L^-T [S - I | m / (2 vbar)] (fp64), K_ZX-bar = [Q' | a] [A ; mu_bar^T] (fp32, unscaled)
-    const bool var_late = overlap && !(flags & 16) && Mp >= STEP_VAR_LATE_MP && (STEP_VAR_LATE == 2 || (STEP_VAR_LATE == 1 && Bp >= STEP_Q_CLASSIC_BP));
+    const bool var_late = overlap && !(flags & 16) && Mp >= STEP_VAR_LATE_MP;
     auto solve_q = [&]() -> int {
         // (only the fp32 copy of [Q' | a] is read afterwards.  A large solve writes it directly; a small one -- fewer than 1024
         //  output tiles -- splits K onto an fp64 target: its own, Qe64, not the scratch the forward solve has used already)
@@ -707,9 +696,8 @@ extern "C" int dsvgp_elbo_step_f32(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const ds
     // the left one is a widening), and G carries 2e-6 of its largest entry per element -- sqrt(M') times more than what fp32
     // accumulation of this product adds.  So the product itself runs on the fp32 LDS-DMA kernel (gemm32.hip, 2x the fp64 rate;
     // result into the [Q' | a] scratch, free once the dense product has read it) and only its RESULT is widened for the fp64
-    // Cholesky backward.  STEP_PHI64 / flag 64 / shapes gemm32 does not take: the fp64-accumulated form.
+    // Cholesky backward.  Flag 64 / shapes gemm32 does not take: the fp64-accumulated form.
     auto phi_arg = [&](bool qe32_free) -> int {
-#if !STEP_PHI64
         const bool own = (ctx->prezeroed || pl->precleared) && pl->phi32_own;          // (its own, already cleared place: step_layout / preclear)
         if ((qe32_free || own) && !(flags & 64)) {
             GemmArgs g{};
@@ -723,7 +711,6 @@ extern "C" int dsvgp_elbo_step_f32(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const ds
             if (rc > 1) return rc;
             if (rc == 1) return launch_widen_sym_f32_f64(ctx->stream, P32, ldQ32, G1, Mp, Mp);   // widening + Phi(.) + Phi(.)^T in one pass
         }
-#endif
         int rc = dsvgp_gemm(ctx, 1, DSVGP_GEMM_TRANS_A | DSVGP_GEMM_OUT_LOWER | DSVGP_GEMM_B_IS_FLOAT, Mp, Mp, Mp + 1, -1.0, S64e, ldST, Ge, Mp,
                             0.0, nullptr, 0, G1, Mp, nullptr, 0, nullptr);
         if (rc) return rc;
@@ -748,7 +735,7 @@ extern "C" int dsvgp_elbo_step_f32(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const ds
     const bool tail_side = overlap && (flags & 16);
     if (overlap && var_late) {
         // the variational block (G L_S, the trace / KL pass) BEHIND the dense product, beside the Cholesky backward's few-tile fp64 products,
-        // instead of beside the [Q' | a] solve: that solve then runs alone, on the pipelined lean kernel (STEP_VAR_LATE)
+        // instead of beside the [Q' | a] solve: that solve then runs alone, on the pipelined lean kernel
         STEP_CALL(solve_q());
         STEP_CALL(dense());
         STEP_HIP(hipEventRecord(pl->ev_fork2, main));
