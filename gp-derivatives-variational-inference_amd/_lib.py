@@ -111,6 +111,9 @@ SIGNATURES = {
     "dsvgp_kernel_transform_f64": (_i, [_p, _p, _l, _p, _i, _p, _i, _i, _p, _d]),
     "dsvgp_kernel_bwd_transform_f64": (_i, [_p, _p, _l, _p, _l, _p, _i, _p, _i, _i, _p, _p]),
     "dsvgp_kernel_bwd_points_f64": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p]),
+    "dsvgp_kernel_fwd_f64": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _d, _i, _p, _l]),
+    "dsvgp_kernel_bwd_f64_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dsvgp_kernel_bwd_f64": (_i, [_p, _p, _l, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p, _p, _z]),
     "dsvgp_colstats_f64": (_i, [_p, _p, _l, _p, _l, _p, _i, _i, _p, _p]),
     "dsvgp_abar_f64": (_i, [_p, _p, _l, _p, _l, _p, _p, _p, _i, _i, _p, _l, _p, _l]),
     "dsvgp_likelihood_terms_f64": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _i, _d, _p, _p, _p, _p, _p]),

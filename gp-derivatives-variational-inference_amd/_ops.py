@@ -367,8 +367,44 @@ def pack_points_f64(ctx, x, v, p, hyp, center=None):
     return P, sf, vn
 
 
+F64_REGISTER_P = 16     # directions per point that csrc/assemble64.hip's transform kernels hold in registers
+
+
+def kernel_fwd_f64_tiled(ctx, pack1, n1, pack2, n2, d, p, hyp, jitter=0.0, out=None):
+    """kernel_fwd_f64 on the tiled kernels (csrc/assemble64_tiled.hip) at any p <= 95: one launch, T never leaves the chip.
+    jitter != 0 marks the symmetric (K_ZZ) call, as in kernel_fwd_f64"""
+    q = p + 1
+    if out is None:
+        out = torch.empty(n1 * q, n2 * q, dtype=f64, device=pack1[0].device)
+    _req(out, f64, "out", 2)
+    if out.shape != (n1 * q, n2 * q):
+        raise ValueError("out has shape %s, expected %s" % (tuple(out.shape), (n1 * q, n2 * q)))
+    check(lib.dsvgp_kernel_fwd_f64(ctx.h, _ptr(pack1[0]), _ptr(pack1[1]), n1, _ptr(pack2[0]), _ptr(pack2[1]), n2, d, p,
+                                   _ptr(_req(hyp, f64, "hyp", 1)), float(jitter), 1 if jitter != 0.0 else 0, _ptr(out), _ld(out)),
+          "dsvgp_kernel_fwd_f64")
+    return out
+
+
+def kernel_bwd_f64_tiled(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp, workspace=None):
+    """kernel_bwd_f64 on the tiled kernels at any p <= 95 (no [n1 q, n2 q] scratch); -> the workspace used"""
+    _req(G, f64, "G", 2)
+    if G.shape != (n1 * (p + 1), n2 * (p + 1)):
+        raise ValueError("G has shape %s, expected %s" % (tuple(G.shape), (n1 * (p + 1), n2 * (p + 1))))
+    nbytes = int(lib.dsvgp_kernel_bwd_f64_workspace_bytes(n1, n2, d, p))
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=G.device)
+    check(lib.dsvgp_kernel_bwd_f64(ctx.h, _ptr(G), _ld(G), _ptr(pack1[0]), _ptr(pack1[1]), _ptr(pack1[2]), n1, _ptr(pack2[0]),
+                                   _ptr(pack2[1]), n2, d, p, _ptr(_req(hyp, f64, "hyp", 1)), 1 if symmetric else 0,
+                                   _ptr(_req(d_x1, f64, "d_x1", 2)), _ptr(d_v1 if p > 0 else None),
+                                   _ptr(_req(d_hyp, f64, "d_hyp", 1)), _ptr(workspace), workspace.numel()), "dsvgp_kernel_bwd_f64")
+    return workspace
+
+
 def kernel_fwd_f64(ctx, pack1, n1, pack2, n2, d, p, hyp, jitter=0.0, out=None):
-    """outputscale * K(x1, x2; v1, v2) [+ jitter I] in fp64: T = P1 P2^T on the fp64 MFMA GEMM, micro-block transform in place"""
+    """outputscale * K(x1, x2; v1, v2) [+ jitter I] in fp64.  p <= 16: T = P1 P2^T on the fp64 MFMA GEMM, micro-block transform in
+    place; more directions: the tiled kernels"""
+    if p > F64_REGISTER_P:
+        return kernel_fwd_f64_tiled(ctx, pack1, n1, pack2, n2, d, p, hyp, jitter, out)
     q = p + 1
     if out is None:
         out = torch.empty(n1 * q, n2 * q, dtype=f64, device=pack1[0].device)
@@ -382,6 +418,9 @@ def kernel_fwd_f64(ctx, pack1, n1, pack2, n2, d, p, hyp, jitter=0.0, out=None):
 
 def kernel_bwd_f64(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp, scratch=None):
     """backward of kernel_fwd_f64 w.r.t. (x1, v1, lengthscale, outputscale); accumulates into d_x1, d_v1, d_hyp[0..1]"""
+    if p > F64_REGISTER_P:
+        kernel_bwd_f64_tiled(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp)
+        return
     q = p + 1
     _req(G, f64, "G", 2)
     K4 = (d + 3) // 4 * 4

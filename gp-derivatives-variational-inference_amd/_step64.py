@@ -241,9 +241,9 @@ class ElboEngine64(ElboEngine):
         _ops.transpose_f64(ctx, Rbar, Kb)
         dZ, dV = grads["inducing_points"], grads["inducing_directions"]
         d_hyp = torch.zeros(4, dtype=f64, device=dev)
-        scratch = self._get("T_zx", (Mp, Bp), f64)
+        scratch = self._get("T_zx", (Mp, Bp), f64) if p <= _ops.F64_REGISTER_P else None      # (the tiled kernels need no T buffer)
         _ops.kernel_bwd_f64(ctx, Kb, packZ, M, packX, B, d, p, hyp, False, dZ, dV, d_hyp, scratch)
-        scratch = self._get("T_zz", (Mp, Mp), f64)
+        scratch = self._get("T_zz", (Mp, Mp), f64) if p <= _ops.F64_REGISTER_P else None      # (the tiled kernels need no T buffer)
         _ops.kernel_bwd_f64(ctx, Kzzbar, packZ, M, packZ, M, d, p, hyp, True, dZ, dV, d_hyp, scratch)
         # likelihood / prior-diagonal parts (scal) + kernel parts (d_hyp) through the softplus constraints
         d_raw = self._raw_grads64(params, scal)
@@ -497,10 +497,10 @@ class ElboEngine64(ElboEngine):
             full.zero_()
             full[:, ::p + 1] = Kb
             Kb = full
-        scratch = self._get("T_zx", (Mp, B * (p + 1)), f64)
+        scratch = self._get("T_zx", (Mp, B * (p + 1)), f64) if p <= _ops.F64_REGISTER_P else None      # (the tiled kernels need no T buffer)
         _ops.kernel_bwd_f64(ctx, Kb, packZ, M, packX, B, d, p, hyp, False, dZ, dV, d_hyp, scratch)
         Kzzbar = self._chol_backward(ctx, L, Lbar, ws, Mp, phi_arg=phi_arg)
-        scratch = self._get("T_zz", (Mp, Mp), f64)
+        scratch = self._get("T_zz", (Mp, Mp), f64) if p <= _ops.F64_REGISTER_P else None      # (the tiled kernels need no T buffer)
         _ops.kernel_bwd_f64(ctx, Kzzbar, packZ, M, packZ, M, d, p, hyp, True, dZ, dV, d_hyp, scratch)
         # softplus chain rule of the kernel hyper-parameters; d_raw already holds the likelihood / prior-diagonal parts
         sig = [torch.sigmoid(params[k].reshape(())) for k in ("raw_lengthscale", "raw_outputscale")]

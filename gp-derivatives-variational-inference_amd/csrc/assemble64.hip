@@ -13,11 +13,13 @@
 //   points    dP1 = Tbar [P2 | indicator] -> d_x1, d_v1 through x/ell and the direction normalisation (the indicator
 //             column collects the row sums that carry the self-term gradients nrm-bar, alpha-bar).
 // Not a throughput path (fp64 mode is the reference's experiment setting, not the benchmark): clarity over tiling.
+// The two transform kernels take p <= 16; assemble64_tiled.hip holds the tiled, fused kernels for any p <= 95 on the same packs.
 #include "common.h"
 
 namespace {
 
 constexpr int PMAX = 16;                      // directions per point supported by the per-thread register arrays
+constexpr int PMAX_TILED = 95;                // ... by the kernels without such arrays (pack, points; assemble64_tiled.hip)
 
 __global__ void pack64_kernel(const double* __restrict__ x, const double* __restrict__ v, int n, int d, int p,
                               const double* __restrict__ hyp, const double* __restrict__ center, double* __restrict__ P,
@@ -371,7 +373,7 @@ extern "C" int dsvgp_likelihood_terms_f64(dsvgp_ctx* ctx, const double* mu0, con
 
 extern "C" int dsvgp_pack_points_f64(dsvgp_ctx* ctx, const double* x, const double* v, int n, int d, int p, const double* hyp,
                                      const double* center, double* P, double* self, double* vnorm) {
-    if (!ctx || !x || !hyp || !P || !self || n < 0 || d <= 0 || p < 0 || p > 16 || (p > 0 && (!v || !vnorm))) return DSVGP_EINVAL;
+    if (!ctx || !x || !hyp || !P || !self || n < 0 || d <= 0 || p < 0 || p > PMAX_TILED || (p > 0 && (!v || !vnorm))) return DSVGP_EINVAL;
     if (n == 0) return 0;
     const int K4 = (d + 3) & ~3, DP = K4 + 4;
     const int rows = n * (p + 1);
@@ -402,7 +404,7 @@ extern "C" int dsvgp_kernel_bwd_transform_f64(dsvgp_ctx* ctx, const double* G, i
 }
 extern "C" int dsvgp_kernel_bwd_points_f64(dsvgp_ctx* ctx, const double* dP, const double* P1, const double* vnorm1, int n1,
                                            int d, int p, const double* hyp, int symmetric, double* d_x1, double* d_v1) {
-    if (!ctx || !dP || !P1 || !hyp || !d_x1 || n1 < 0 || d <= 0 || p < 0 || p > 16 || (p > 0 && (!vnorm1 || !d_v1))) return DSVGP_EINVAL;
+    if (!ctx || !dP || !P1 || !hyp || !d_x1 || n1 < 0 || d <= 0 || p < 0 || p > PMAX_TILED || (p > 0 && (!vnorm1 || !d_v1))) return DSVGP_EINVAL;
     if (n1 == 0) return 0;
     const int K4 = (d + 3) & ~3, DP = K4 + 4;
     hipLaunchKernelGGL(bwd_points64_kernel, dim3(n1), dim3(64), sizeof(double) * (p + 2), ctx->stream, dP, P1, vnorm1, n1, d, p,

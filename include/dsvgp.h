@@ -158,7 +158,8 @@ int dsvgp_kernel_bwd_canon2(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is
  *   dsvgp_kernel_transform_f64      T[n1(p+1), n2(p+1)] -> outputscale * K in place (+ jitter on the global diagonal)
  *   dsvgp_kernel_bwd_transform_f64  (G = dLoss/dK, T) -> Tbar in place of T; d_hyp[0] += d lengthscale, d_hyp[1] += d outputscale
  *   dsvgp_kernel_bwd_points_f64     dP1[n1(p+1), DP] = Tbar [P2 | indicator] -> d_x1 +=, d_v1 += (x2 when symmetric)
- * hyp: device double[3+] = {lengthscale, outputscale, noise}.  p <= 16.                                              */
+ * hyp: device double[3+] = {lengthscale, outputscale, noise}.  The two transform entries keep the directions of a micro-block in
+ * per-thread registers and take p <= 16; dsvgp_pack_points_f64 and dsvgp_kernel_bwd_points_f64 take p <= 95.               */
 int dsvgp_pack_points_f64(dsvgp_ctx* ctx, const double* x, const double* v, int n, int d, int p, const double* hyp,
                           const double* center, double* P, double* self, double* vnorm);
 int dsvgp_kernel_transform_f64(dsvgp_ctx* ctx, double* T, int64_t ld, const double* self1, int n1, const double* self2,
@@ -186,6 +187,22 @@ int dsvgp_elbo_fast_tail_f64(dsvgp_ctx* ctx, const double* mu0, const double* y,
                              const double* hyp, const double* tvar, double rows, double* mu, double* mu_bar, double* scal);
 int dsvgp_kernel_bwd_points_f64(dsvgp_ctx* ctx, const double* dP, const double* P1, const double* vnorm1, int n1, int d,
                                 int p, const double* hyp, int symmetric, double* d_x1, double* d_v1);
+/* Tiled fp64 assembly (csrc/assemble64_tiled.hip): the same kernel matrix and the same backward from the packs of
+ * dsvgp_pack_points_f64, for ANY 0 <= p <= 95 and any d >= 1 (workgroup LDS independent of d), with T = P1 P2^T computed on the fp64
+ * MFMA inside the assembly kernels -- no [n1 (p+1), n2 (p+1)] intermediate.  DSVGP_EINVAL for p > 95, ld / ldg < n2 (p+1), bases that
+ * are not 8-byte aligned, symmetric != 0 with n1 != n2.
+ *   dsvgp_kernel_fwd_f64   out[n1(p+1), n2(p+1)] (leading dimension ld) = outputscale * K; symmetric != 0 (x1 == x2, v1 == v2: K_ZZ)
+ *                          adds jitter on the global diagonal, symmetric == 0 ignores jitter.
+ *   dsvgp_kernel_bwd_f64   G = dLoss/dOut -> d_x1[n1,d] +=, d_v1[n1*p,d] +=, d_hyp[0] += d lengthscale, d_hyp[1] += d outputscale, as
+ *                          the sequence gemm, dsvgp_kernel_bwd_transform_f64, gemm, dsvgp_kernel_bwd_points_f64 (symmetric != 0: point
+ *                          and direction gradients doubled).  workspace: dsvgp_kernel_bwd_f64_workspace_bytes(n1, n2, d, p) bytes of
+ *                          device memory (0 = geometry not taken), cleared here; sums meet in fp64 atomics (run-order rounding).      */
+int dsvgp_kernel_fwd_f64(dsvgp_ctx* ctx, const double* P1, const double* self1, int n1, const double* P2, const double* self2,
+                         int n2, int d, int p, const double* hyp, double jitter, int symmetric, double* out, int64_t ld);
+size_t dsvgp_kernel_bwd_f64_workspace_bytes(int n1, int n2, int d, int p);
+int dsvgp_kernel_bwd_f64(dsvgp_ctx* ctx, const double* G, int64_t ldg, const double* P1, const double* self1, const double* vnorm1,
+                         int n1, const double* P2, const double* self2, int n2, int d, int p, const double* hyp, int symmetric,
+                         double* d_x1, double* d_v1, double* d_hyp, void* workspace, size_t workspace_bytes);
 
 /* ---- Cholesky: psd_safe_cholesky(K_ZZ.double()) (DirectionalGradVariationalStrategy.py:72-75)
  * In-place lower Cholesky of the row-major fp64 matrix A[n,n] (rocSOLVER dpotrf); only the lower
