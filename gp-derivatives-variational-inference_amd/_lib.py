@@ -39,6 +39,22 @@ class ElboStepIO(C.Structure):
                 ("split_ws", _p), ("split_ws_bytes", _z), ("dir_idx", _p), ("dir_idx_base", _i), ("v_one_hot", _i)]
 
 
+class ElboStepIO64(C.Structure):
+    """``dsvgp_elbo_step_io_f64`` of include/dsvgp.h (device pointers of one float64 ELBO step); ``struct_size`` is set here, every
+    other field starts from zero (the versioning contract of the header)"""
+    _fields_ = [("struct_size", _z), ("Z", _p), ("V", _p), ("m", _p), ("LS", _p), ("ldls", _l),
+                ("constant", _p), ("raw_lengthscale", _p), ("raw_outputscale", _p), ("raw_noise", _p),
+                ("x", _p), ("y", _p), ("D", _p),
+                ("flat", _p), ("flat_doubles", _z),
+                ("dZ", _p), ("dV", _p), ("dm", _p), ("dLS", _p), ("lddls", _l),
+                ("d_hyp", _p), ("d_constant", _p), ("d_raw_lengthscale", _p), ("d_raw_outputscale", _p), ("d_raw_noise", _p),
+                ("loss", _p), ("mu", _p), ("num_data", _d), ("global_rows", _d), ("kzz_jitter", _d)]
+
+    def __init__(self):
+        super().__init__()
+        self.struct_size = C.sizeof(ElboStepIO64)
+
+
 class ElboStepDP(C.Structure):
     """``dsvgp_elbo_step_dp`` of include/dsvgp.h (rank, world and the collective operands of one data-parallel rank)"""
     _fields_ = [("rank", _i), ("world", _i), ("wire", _p), ("wire_floats", _z), ("q_local", _p), ("q_all", _p),
@@ -68,6 +84,15 @@ SIGNATURES = {
     "dsvgp_elbo_step_timings5": (_i, [_p, _i, _p]),
     "dsvgp_elbo_step_timed_count": (C.c_long, [_p]),
     "dsvgp_elbo_step_locate": (_i, [_p, _i, _p, _p, _p, _p]),
+    "dsvgp_elbo_step_f64_supported": (_i, [_i, _i, _i, _i]),
+    "dsvgp_elbo_step_f64_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dsvgp_elbo_step_f64_plan_create": (_i, [_p, _i, _i, _i, _i, C.POINTER(_p)]),
+    "dsvgp_elbo_step_f64_plan_destroy": (_i, [_p]),
+    "dsvgp_elbo_step_f64": (_i, [_p, _p, _p, _p, _z, _i]),
+    "dsvgp_elbo_step_f64_status": (_i, [_p, _p, _p]),
+    "dsvgp_elbo_step_f64_timings": (_i, [_p, _i, _p]),
+    "dsvgp_elbo_step_f64_timed_count": (C.c_long, [_p]),
+    "dsvgp_gather_batch_f64": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
     "dsvgp_version": (C.c_char_p, []),
     "dsvgp_hyp_forward": (_i, [_p, _p, _p, _p, _p]),
     "dsvgp_hyp_backward": (_i, [_p, _p, _p, _p, _p, _p, _p, _p]),

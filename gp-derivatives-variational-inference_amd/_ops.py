@@ -144,6 +144,46 @@ class StepPlan:
         return [float(v) for v in self._ms]
 
 
+class StepPlan64:
+    """``dsvgp_step_plan_f64`` of one (M, d, p, B): host-side object of the float64 model mode's one-call ELBO step (csrc/step64.hip)"""
+
+    def __init__(self, ctx, M, d, p, B):
+        h = C.c_void_p()
+        check(lib.dsvgp_elbo_step_f64_plan_create(ctx.h, int(M), int(d), int(p), int(B), C.byref(h)), "dsvgp_elbo_step_f64_plan_create")
+        self.h = h
+        self.bytes = int(lib.dsvgp_elbo_step_f64_workspace_bytes(int(M), int(d), int(p), int(B)))
+        self.io = _lib.ElboStepIO64()
+        self._hyp = (C.c_double * 4)()
+        self._info = C.c_int(0)
+        self._ms = (C.c_float * 5)()
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            lib.dsvgp_elbo_step_f64_plan_destroy(h)
+
+    def run(self, ctx, workspace, flags):
+        check(lib.dsvgp_elbo_step_f64(ctx.h, self.h, C.byref(self.io), _ptr(workspace), workspace.numel(), int(flags)),
+              "dsvgp_elbo_step_f64")
+
+    def status(self):
+        """(potrf status word, [lengthscale, outputscale, noise, 0]) of the step queued last; waits for its factorisation only"""
+        check(lib.dsvgp_elbo_step_f64_status(self.h, self._hyp, C.byref(self._info)), "dsvgp_elbo_step_f64_status")
+        return int(self._info.value), [float(v) for v in self._hyp]
+
+    def timed_count(self):
+        return int(lib.dsvgp_elbo_step_f64_timed_count(self.h))
+
+    def timings(self, back=0):
+        """[solve_fwd, assemble_fwd, assemble_bwd, gram, dense] HIP-event durations (ms) of the timed step ``back`` steps before the last"""
+        check(lib.dsvgp_elbo_step_f64_timings(self.h, int(back), self._ms), "dsvgp_elbo_step_f64_timings")
+        return [float(v) for v in self._ms]
+
+
+def step64_supported(M, d, p, B):
+    return bool(lib.dsvgp_elbo_step_f64_supported(int(M), int(d), int(p), int(B)))
+
+
 def step_supported(M, d, p, B, world=1, per_output=False):
     if per_output:
         return world == 1 and int(lib.dsvgp_elbo_step_po_workspace_bytes(int(M), int(d), int(p), int(B))) > 0
@@ -843,6 +883,22 @@ def gather_batch(ctx, X, Y, idx, cols, p, xb, yb, E=None, Db=None):
                                  _ptr(_req(idx, torch.int64, "idx", 1)), idx.shape[0], X.shape[1], Y.shape[1],
                                  _ptr(_req(cols, torch.int32, "cols", 1)), p, _ptr(xb), _ptr(yb), _ptr(E), _ptr(Db)),
           "dsvgp_gather_batch")
+
+
+def gather_batch_f64(ctx, X, Y, idx, cols, p, xb, yb, E=None, Db=None):
+    """``gather_batch`` of the float64 model mode: minibatch rows of X, the selected (interleaved) columns of Y and, with the [d, d]
+    direction table E, the tiled one-hot directions Db[nb * p, d] in one launch"""
+    if E is not None and (E.shape != (X.shape[1], X.shape[1]) or not E.is_contiguous() or E.dtype != f64 or Db is None or
+                          Db.shape != (idx.shape[0] * p, X.shape[1]) or not Db.is_contiguous() or Db.dtype != f64):
+        raise ValueError("gather_batch_f64: E must be [d, d] and Db [nb * p, d] float64 contiguous")
+    if not (X.is_contiguous() and Y.is_contiguous()):
+        raise ValueError("gather_batch_f64: X and Y must be contiguous")
+    if xb.shape != (idx.shape[0], X.shape[1]) or yb.numel() != idx.shape[0] * (p + 1) or cols.numel() != p + 1:
+        raise ValueError("gather_batch_f64: output shapes do not match the index lists")
+    check(lib.dsvgp_gather_batch_f64(ctx.h, _ptr(_req(X, f64, "X", 2)), _ptr(_req(Y, f64, "Y", 2)),
+                                     _ptr(_req(idx, torch.int64, "idx", 1)), idx.shape[0], X.shape[1], Y.shape[1],
+                                     _ptr(_req(cols, torch.int32, "cols", 1)), p, _ptr(_req(xb, f64, "xb", 2)), _ptr(_req(yb, f64, "yb", 1)),
+                                     _ptr(E), _ptr(Db)), "dsvgp_gather_batch_f64")
 
 
 ADAM_MAX_TENSORS = 16

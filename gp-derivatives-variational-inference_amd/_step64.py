@@ -13,6 +13,10 @@ and the ELBO are then all fp64.  ``ElboEngine64`` is that mode of ``directional_
     expressions in closed form.  Nothing goes through torch.autograd (the reference differentiates the same expressions by
     autograd, directional_vi.py:245-249).
 
+The Gram-formulation ELBO step of one rank is ONE C call (``dsvgp_elbo_step_f64``, csrc/step64.hip; ``_c_step64``): forward, backward and every
+gradient queued without a host read, the elementwise passes between the products as HIP kernels of their own.  On by default, ``DSVGP_C_STEP=0``
+switches it off; what it does not cover stays on the Python-orchestrated paths below.
+
 Two formulations, as in the fp32 engine: the general (variance-carrying) one covers ELBO and PLL; in ELBO mode, when the caller
 does not read the per-output variances, the Gram-matrix formulation (``_elbo_fast64``) needs three [M', B'] products instead
 of six.  q(u) may be a NaturalVariationalDistribution (``train_gp(use_ngd=True)``: natural parameters in, expectation-parameter gradients out).
@@ -45,6 +49,7 @@ class ElboEngine64(ElboEngine):
         super().__init__(device, trsm_nb)
         self.elbo_fast = True
         self.fast_min_work = 4_000_000      # M' B' below which the per-output path is used anyway (C2: host-bound, 2.42 vs 2.58 ms)
+        self.c_step_status = None           # potrf status word of the last one-call step (None: the step took another path)
 
     # ---- forward pieces -----------------------------------------------------------------------
     def _check(self, params, x, D):
@@ -415,9 +420,125 @@ class ElboEngine64(ElboEngine):
             out = (loss, {_NGD_RENAME.get(k, k): v for k, v in grads.items()}, mu, varn)
         return out
 
+    # ---- the Gram-formulation step as ONE C call (dsvgp_elbo_step_f64, csrc/step64.hip) ----
+    def _c_step64_eligible(self, params, x, D, mll_type, fast):
+        """ELBO with ``fast`` None / True on one rank, Cholesky whitening, every data point with its derivatives, explicit-inverse
+        regime; an explicit ``fast=False`` (per-output variances), PLL, shared directions, derivative-free data, CIQ, a collective
+        with world > 1 and graph capture keep their paths.  The ``fast_min_work`` rule does not apply: it exists because the
+        Python-orchestrated Gram path is host-bound at small M' B'."""
+        if not (self.c_step and mll_type == "ELBO" and (fast is True or (fast is None and self.elbo_fast)) and not self.capture_mode
+                and self.whitening == "cholesky" and self.data_outputs == "all" and not self.shared_directions and not self._no_middle
+                and self.potrf_algo == 1 and self.fused_inverse and self._trsm_nb is None):
+            return False
+        coll = self.collective
+        if coll is not None and coll.world > 1:
+            return False
+        Z, V = params["inducing_points"], params["inducing_directions"]
+        M, d = Z.shape
+        p = V.shape[0] // M if M else 0
+        if p > 0 and (D is None or D.shape != (x.shape[0] * p, d)):
+            return False
+        return M > 0 and x.shape[0] > 0 and _ops.step64_supported(M, d, p, x.shape[0])
+
+    def _alloc_grads64(self, params):
+        """all gradients, the loss and d_hyp[4] in one flat float64 buffer that the call clears (every slot 64-byte aligned)"""
+        pad = lambda nk: (nk + 7) // 8 * 8
+        total = sum(pad(params[k].numel()) for k in PARAM_NAMES)
+        flat = torch.empty(total + 8, dtype=f64, device=self.device)
+        views, off = {}, 0
+        for k in PARAM_NAMES:
+            nk = params[k].numel()
+            views[k] = flat[off:off + nk].view(params[k].shape)
+            off += pad(nk)
+        return flat, views, flat[off:off + 1], flat[off + 1:off + 5]
+
+    def _c_step64(self, ctx, params, x, y, D, num_data, rows, include_kl):
+        """queues the whole step with one ctypes call and reads the factorisation's status word (a wait for the factorisation, not
+        for the step); returns None when the factorisation failed: the caller repeats the step through the jitter ladder"""
+        Z, V = params["inducing_points"], params["inducing_directions"]
+        M, d = Z.shape
+        p = V.shape[0] // M
+        B = x.shape[0]
+        Mp, Bp = M * (p + 1), B * (p + 1)
+        self._problem_size(Mp)
+        pkey = ("f64", M, d, p, B)
+        plan = self._plans.get(pkey)
+        if plan is None:
+            plan = self._plans[pkey] = _ops.StepPlan64(ctx, M, d, p, B)
+        ws = self._bytes("cstep64_ws_%d_%d_%d_%d" % (M, d, p, B), plan.bytes)       # one workspace per plan (a ragged tail batch has its own)
+        m, LS = params["variational_mean"], params["chol_variational_covar"]
+        for name, t in (("inducing_points", Z), ("inducing_directions", V), ("x", x), ("y", y), ("D", D), ("variational_mean", m),
+                        ("chol_variational_covar", LS)):
+            if t is not None and t.numel() and (t.dtype != f64 or not t.is_cuda or (t.dim() == 2 and t.stride(1) != 1)
+                                                or (t.dim() != 2 and not t.is_contiguous())):
+                raise _lib.DsvgpError("%s must be a float64 GPU tensor with unit inner stride" % name)
+        if not (Z.is_contiguous() and x.is_contiguous() and (p == 0 or (V.is_contiguous() and D.is_contiguous()))):
+            raise ValueError("points and directions must be contiguous")
+        if LS.shape != (Mp, Mp) or m.shape != (Mp,):
+            raise ValueError("q(u) must have M(p+1) = %d values" % Mp)
+        for name in ("constant", "raw_lengthscale", "raw_outputscale", "raw_noise"):      # (handed over as bare device pointers)
+            t = params[name]
+            if t.numel() != 1 or not t.is_contiguous():
+                raise _lib.DsvgpError("%s must be a contiguous float64 GPU tensor with one element" % name)
+        flat, grads, loss_out, d_hyp = self._alloc_grads64(params)
+        mu = torch.empty(Bp, dtype=f64, device=self.device)
+        dLS = grads["chol_variational_covar"]
+        P = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        io = plan.io
+        io.Z, io.V, io.m, io.LS, io.ldls = P(Z), P(V), P(m), P(LS), _ops._ld(LS)
+        io.constant, io.raw_lengthscale = P(params["constant"]), P(params["raw_lengthscale"])
+        io.raw_outputscale, io.raw_noise = P(params["raw_outputscale"]), P(params["raw_noise"])
+        io.x, io.y, io.D = P(x), P(y), P(D) if p > 0 else None
+        io.flat, io.flat_doubles = flat.data_ptr(), flat.numel()
+        io.dZ, io.dV, io.dm = P(grads["inducing_points"]), P(grads["inducing_directions"]), P(grads["variational_mean"])
+        io.dLS, io.lddls = P(dLS), _ops._ld(dLS)
+        io.d_hyp, io.d_constant = P(d_hyp), P(grads["constant"])
+        io.d_raw_lengthscale, io.d_raw_outputscale = P(grads["raw_lengthscale"]), P(grads["raw_outputscale"])
+        io.d_raw_noise, io.loss, io.mu = P(grads["raw_noise"]), P(loss_out), P(mu)
+        io.num_data, io.global_rows, io.kzz_jitter = float(num_data), float(rows), float(self.kzz_jitter)
+        overlap = self.overlap if self.overlap is not None else Mp >= 512
+        timed = self.record_events and self._rec_count % max(1, self.record_every) == 0
+        if self.record_events:
+            self._rec_count += 1
+        flags = (1 if overlap else 0) | (2 if include_kl else 0) | (4 if timed else 0)
+        tr = self.host_trace                  # (tools/host_trace.py: where the host's time goes; None in production)
+        if tr is not None:
+            import time as _t
+            t0 = _t.perf_counter()
+        plan.run(ctx, ws, flags)
+        if tr is not None:
+            t1 = _t.perf_counter()
+        info, hyp = plan.status()             # waits for the factorisation only; the rest of the step stays queued
+        if tr is not None:
+            tr.append((t0, t1, _t.perf_counter()))
+        self._hyp_host = hyp[:3]
+        self.c_step_status = info
+        if info != 0:
+            return None
+        if timed:
+            self.c_step_timed.append((plan, plan.timed_count() - 1))
+        self.c_step_used = True
+        return loss_out[0], grads, mu, torch.empty(0, dtype=f64, device=self.device)
+
     def _loss_and_grads64(self, ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
         """first attempt without a host read of the potrf status inside the step; the status is read once at the end and a failed
         factorisation (rare: psd_safe_cholesky's jitter ladder) repeats the step synchronously"""
+        self.c_step_used = False
+        self.c_step_status = None
+        self._check(params, x, D)
+        if mll_type not in ("ELBO", "PLL"):
+            raise ValueError("mll_type must be 'ELBO' or 'PLL'")
+        if self._c_step64_eligible(params, x, D, mll_type, fast):
+            pz = params["inducing_directions"].shape[0] // params["inducing_points"].shape[0]
+            Bq = x.shape[0] * (pz + 1)
+            if y.shape != (Bq,) or y.dtype != f64:
+                raise ValueError("y must be the interleaved float64 target vector of length B*(p+1)=%d" % Bq)
+            self._eval_cache = None
+            out = self._c_step64(ctx, params, x, y.contiguous(), D, num_data, float(Bq if global_rows is None else global_rows),
+                                 include_kl)
+            if out is not None:
+                return out
+            return self._loss_and_grads64_once(ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast, True)
         out = self._loss_and_grads64_once(ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast, False)
         if int(self._info64.item()) != 0:
             out = self._loss_and_grads64_once(ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast, True)

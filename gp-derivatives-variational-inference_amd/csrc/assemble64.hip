@@ -15,6 +15,7 @@
 // Not a throughput path (fp64 mode is the reference's experiment setting, not the benchmark): clarity over tiling.
 // The two transform kernels take p <= 16; assemble64_tiled.hip holds the tiled, fused kernels for any p <= 95 on the same packs.
 #include "common.h"
+#include "pack64.h"
 
 namespace {
 
@@ -25,36 +26,8 @@ __global__ void pack64_kernel(const double* __restrict__ x, const double* __rest
                               const double* __restrict__ hyp, const double* __restrict__ center, double* __restrict__ P,
                               double* __restrict__ self, double* __restrict__ vnorm, int K4, int DP) {
     const int row = blockIdx.x * blockDim.x + threadIdx.x;
-    const int q = p + 1;
-    if (row >= n * q) return;
-    const int i = row / q, a = row - i * q;
-    const double ell = hyp[0];
-    double* Pr = P + (int64_t)row * DP;
-    const double* xi = x + (int64_t)i * d;
-    for (int k = 0; k < DP; ++k) Pr[k] = 0.0;
-    if (a == 0) {
-        double acc = 0.0;
-        for (int k = 0; k < d; ++k) {
-            const double xt = (xi[k] - (center ? center[k] : 0.0)) / ell;    // x.div(lengthscale), :67-68
-            Pr[k] = xt;
-            acc = fma(xt, xt, acc);
-        }
-        Pr[K4] = 1.0;                                   // indicator column (row sums in the backward)
-        self[row] = acc;
-    } else {
-        const double* vi = v + ((int64_t)i * p + (a - 1)) * d;
-        double ss = 0.0;
-        for (int k = 0; k < d; ++k) ss = fma(vi[k], vi[k], ss);
-        const double nrm = sqrt(ss);                    // :57-58
-        double acc = 0.0;
-        for (int k = 0; k < d; ++k) {
-            const double vh = vi[k] / nrm;
-            Pr[k] = vh;
-            acc = fma(vh, (xi[k] - (center ? center[k] : 0.0)) / ell, acc);
-        }
-        self[row] = acc;
-        vnorm[(int64_t)i * p + (a - 1)] = nrm;
-    }
+    if (row >= n * (p + 1)) return;
+    pack64_row(x, v, row, d, p, hyp[0], center, P, self, vnorm, K4, DP);
 }
 
 // T -> K in place; one thread per point pair (consecutive threads: consecutive pairs of one point row)

@@ -4,7 +4,7 @@
 
 What is different underneath (MI355X-first):
   * the dataset is made resident in HBM once; each step's minibatch is gathered on the GPU
-    (``dsvgp_gather_batch``) from a per-epoch ``randperm`` instead of ``DataLoader``'s per-index collate
+    (``dsvgp_gather_batch`` / ``dsvgp_gather_batch_f64``) from a per-epoch ``randperm`` instead of ``DataLoader``'s per-index collate
     plus a host->device copy per step (directional_vi.py:133,229-232);
   * ``likelihood(model(x))`` + ``mll`` + ``backward`` run as one fused HIP forward/backward (``_step.py``);
   * both Adam optimizers are the fused HIP Adam (``optim.FusedAdam``), stepped with the same
@@ -299,9 +299,15 @@ class TrainLoop:
         nb = idx.shape[0]
         self.ctx.bind()                         # the library launches on torch's CURRENT stream (the capture stream under a graph)
         Db = None
-        if self.X.dtype == torch.float64:       # fp64 model mode: plain index_select (O(B d) copies)
-            x_batch = self.X.index_select(0, idx)
-            y_batch = self.Y.index_select(0, idx).index_select(1, cols.long()).reshape(-1)
+        if self.X.dtype == torch.float64:       # fp64 model mode: dsvgp_gather_batch_f64 (x, interleaved y and the tiled directions, one launch)
+            x_batch = torch.empty(nb, dim, dtype=torch.float64, device=dev)
+            y_batch = torch.empty(nb * (py + 1), dtype=torch.float64, device=dev)
+            fused_dirs = (not self.dfree and not self.full_gradient and py == p and p > 0
+                          and self.E_canonical.shape == (dim, dim) and self.E_canonical.dtype == torch.float64
+                          and self.E_canonical.is_contiguous())
+            Db = torch.empty(nb * p, dim, dtype=torch.float64, device=dev) if fused_dirs else None
+            _ops.gather_batch_f64(self.ctx, self.X, self.Y, idx, cols, py, x_batch, y_batch,
+                                  self.E_canonical if fused_dirs else None, Db)
         else:
             x_batch = torch.empty(nb, dim, dtype=torch.float32, device=dev)
             y_batch = torch.empty(nb * (py + 1), dtype=torch.float32, device=dev)

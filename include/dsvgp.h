@@ -579,6 +579,60 @@ int dsvgp_elbo_step_timings(dsvgp_step_plan* plan, int steps_back, float* ms3); 
 int dsvgp_elbo_step_timings5(dsvgp_step_plan* plan, int steps_back, float* ms5);
 long dsvgp_elbo_step_timed_count(const dsvgp_step_plan* plan);   /* steps queued with flag 4 so far (index of the last: count - 1) */
 
+/* ---- the whole ELBO step of the FLOAT64 model mode from one host call (csrc/step64.hip) -- the reference's experiment scripts run
+ * under torch.set_default_dtype(torch.float64) (experiments/synthetic/exp_script.py:56): parameters, minibatch, kernel matrices, the
+ * whitening solve and the ELBO all in double.  dsvgp_elbo_step_f64 queues forward + backward of one minibatch ELBO evaluation
+ * (directionalvi/directional_vi.py:245-249 with DirectionalGradVariationalStrategy.forward, DGVS.py:89-208) without a host read, a
+ * host synchronisation or a device allocation: Gram formulation of the ELBO, Cholesky variational distribution, Cholesky whitening,
+ * every data point with its p directional derivatives, one rank, explicit-inverse regime M(p+1) <= 8192, any d >= 1, 0 <= p <= 95
+ * (p <= 16: register assembly of csrc/assemble64.hip, its T scratch in the workspace; more directions: csrc/assemble64_tiled.hip).
+ *   io         device pointers, all double.  THE CALLER ZEROES THE STRUCT (memset / = {0}) and sets struct_size = sizeof(struct):
+ *              fields appended in later versions are read only when struct_size covers them, and an older caller's zeroed struct
+ *              keeps its meaning.  io->flat[0 .. flat_doubles) is cleared by the call and must contain every gradient slot, the
+ *              loss and d_hyp[4].  There are no dir_idx fields: the fp64 assembly has no canonical-direction kernels.
+ *   plan       host object of one (M, d, p, B): workspace layout, second stream, events, pinned status word
+ *   workspace  caller-owned device memory of dsvgp_elbo_step_f64_workspace_bytes(M, d, p, B) bytes, 256-byte aligned
+ *   flags      1: second stream (K_ZX's assembly and S = L_S L_S^T under the Cholesky chain); 2: include the KL term; 4: record
+ *              HIP-event timings (dsvgp_elbo_step_f64_timings); 8: the workspace contents are undefined (accepted for symmetry
+ *              with dsvgp_elbo_step_f32: this step keeps nothing in the workspace between calls)
+ * Gradients are those of loss = -(sum_j ll_j / global_rows - KL / num_data).  A factorisation that fails leaves NaNs in the outputs
+ * and a non-zero status word: dsvgp_elbo_step_f64_status waits for the factorisation only and returns it (and the constrained
+ * hyper-parameters); the caller then runs psd_safe_cholesky's jitter ladder on the piecewise entry points.
+ * dsvgp_elbo_step_f64_supported: 1 when the call takes (M, d, p, B), 0 otherwise (then _workspace_bytes is 0 as well); both are
+ * pure host functions.  dsvgp_elbo_step_f64_timings: ms5 = HIP-event durations (ms) of the step queued with flag 4 `steps_back`
+ * timed steps before the last one (the plan keeps 128): forward solve A = L^-1 K_ZX, K_ZX assembly, K_ZX-bar kernel backward, Gram
+ * product, dense K_ZX-bar product; waits for that step.                                                                         */
+typedef struct dsvgp_step_plan_f64 dsvgp_step_plan_f64;
+typedef struct dsvgp_elbo_step_io_f64 {
+    size_t struct_size;              /* sizeof(dsvgp_elbo_step_io_f64) of the CALLER's header                                    */
+    /* parameters: inducing points [M,d], directions [M p,d], q(u) mean [M'], Cholesky factor [M',M'] (lower triangle read),
+     * constant mean [1], raw hyper-parameters [1] each                                                                          */
+    const double *Z, *V, *m, *LS; int64_t ldls;
+    const double *constant, *raw_lengthscale, *raw_outputscale, *raw_noise;
+    /* minibatch: x [B,d], interleaved targets y [B(p+1)], derivative directions D [B p, d]                                       */
+    const double *x, *y, *D;
+    /* outputs: the flat gradient buffer (cleared here) and the slots inside it                                                   */
+    double* flat; size_t flat_doubles;
+    double *dZ, *dV, *dm, *dLS; int64_t lddls;
+    double *d_hyp, *d_constant, *d_raw_lengthscale, *d_raw_outputscale, *d_raw_noise, *loss;
+    double* mu;                      /* [B(p+1)] predictive mean of q(f) at the batch (constant mean included); not inside flat  */
+    double num_data, global_rows;    /* VariationalELBO num_data ((d+1) N); B'(global) of the minibatch                          */
+    double kzz_jitter;               /* LazyTensor.add_jitter() default 1e-3 (DGVS.py:144)                                      */
+} dsvgp_elbo_step_io_f64;
+int dsvgp_elbo_step_f64_supported(int M, int d, int p, int B);
+size_t dsvgp_elbo_step_f64_workspace_bytes(int M, int d, int p, int B);
+int dsvgp_elbo_step_f64_plan_create(dsvgp_ctx* ctx, int M, int d, int p, int B, dsvgp_step_plan_f64** out);
+int dsvgp_elbo_step_f64_plan_destroy(dsvgp_step_plan_f64* plan);
+int dsvgp_elbo_step_f64(dsvgp_ctx* ctx, dsvgp_step_plan_f64* plan, const dsvgp_elbo_step_io_f64* io, void* workspace,
+                        size_t workspace_bytes, int flags);
+int dsvgp_elbo_step_f64_status(dsvgp_step_plan_f64* plan, double* hyp4, int* info);
+int dsvgp_elbo_step_f64_timings(dsvgp_step_plan_f64* plan, int steps_back, float* ms5);
+long dsvgp_elbo_step_f64_timed_count(const dsvgp_step_plan_f64* plan);
+/* minibatch gather of the float64 model mode (dsvgp_gather_batch in double): xb[b,:] = X[idx[b],:], yb[b(p+1)+c] = Y[idx[b], cols[c]],
+ * and with E[d,d] != NULL the tiled one-hot directions Db[(b p + a), :] = E[cols[a+1] - 1, :]                                   */
+int dsvgp_gather_batch_f64(dsvgp_ctx* ctx, const double* X, const double* Y, const int64_t* idx, int nb, int d, int ycols,
+                           const int* cols, int p, double* xb, double* yb, const double* E, double* Db);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
