@@ -67,6 +67,7 @@ SIGNATURES = {
     "dsvgp_destroy": (_i, [_p]),
     "dsvgp_set_stream": (_i, [_p, _p]),
     "dsvgp_set_deterministic": (_i, [_p, _p, _z]),
+    "dsvgp_deterministic_f64_scratch_bytes": (_z, [_i, _i, _i, _i]),
     "dsvgp_elbo_step_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "dsvgp_elbo_step_plan_create": (_i, [_p, _i, _i, _i, _i, C.POINTER(_p)]),
     "dsvgp_elbo_step_plan_destroy": (_i, [_p]),

@@ -321,8 +321,10 @@ class ElboEngine64(ElboEngine):
         ms, LS = params["variational_mean"], params["chol_variational_covar"]
         grads = {k: g[k] for k in PARAM_NAMES if k not in ("inducing_directions", "variational_mean", "chol_variational_covar")}
         grads["inducing_directions"] = g["inducing_directions"].reshape(M, p, -1).sum(0)
-        dm = torch.zeros_like(ms)
-        dm.index_add_(0, idx, g["variational_mean"])
+        # the transpose of the interleave of _shared_expand64: value entries one to one, the p shared derivative entries summed over
+        # the M points (a plain reduction: index_add_ on the GPU adds in an order that changes from run to run)
+        gm = g["variational_mean"].reshape(M, p + 1)
+        dm = torch.cat([gm[:, 0], gm[:, 1:].sum(0)])
         dLS = torch.zeros_like(LS, memory_format=torch.contiguous_format)
         if include_kl:                                             # KL of the (M + p)-dimensional q(u)
             Lt = torch.tril(LS)
@@ -403,12 +405,31 @@ class ElboEngine64(ElboEngine):
             if mll_type not in ("ELBO", "PLL"):
                 raise ValueError("mll_type must be 'ELBO' or 'PLL'")
             return self._ciq_step64(_ops.Context.get(self.device), params, x, y, D, num_data, mll_type, global_rows, include_kl, True)
-        if getattr(self, "deterministic", False):
-            # the bitwise-reproducible mode (fixed-order split-K slabs, one stream) is built for the fp32 engine only: the fp64
-            # engine's transposed gemv and split-K products sum through fp64 atomics
-            raise NotImplementedError("deterministic mode covers the float32 engine (ElboEngine); the float64 model mode "
-                                      "(ElboEngine64) sums split-K slices and the transposed gemv with fp64 atomics")
         ctx = _ops.Context.get(self.device)
+        if self.deterministic:
+            # bitwise-reproducible mode (``engine.deterministic = True`` / DSVGP_DETERMINISTIC=1): every sum that meets in fp64 atomics by
+            # default -- split-K slices, column sums, the scalar sums, the tiled kernel backward's dP1 -- goes through this scratch in a
+            # fixed order (dsvgp_set_deterministic), and the step runs on ONE stream: the scratch serves one stream at a time.  Every
+            # Cholesky-whitened path is covered, the one-call step included (CIQ, routed above, is not part of the mode).
+            coll = self.collective
+            if coll is not None and coll.world > 1:
+                raise NotImplementedError("deterministic float64 model mode covers one rank: a collective with world > 1 "
+                                          "(world = %d) is not built for it" % coll.world)
+            Z, V = params["inducing_points"], params["inducing_directions"]
+            Mz = Z.shape[0]
+            pz = V.shape[0] if self.shared_directions else (V.shape[0] // Mz if Mz else 0)
+            nbytes = int(_lib.lib.dsvgp_deterministic_f64_scratch_bytes(Mz, Z.shape[1], pz, x.shape[0]))
+            if nbytes == 0:
+                raise ValueError("deterministic float64 model mode: shape (M, d, p, B) = (%d, %d, %d, %d) is not taken"
+                                 % (Mz, Z.shape[1], pz, x.shape[0]))
+            ctx.set_deterministic(self._bytes("det_slab64", nbytes))
+            try:
+                return self._loss_and_grads_entry64(ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
+            finally:
+                ctx.set_deterministic(None)
+        return self._loss_and_grads_entry64(ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
+
+    def _loss_and_grads_entry64(self, ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
         params, nat = self._from_natural(ctx, params)
         if self.shared_directions:
             out = self._shared_step64(ctx, params, x, y, D, num_data, mll_type, global_rows, include_kl)
@@ -425,7 +446,8 @@ class ElboEngine64(ElboEngine):
         """ELBO with ``fast`` None / True on one rank, Cholesky whitening, every data point with its derivatives, explicit-inverse
         regime; an explicit ``fast=False`` (per-output variances), PLL, shared directions, derivative-free data, CIQ, a collective
         with world > 1 and graph capture keep their paths.  The ``fast_min_work`` rule does not apply: it exists because the
-        Python-orchestrated Gram path is host-bound at small M' B'."""
+        Python-orchestrated Gram path is host-bound at small M' B'.  ``deterministic`` does not change the answer: the call covers
+        that mode itself (one stream, fixed-order sums through the context's scratch)."""
         if not (self.c_step and mll_type == "ELBO" and (fast is True or (fast is None and self.elbo_fast)) and not self.capture_mode
                 and self.whitening == "cholesky" and self.data_outputs == "all" and not self.shared_directions and not self._no_middle
                 and self.potrf_algo == 1 and self.fused_inverse and self._trsm_nb is None):
@@ -496,7 +518,7 @@ class ElboEngine64(ElboEngine):
         io.d_raw_lengthscale, io.d_raw_outputscale = P(grads["raw_lengthscale"]), P(grads["raw_outputscale"])
         io.d_raw_noise, io.loss, io.mu = P(grads["raw_noise"]), P(loss_out), P(mu)
         io.num_data, io.global_rows, io.kzz_jitter = float(num_data), float(rows), float(self.kzz_jitter)
-        overlap = self.overlap if self.overlap is not None else Mp >= 512
+        overlap = (self.overlap if self.overlap is not None else Mp >= 512) and not self.deterministic     # (the call ignores flag 1 then)
         timed = self.record_events and self._rec_count % max(1, self.record_every) == 0
         if self.record_events:
             self._rec_count += 1

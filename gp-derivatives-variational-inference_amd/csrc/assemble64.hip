@@ -57,11 +57,13 @@ __global__ __launch_bounds__(256) void fwd_transform64_kernel(double* __restrict
     blk[0] = k + (diag ? jitter : 0.0);
 }
 
-// (Gbar, T) -> Tbar in place of T; block partial sums of <Gbar, K>/s and of the lengthscale gradient go to d_hyp by atomics
+// (Gbar, T) -> Tbar in place of T; block partial sums of <Gbar, K>/s and of the lengthscale gradient go to d_hyp by atomics, or
+// (deterministic mode) to partials[workgroup][2] = {d lengthscale, d outputscale}, added in order afterwards
 __global__ __launch_bounds__(256) void bwd_transform64_kernel(const double* __restrict__ G, int64_t ldg, double* __restrict__ T,
                                                               int64_t ldt, const double* __restrict__ self1, int n1,
                                                               const double* __restrict__ self2, int n2, int p,
-                                                              const double* __restrict__ hyp, double* __restrict__ d_hyp) {
+                                                              const double* __restrict__ hyp, double* __restrict__ d_hyp,
+                                                              double* __restrict__ partials) {
     __shared__ double red[2][4];
     const int64_t pid = (int64_t)blockIdx.x * 256 + threadIdx.x;
     double ds = 0.0, dl = 0.0;
@@ -120,8 +122,10 @@ __global__ __launch_bounds__(256) void bwd_transform64_kernel(const double* __re
     if (lane == 0) { red[0][wave] = ds; red[1][wave] = dl; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(&d_hyp[1], red[0][0] + red[0][1] + red[0][2] + red[0][3]);     // d outputscale
-        atomicAdd(&d_hyp[0], red[1][0] + red[1][1] + red[1][2] + red[1][3]);     // d lengthscale
+        const double vs = red[0][0] + red[0][1] + red[0][2] + red[0][3];         // d outputscale
+        const double vl = red[1][0] + red[1][1] + red[1][2] + red[1][3];         // d lengthscale
+        if (partials) { partials[2 * (int64_t)blockIdx.x] = vl; partials[2 * (int64_t)blockIdx.x + 1] = vs; }
+        else { atomicAdd(&d_hyp[1], vs); atomicAdd(&d_hyp[0], vl); }
     }
 }
 
@@ -163,10 +167,11 @@ __global__ __launch_bounds__(64) void bwd_points64_kernel(const double* __restri
 
 // mu_j = sum_i A[i,j] m[i] (+ constant added by the caller), cs_j = sum_i (W[i,j]^2 - A[i,j]^2): the two column reductions of
 // DGVS.py:188,192-205 over the fp64 interpolation matrices.  64 columns x 4 row lanes per block, row range split over
-// gridDim.y, fp64 atomics into zeroed outputs.
+// gridDim.y, fp64 atomics into zeroed outputs -- or (deterministic mode) plain stores to the partial rows pmu / pcs [gridDim.y][Bp].
 __global__ __launch_bounds__(256) void colstats64_kernel(const double* __restrict__ A, int64_t lda, const double* __restrict__ W,
                                                          int64_t ldw, const double* __restrict__ m, int Mp, int Bp,
-                                                         double* __restrict__ mu, double* __restrict__ cs) {
+                                                         double* __restrict__ mu, double* __restrict__ cs, double* __restrict__ pmu,
+                                                         double* __restrict__ pcs) {
     __shared__ double red[2][4][64];
     const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
     const int j = blockIdx.x * 64 + c;
@@ -186,8 +191,15 @@ __global__ __launch_bounds__(256) void colstats64_kernel(const double* __restric
     red[1][g][c] = sq;
     __syncthreads();
     if (g == 0 && j < Bp) {
-        atomicAdd(mu + j, red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c]);
-        if (W) atomicAdd(cs + j, red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c]);
+        const double vm = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
+        const double vc = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+        if (pmu) {
+            pmu[(int64_t)blockIdx.y * Bp + j] = vm;
+            if (W) pcs[(int64_t)blockIdx.y * Bp + j] = vc;
+        } else {
+            atomicAdd(mu + j, vm);
+            if (W) atomicAdd(cs + j, vc);
+        }
     }
 }
 
@@ -215,7 +227,8 @@ __global__ __launch_bounds__(256) void likelihood64_kernel(const double* __restr
                                                            int ncols, int p, const double* __restrict__ hyp, int mll_type,
                                                            double inv_rows, double* __restrict__ mu_out,
                                                            double* __restrict__ varn_out, double* __restrict__ mu_bar,
-                                                           double* __restrict__ var_bar, double* __restrict__ scal) {
+                                                           double* __restrict__ var_bar, double* __restrict__ scal,
+                                                           double* __restrict__ partials) {
     __shared__ double red[5][4];
     const double ell = hyp[0], s = hyp[1], noise = hyp[2], c = constant[0];
     const double LOG2PI = 1.8378770664093454835606594728112;
@@ -261,7 +274,11 @@ __global__ __launch_bounds__(256) void likelihood64_kernel(const double* __restr
         if (lane == 0) red[q][wave] = v;
     }
     __syncthreads();
-    if (threadIdx.x < 5) atomicAdd(&scal[threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
+    if (threadIdx.x < 5) {
+        const double v = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        if (partials) partials[5 * blockIdx.x + threadIdx.x] = v;        // deterministic mode: added in order afterwards
+        else atomicAdd(&scal[threadIdx.x], v);
+    }
 }
 
 // Scalar tail of the fp64 ELBO fast path (ElboEngine64._elbo_fast64): the variance enters the ELBO only through its sum, so
@@ -270,7 +287,7 @@ __global__ __launch_bounds__(256) void fast_tail64_kernel(const double* __restri
                                                           const double* __restrict__ constant, int ncols,
                                                           const double* __restrict__ hyp, double inv_rows,
                                                           double* __restrict__ mu_out, double* __restrict__ mu_bar,
-                                                          double* __restrict__ scal) {
+                                                          double* __restrict__ scal, double* __restrict__ partials) {
     __shared__ double red[2][4];
     const double noise = hyp[2], c = constant[0];
     const double k = -inv_rows / noise;
@@ -286,7 +303,11 @@ __global__ __launch_bounds__(256) void fast_tail64_kernel(const double* __restri
     for (int off = 32; off > 0; off >>= 1) { a0 += __shfl_down(a0, off); a1 += __shfl_down(a1, off); }
     if (lane == 0) { red[0][wave] = a0; red[1][wave] = a1; }
     __syncthreads();
-    if (threadIdx.x < 2) atomicAdd(&scal[6 + threadIdx.x], red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3]);
+    if (threadIdx.x < 2) {
+        const double v = red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        if (partials) partials[2 * blockIdx.x + threadIdx.x] = v;        // deterministic mode: added in order afterwards
+        else atomicAdd(&scal[6 + threadIdx.x], v);
+    }
 }
 // ... and the closed forms (one thread): sum_j var_j + noise = s npts (1 + pd / ell^2) + ncols (1e-4 + noise) + tvar,
 // ll = -1/2 [(sum r^2 + that) / noise + ncols (log noise + log 2 pi)]  (expected_log_prob summed, directional_vi.py:245-246);
@@ -320,9 +341,15 @@ extern "C" int dsvgp_elbo_fast_tail_f64(dsvgp_ctx* ctx, const double* mu0, const
     if (e != hipSuccess) return 1000 + (int)e;
     int blocks = cdiv(ncols, 256);
     if (blocks > 256) blocks = 256;
+    double* parts = nullptr;
+    if (ctx->det_slab && !(parts = det_scratch64(ctx, (size_t)2 * blocks))) return DSVGP_EINVAL;      // (never back to atomics in this mode)
     hipLaunchKernelGGL(fast_tail64_kernel, dim3(blocks), dim3(256), 0, ctx->stream, mu0, y, constant, ncols, hyp, 1.0 / rows, mu,
-                       mu_bar, scal);
+                       mu_bar, scal, parts);
     DSVGP_LAUNCH_CHECK();
+    if (parts) {
+        const int rc = launch_det_sum_scalars64(ctx->stream, parts, blocks, 2, scal + 6);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(fast_tail64_final_kernel, dim3(1), dim3(64), 0, ctx->stream, hyp, tvar, ncols, npts, pd, 1.0 / rows, scal);
     DSVGP_LAUNCH_CHECK();
     return 0;
@@ -338,9 +365,12 @@ extern "C" int dsvgp_likelihood_terms_f64(dsvgp_ctx* ctx, const double* mu0, con
     if (e != hipSuccess) return 1000 + (int)e;
     int blocks = cdiv(ncols, 256);
     if (blocks > 256) blocks = 256;
+    double* parts = nullptr;
+    if (ctx->det_slab && !(parts = det_scratch64(ctx, (size_t)5 * blocks))) return DSVGP_EINVAL;      // (never back to atomics in this mode)
     hipLaunchKernelGGL(likelihood64_kernel, dim3(blocks), dim3(256), 0, ctx->stream, mu0, cs, y, constant, ncols, p, hyp, mll_type,
-                       1.0 / rows, mu, varn, mu_bar, var_bar, scal);
+                       1.0 / rows, mu, varn, mu_bar, var_bar, scal, parts);
     DSVGP_LAUNCH_CHECK();
+    if (parts) return launch_det_sum_scalars64(ctx->stream, parts, blocks, 5, scal);
     return 0;
 }
 
@@ -370,9 +400,13 @@ extern "C" int dsvgp_kernel_bwd_transform_f64(dsvgp_ctx* ctx, const double* G, i
     if (!ctx || !G || !T || !self1 || !self2 || !hyp || !d_hyp || n1 < 0 || n2 < 0 || p < 0 || p > 16) return DSVGP_EINVAL;
     if (ldg < (int64_t)n2 * (p + 1) || ldt < (int64_t)n2 * (p + 1)) return DSVGP_EINVAL;
     if (n1 == 0 || n2 == 0) return 0;
-    hipLaunchKernelGGL(bwd_transform64_kernel, dim3(cdiv((int64_t)n1 * n2, 256)), dim3(256), 0, ctx->stream, G, ldg, T, ldt,
-                       self1, n1, self2, n2, p, hyp, d_hyp);
+    const int blocks = cdiv((int64_t)n1 * n2, 256);
+    double* parts = nullptr;
+    if (ctx->det_slab && !(parts = det_scratch64(ctx, (size_t)2 * blocks))) return DSVGP_EINVAL;      // (never back to atomics in this mode)
+    hipLaunchKernelGGL(bwd_transform64_kernel, dim3(blocks), dim3(256), 0, ctx->stream, G, ldg, T, ldt, self1, n1, self2, n2, p, hyp,
+                       d_hyp, parts);
     DSVGP_LAUNCH_CHECK();
+    if (parts) return launch_det_sum_scalars64(ctx->stream, parts, blocks, 2, d_hyp);
     return 0;
 }
 extern "C" int dsvgp_kernel_bwd_points_f64(dsvgp_ctx* ctx, const double* dP, const double* P1, const double* vnorm1, int n1,
@@ -389,13 +423,29 @@ extern "C" int dsvgp_colstats_f64(dsvgp_ctx* ctx, const double* A, int64_t lda, 
                                   int Mp, int Bp, double* mu, double* cs) {
     if (!ctx || !A || !m || !mu || (W && !cs) || Mp < 0 || Bp < 0 || lda < Bp || (W && ldw < Bp)) return DSVGP_EINVAL;
     if (Bp == 0) return 0;
-    hipError_t e;
-    if ((e = hipMemsetAsync(mu, 0, sizeof(double) * Bp, ctx->stream)) != hipSuccess) return 1000 + (int)e;
-    if (W && (e = hipMemsetAsync(cs, 0, sizeof(double) * Bp, ctx->stream)) != hipSuccess) return 1000 + (int)e;
+    if (!ctx->det_slab || Mp == 0) {         // (deterministic mode: every element is stored by the kernel or by the rows pass)
+        hipError_t e;
+        if ((e = hipMemsetAsync(mu, 0, sizeof(double) * Bp, ctx->stream)) != hipSuccess) return 1000 + (int)e;
+        if (W && (e = hipMemsetAsync(cs, 0, sizeof(double) * Bp, ctx->stream)) != hipSuccess) return 1000 + (int)e;
+    }
     if (Mp == 0) return 0;
-    const int splits = max(1, min(64, Mp / 64));
-    hipLaunchKernelGGL(colstats64_kernel, dim3(cdiv(Bp, 64), splits), dim3(256), 0, ctx->stream, A, lda, W, ldw, m, Mp, Bp, mu, cs);
+    int splits = max(1, min(64, Mp / 64));
+    double *pmu = nullptr, *pcs = nullptr;
+    if (ctx->det_slab) {
+        // deterministic mode: as many row chunks as the scratch holds partial rows for; below two, ONE chunk that stores mu / cs itself
+        const size_t fit = ctx->det_bytes / sizeof(double) / ((size_t)Bp * (W ? 2 : 1));
+        if ((size_t)splits > fit) splits = (int)fit;
+        if (splits >= 2 && (pmu = det_scratch64(ctx, (size_t)splits * Bp * (W ? 2 : 1)))) pcs = pmu + (size_t)splits * Bp;
+        else { splits = 1; pmu = mu; pcs = cs; }
+    }
+    hipLaunchKernelGGL(colstats64_kernel, dim3(cdiv(Bp, 64), splits), dim3(256), 0, ctx->stream, A, lda, W, ldw, m, Mp, Bp, mu, cs, pmu,
+                       pcs);
     DSVGP_LAUNCH_CHECK();
+    if (pmu && pmu != mu) {
+        int rc = launch_det_sum_rows64(ctx->stream, pmu, splits, Bp, mu);
+        if (!rc && W) rc = launch_det_sum_rows64(ctx->stream, pcs, splits, Bp, cs);
+        return rc;
+    }
     return 0;
 }
 extern "C" int dsvgp_abar_f64(dsvgp_ctx* ctx, const double* A, int64_t lda, const double* U, int64_t ldu, const double* m,

@@ -16,7 +16,12 @@
 //   phase 3  Tbar_ab = k G_ab / ell^2
 //   phase 4  dP1[tile rows, :] += Tbar [P2 | indicator] on the MFMA, 64 packed columns at a time; the accumulators stay in
 //            registers across the sweep when the packed width is <= 64, and meet in fp64 vector atomics on the zeroed
-//            dP1[n1 q, DP] workspace (not a run-to-run deterministic sum, like the rest of the fp64 engine).
+//            dP1[n1 q, DP] workspace (run-order rounding: the default).
+// Deterministic mode (dsvgp_set_deterministic): every sweep group owns one slab [n1 q][DP] of the caller's scratch and writes it with
+// plain stores -- once at the end of its sweep when the accumulators stay in registers, tile by tile in column order (its own earlier
+// value read back and added to) at packed widths above 64 -- and its two hyper-parameter partials go to partials[workgroup][2]; a
+// fixed-order pass (det64.hip) adds the slabs in sweep order into dP1 for the points launch.  A scratch too small for all slabs takes
+// longer sweeps, down to one workgroup per tile row writing dP1 itself.
 // fp64 MFMA layouts: A[m = lane & 15][k = lane >> 4], B[k = lane >> 4][n = lane & 15], C/D row = (lane >> 4) + 4 reg, col = lane & 15.
 #include <limits.h>
 
@@ -199,7 +204,8 @@ __global__ __launch_bounds__(NT) void kernel_bwd64_tiled_kernel(const double* __
                                                                const double* __restrict__ P2, const double* __restrict__ self2, int n2q,
                                                                int q, int ntc, int sweep, int nsg, int K4, int DP,
                                                                const double* __restrict__ hyp, double* __restrict__ dP,
-                                                               double* __restrict__ d_hyp) {
+                                                               double* __restrict__ d_hyp, int64_t slab_stride,
+                                                               double* __restrict__ partials) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const Geo g = geo_of(q);
     const int Tt = g.Tt, Tp = g.Tp, LDT = g.LDT, R = g.R;
@@ -224,6 +230,7 @@ __global__ __launch_bounds__(NT) void kernel_bwd64_tiled_kernel(const double* __
         pjc[r] = r / q;
     }
     const bool keep = DP <= NCH;                        // dP1 accumulators live in registers across the sweep
+    double* const slab = partials ? dP + (int64_t)sg * slab_stride : nullptr;      // deterministic mode: this sweep group's own dP1
     const int mt = Tp >> 4;
     acc4 acc[MAXD];
 #pragma unroll
@@ -383,7 +390,14 @@ __global__ __launch_bounds__(NT) void kernel_bwd64_tiled_kernel(const double* __
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int m = tm * 16 + (lane >> 4) + 4 * r, n = n0 + tn * 16 + (lane & 15);
-                            if (m < rows && n < DP) atomicAdd(dP + (int64_t)(row0 + m) * DP + n, a4[r]);
+                            if (m < rows && n < DP) {
+                                if (slab) {             // one writer per address: store, then (no register sweep) add in column-tile order
+                                    double* dst = slab + (int64_t)(row0 + m) * DP + n;
+                                    *dst = (keep || ct == ct0) ? a4[r] : *dst + a4[r];
+                                } else {
+                                    atomicAdd(dP + (int64_t)(row0 + m) * DP + n, a4[r]);
+                                }
+                            }
                         }
                         a4 = acc4{0.0, 0.0, 0.0, 0.0};
                     }
@@ -397,8 +411,10 @@ __global__ __launch_bounds__(NT) void kernel_bwd64_tiled_kernel(const double* __
     if (lane == 0) { red[wave] = ds; red[4 + wave] = dl; }
     __syncthreads();
     if (tid == 0) {
-        atomicAdd(&d_hyp[1], red[0] + red[1] + red[2] + red[3]);        // d outputscale
-        atomicAdd(&d_hyp[0], red[4] + red[5] + red[6] + red[7]);        // d lengthscale
+        const double vs = red[0] + red[1] + red[2] + red[3];            // d outputscale
+        const double vl = red[4] + red[5] + red[6] + red[7];            // d lengthscale
+        if (partials) { partials[2 * (int64_t)blockIdx.x] = vl; partials[2 * (int64_t)blockIdx.x + 1] = vs; }
+        else { atomicAdd(&d_hyp[1], vs); atomicAdd(&d_hyp[0], vl); }
     }
 }
 
@@ -431,6 +447,22 @@ extern "C" int dsvgp_kernel_fwd_f64(dsvgp_ctx* ctx, const double* P1, const doub
     return 0;
 }
 
+// deterministic mode: bytes of scratch that hold every sweep group's dP1 slab and the d_hyp partials of one backward -- an upper bound
+// that does not shrink when n1 or n2 grows (the exact count does: a longer sweep can mean fewer groups).  From bwd64_tiled_sweep:
+// nsg = ntc while ntr ntc < 2048, nsg <= 2048 / ntr + 2 while the sweep is below its cap of 32, nsg = ceil(ntc / 32) above.
+size_t kernel_bwd64_tiled_det_bytes(int n1, int n2, int d, int p) {
+    if (bad_geometry(n1, n2, d, p) || n1 == 0 || n2 == 0) return 0;
+    const int q = p + 1;
+    const Geo g = geo_of(q);
+    const size_t n1q = (size_t)n1 * q, ntr = cdiv((int64_t)n1 * q, g.Tt), ntc = cdiv((int64_t)n2 * q, g.Tt);
+    const size_t DP = (size_t)((d + 3) & ~3) + 4;
+    auto lo = [](size_t a, size_t b) { return a < b ? a : b; };
+    const size_t capped = (ntc + 31) / 32;
+    const size_t rows = umax(lo(ntc * n1q, (size_t)2048 * g.Tt + 2 * n1q), capped * n1q);       // >= nsg n1 q
+    const size_t parts = umax(lo(ntc * ntr, 2048 + 2 * ntr), capped * ntr);                       // >= nsg ntr
+    return (rows * DP + 2 * parts) * sizeof(double);
+}
+
 extern "C" size_t dsvgp_kernel_bwd_f64_workspace_bytes(int n1, int n2, int d, int p) {
     if (bad_geometry(n1, n2, d, p) || n1 == 0) return 0;
     const size_t DP = (size_t)((d + 3) & ~3) + 4;
@@ -453,18 +485,44 @@ extern "C" int dsvgp_kernel_bwd_f64(dsvgp_ctx* ctx, const double* G, int64_t ldg
     const int q = p + 1, K4 = (d + 3) & ~3, DP = K4 + 4;
     const Geo g = geo_of(q);
     const int ntr = cdiv((int64_t)n1 * q, g.Tt), ntc = cdiv((int64_t)n2 * q, g.Tt);
-    // column tiles per workgroup: as long a sweep as leaves ~4 workgroups per CU
-    int sweep = (int)(((int64_t)ntr * ntc) / 1024);
-    sweep = max(1, min(min(sweep, 32), ntc));
-    const int nsg = cdiv(ntc, sweep);
+    int nsg;
+    int sweep = bwd64_tiled_sweep(ntr, ntc, &nsg);
     if ((int64_t)ntr * nsg > INT_MAX) return DSVGP_EINVAL;
     double* dP = (double*)workspace;
-    hipError_t e = hipMemsetAsync(dP, 0, need, ctx->stream);
-    if (e != hipSuccess) return 1000 + (int)e;
+    const size_t slab_doubles = need / sizeof(double);
+    double *target = dP, *partials = nullptr;
+    int64_t slab_stride = 0;
+    if (ctx->det_slab) {
+        // deterministic mode: slabs[nsg][n1 q][DP] | partials[ntr nsg][2] in the scratch; fewer, longer sweeps if it is small; with one
+        // sweep group per tile row that workgroup is the only writer of its dP1 rows and writes them in place (never back to atomics)
+        const size_t have = ctx->det_bytes / sizeof(double);
+        if (((uintptr_t)ctx->det_slab & 7) || have < (size_t)2 * ntr) return DSVGP_EINVAL;
+        while (nsg > 1 && (size_t)nsg * (slab_doubles + (size_t)2 * ntr) > have) {
+            ++sweep;
+            nsg = cdiv(ntc, sweep);
+        }
+        if (nsg > 1) {
+            target = (double*)ctx->det_slab;
+            slab_stride = (int64_t)slab_doubles;
+            partials = target + (size_t)nsg * slab_doubles;
+        } else {
+            sweep = ntc;
+            partials = (double*)ctx->det_slab;
+        }
+    } else {
+        hipError_t e = hipMemsetAsync(dP, 0, need, ctx->stream);
+        if (e != hipSuccess) return 1000 + (int)e;
+    }
     const size_t lds = bwd_lds_bytes(q);
     if (lds > 48 * 1024) (void)hipFuncSetAttribute((const void*)kernel_bwd64_tiled_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kernel_bwd64_tiled_kernel, dim3(ntr * nsg), dim3(NT), lds, ctx->stream, G, ldg, P1, self1, n1 * q, P2, self2, n2 * q,
-                       q, ntc, sweep, nsg, K4, DP, hyp, dP, d_hyp);
+                       q, ntc, sweep, nsg, K4, DP, hyp, target, d_hyp, slab_stride, partials);
     DSVGP_LAUNCH_CHECK();
+    if (partials) {
+        int rc = 0;
+        if (nsg > 1) rc = launch_det_sum_rows64(ctx->stream, target, nsg, (int64_t)slab_doubles, dP);
+        if (!rc) rc = launch_det_sum_scalars64(ctx->stream, partials, ntr * nsg, 2, d_hyp);
+        if (rc) return rc;
+    }
     return dsvgp_kernel_bwd_points_f64(ctx, dP, P1, vnorm1, n1, d, p, hyp, symmetric, d_x1, d_v1);
 }

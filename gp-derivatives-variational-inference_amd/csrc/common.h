@@ -92,6 +92,30 @@ void launch_widen_f32_f64(hipStream_t st, const float* src, int64_t ld, double* 
 int launch_gemm64(hipStream_t st, const GemmArgs& g);     // gemm64.hip: 1 = taken, 0 = not eligible, > 1 = error
 int launch_gemm32(hipStream_t st, const GemmArgs& g);     // gemm32.hip (fp32, 32x32x2 MFMA): same convention
 
+// ---------------------------------------------------------------------------------------------
+// Deterministic float64 model mode (det64.hip): what the fp64 kernels add through atomics by default goes, with ctx->det_slab set, to
+// the caller's scratch as per-workgroup partials (plain vector stores), and one of these fixed-order passes adds them.  Every launcher
+// takes the scratch from its start and queues the pass that consumes it before it returns: the scratch serves one stream.
+//   rows:    out[j] = parts[0][j] + parts[1][j] + ... + parts[ns - 1][j]      (j < n; column sums, dP1 slabs)
+//   scalars: out[c] += sum_i parts[i][c] (i < n, c < nc), 256 strided chains per component joined by a fixed tree
+// ---------------------------------------------------------------------------------------------
+int launch_det_sum_rows64(hipStream_t st, const double* parts, int ns, int64_t n, double* out);
+int launch_det_sum_scalars64(hipStream_t st, const double* parts, int n, int nc, double* out);
+static inline double* det_scratch64(const dsvgp_ctx* ctx, size_t doubles) {      // the scratch if it holds that many doubles, else null
+    return (ctx->det_slab && ctx->det_bytes / sizeof(double) >= doubles && ((uintptr_t)ctx->det_slab % 8) == 0) ? (double*)ctx->det_slab : nullptr;
+}
+// sweep rule of the tiled fp64 kernel backward (assemble64_tiled.hip): column tiles per workgroup -- as long a sweep as leaves ~4
+// workgroups per CU -- and the sweep groups per tile row that follow from it
+static inline int bwd64_tiled_sweep(int ntr, int ntc, int* nsg) {
+    int sweep = (int)(((int64_t)ntr * ntc) / 1024);
+    sweep = sweep < 32 ? sweep : 32;
+    sweep = sweep < ntc ? sweep : ntc;
+    sweep = sweep > 1 ? sweep : 1;
+    *nsg = cdiv(ntc, sweep);
+    return sweep;
+}
+size_t kernel_bwd64_tiled_det_bytes(int n1, int n2, int d, int p);      // assemble64_tiled.hip: slabs + partials of one backward
+
 // blocked Cholesky (potrf.hip)
 size_t potrf_blocked_workspace_bytes(int n);
 // hooks: after the launch that completes block row after_k of L^-1 (rows < 64 (after_k + 1) of Yinv / YinvT are final once it has

@@ -787,7 +787,8 @@ extern "C" int dsvgp_transpose_f32(dsvgp_ctx* ctx, const float* in, int64_t ldi,
 
 // ---- fp64 matrix-vector products of the float64 model mode (_step64.py: mu = A^T m, b = A mu-bar on the [M', B'] panel) ----
 // y = A x: one wave per row, 16-byte loads, butterfly sum.   y = A^T x: a thread per pair of columns, rows in chunks over
-// blockIdx.y, fp64 atomics onto the zeroed y.  (As N = 1 products on the 128 x 128 GEMM kernel they took 0.53 ms each at C4: 1.1 TB/s.)
+// blockIdx.y, fp64 atomics onto the zeroed y -- or (deterministic mode) plain stores to the partial rows parts[gridDim.y][N], added in
+// chunk order afterwards.  (As N = 1 products on the 128 x 128 GEMM kernel they took 0.53 ms each at C4: 1.1 TB/s.)
 __global__ __launch_bounds__(256) void gemv64_rows_kernel(const double* __restrict__ A, int64_t lda, int M, int N,
                                                           const double* __restrict__ x, double* __restrict__ y) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -812,7 +813,7 @@ __global__ __launch_bounds__(256) void gemv64_rows_kernel(const double* __restri
 }
 __global__ __launch_bounds__(256) void gemv64_cols_kernel(const double* __restrict__ A, int64_t lda, int M, int N,
                                                           const double* __restrict__ x, int rows_per_chunk,
-                                                          double* __restrict__ y) {
+                                                          double* __restrict__ y, double* __restrict__ parts) {
     const int j = (blockIdx.x * 256 + threadIdx.x) * 2;
     if (j >= N) return;
     const int i0 = blockIdx.y * rows_per_chunk, i1 = min(M, i0 + rows_per_chunk);
@@ -833,6 +834,12 @@ __global__ __launch_bounds__(256) void gemv64_cols_kernel(const double* __restri
             if (two) s1 = fma(A[(int64_t)i * lda + j + 1], xi, s1);
         }
     }
+    if (parts) {
+        double* dst = parts + (int64_t)blockIdx.y * N + j;
+        dst[0] = s0;
+        if (two) dst[1] = s1;
+        return;
+    }
     atomicAdd(&y[j], s0);
     if (two) atomicAdd(&y[j + 1], s1);
 }
@@ -842,12 +849,25 @@ extern "C" int dsvgp_gemv_f64(dsvgp_ctx* ctx, int trans, const double* A, int64_
     if (!trans) {
         hipLaunchKernelGGL(gemv64_rows_kernel, dim3(cdiv(M, 4)), dim3(256), 0, ctx->stream, A, lda, M, N, x, y);
     } else {
-        hipError_t e = hipMemsetAsync(y, 0, (size_t)N * sizeof(double), ctx->stream);
-        if (e != hipSuccess) return 1000 + (int)e;
         int nch = cdiv(M, 64);
         if (nch > 64) nch = 64;
+        double* parts = nullptr;
+        if (ctx->det_slab) {
+            // deterministic mode: as many row chunks as the scratch holds partial rows for; below two, one chunk that stores y itself
+            const size_t fit = ctx->det_bytes / sizeof(double) / (size_t)N;
+            if ((size_t)nch > fit) nch = fit >= 2 ? (int)fit : 1;
+            parts = nch >= 2 ? det_scratch64(ctx, (size_t)nch * N) : nullptr;
+            if (!parts) { nch = 1; parts = y; }
+        } else {
+            hipError_t e = hipMemsetAsync(y, 0, (size_t)N * sizeof(double), ctx->stream);
+            if (e != hipSuccess) return 1000 + (int)e;
+        }
         const int rpc = cdiv(M, nch);
-        hipLaunchKernelGGL(gemv64_cols_kernel, dim3(cdiv(N, 512), cdiv(M, rpc)), dim3(256), 0, ctx->stream, A, lda, M, N, x, rpc, y);
+        nch = cdiv(M, rpc);
+        hipLaunchKernelGGL(gemv64_cols_kernel, dim3(cdiv(N, 512), nch), dim3(256), 0, ctx->stream, A, lda, M, N, x, rpc, y, parts);
+        DSVGP_LAUNCH_CHECK();
+        if (parts && parts != y) return launch_det_sum_rows64(ctx->stream, parts, nch, N, y);
+        return 0;
     }
     DSVGP_LAUNCH_CHECK();
     return 0;

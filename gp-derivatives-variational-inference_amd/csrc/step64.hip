@@ -10,6 +10,8 @@
 // torch ran between them are the kernels of this file:
 //   prologue64_kernel      column mean of Z, the three softplus constraints, the packed rows of (Z, V) and of (x, D): one launch
 //   gemv64t_acc_kernel     mu0 += A^T m onto the step's cleared head (no fill launch of its own)
+// (deterministic mode, dsvgp_set_deterministic: one stream, and every sum that meets in fp64 atomics by default -- mu0, tvar, the KL
+// sum, the scalar tail, the kernel backwards' d_hyp and dP1, the split-K products -- goes through the caller's scratch in a fixed order)
 //   gram_epilogue64_kernel tril(G) -> symmetric G in one pass, tr G on the way
 //   variational64_kernel   one pass over the lower triangle of (L_S, H = tril(G L_S)): tr(L_S^T G L_S), the KL value, L_S-bar
 //   bvec64_kernel          b = A mu_bar into the extra row of [G ; b^T], m-bar = b + KL gradient
@@ -103,9 +105,10 @@ __global__ __launch_bounds__(256) void colmean_hyp64_kernel(const double* __rest
 }
 
 // y[N] += A^T x on a row-major M x N matrix (y cleared by the caller: the step's head): a thread per pair of columns, the rows in
-// chunks over blockIdx.y, fp64 atomics
+// chunks over blockIdx.y, fp64 atomics -- or (deterministic mode) plain stores to the partial rows parts[gridDim.y][N]
 __global__ __launch_bounds__(256) void gemv64t_acc_kernel(const double* __restrict__ A, int64_t lda, int M, int N,
-                                                          const double* __restrict__ x, int rows_per_chunk, double* __restrict__ y) {
+                                                          const double* __restrict__ x, int rows_per_chunk, double* __restrict__ y,
+                                                          double* __restrict__ parts) {
     const int j = (blockIdx.x * 256 + threadIdx.x) * 2;
     if (j >= N) return;
     const int i0 = blockIdx.y * rows_per_chunk, i1 = min(M, i0 + rows_per_chunk);
@@ -126,13 +129,20 @@ __global__ __launch_bounds__(256) void gemv64t_acc_kernel(const double* __restri
             if (two) s1 = fma(A[(int64_t)i * lda + j + 1], xi, s1);
         }
     }
+    if (parts) {
+        double* dst = parts + (int64_t)blockIdx.y * N + j;
+        dst[0] = s0;
+        if (two) dst[1] = s1;
+        return;
+    }
     atomicAdd(&y[j], s0);
     if (two) atomicAdd(&y[j + 1], s1);
 }
 
 // Gram epilogue: G[i][j] (i < j) = G[j][i] from the lower triangle the OUT_LOWER product wrote, and tvar -= tr G (the diagonal blocks
-// pass their 32 diagonal entries on the way).  32 x 32 blocks through LDS, as phi_sym_kernel.
-__global__ __launch_bounds__(256) void gram_epilogue64_kernel(double* __restrict__ G, int n, int64_t ldg, double* __restrict__ tvar) {
+// pass their 32 diagonal entries on the way).  32 x 32 blocks through LDS, as phi_sym_kernel.  Deterministic mode: parts[diagonal block].
+__global__ __launch_bounds__(256) void gram_epilogue64_kernel(double* __restrict__ G, int n, int64_t ldg, double* __restrict__ tvar,
+                                                              double* __restrict__ parts) {
     __shared__ double tile[32][33];
     const int bi = blockIdx.y, bj = blockIdx.x;
     if (bj < bi) return;                       // upper block (bi, bj), bj >= bi, from lower block (bj, bi)
@@ -149,7 +159,8 @@ __global__ __launch_bounds__(256) void gram_epilogue64_kernel(double* __restrict
     if (bi == bj && tx == 0 && ty == 0) {
         double tr = 0.0;
         for (int k = 0; k < 32; ++k) tr += tile[k][k];          // (rows past n were staged as zero)
-        atomicAdd(tvar, -tr);
+        if (parts) parts[bi] = -tr;
+        else atomicAdd(tvar, -tr);
     }
 }
 
@@ -158,10 +169,12 @@ __global__ __launch_bounds__(256) void gram_epilogue64_kernel(double* __restrict
 //   klsum += m_i^2 + sum_{j <= i} L_S,ij^2 - log(L_S,ii^2)              (with the KL term: KL = (klsum - M') / 2)
 //   dLS_ij = 2 vbar H_ij [+ (L_S,ij - [i == j] / L_S,ii) / num_data]   for j <= i; the strict upper triangle is not touched
 // 2 vbar = 1 / (noise rows): the expression dsvgp_elbo_fast_tail_f64 evaluates for scal[5], from the same hyp[2].
+// Deterministic mode: the two row sums go to parts[i][2] (tvar and klsum are neighbours in the head: one fixed-order pass adds both).
 __global__ __launch_bounds__(256) void variational64_kernel(const double* __restrict__ m, const double* __restrict__ LS, int64_t ldls,
                                                             const double* __restrict__ H, int64_t ldh, int Mp, double inv_nd, int add_kl,
                                                             const double* __restrict__ hyp, double inv_rows, double* __restrict__ tvar,
-                                                            double* __restrict__ klsum, double* __restrict__ dLS, int64_t lddls) {
+                                                            double* __restrict__ klsum, double* __restrict__ dLS, int64_t lddls,
+                                                            double* __restrict__ parts) {
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (i >= Mp) return;
     const double two_vbar = 2.0 * (0.5 * inv_rows / hyp[2]);
@@ -180,8 +193,14 @@ __global__ __launch_bounds__(256) void variational64_kernel(const double* __rest
     }
     for (int off = 32; off > 0; off >>= 1) { at += __shfl_down(at, off); al += __shfl_down(al, off); }
     if (lane == 0) {
-        atomicAdd(tvar, at);
-        if (add_kl) atomicAdd(klsum, al + m[i] * m[i] - log(lii * lii));
+        const double kv = add_kl ? al + m[i] * m[i] - log(lii * lii) : 0.0;
+        if (parts) {
+            parts[2 * i] = at;
+            parts[2 * i + 1] = kv;
+        } else {
+            atomicAdd(tvar, at);
+            if (add_kl) atomicAdd(klsum, kv);
+        }
     }
 }
 
@@ -464,7 +483,6 @@ extern "C" int dsvgp_elbo_step_f64(dsvgp_ctx* ctx, dsvgp_step_plan_f64* pl, cons
     const int M = pl->M, d = pl->d, p = pl->p, B = pl->B, Mp = pl->Mp, Bp = pl->Bp, DP = pl->DP, K4 = pl->K4, nb = pl->nb, ldS = pl->ldS;
     if (p > 0 && (!io->V || !io->D || !io->dV)) return DSVGP_EINVAL;
     if (io->ldls < Mp || io->lddls < Mp) return DSVGP_EINVAL;
-    if (ctx->det_slab) return DSVGP_EINVAL;            // (the deterministic mode covers the float32 step)
     char* w = (char*)workspace;
     double* center = (double*)(w + pl->o_center);
     double *PZ = (double*)(w + pl->o_PZ), *sZ = (double*)(w + pl->o_sZ), *vZ = (double*)(w + pl->o_vZ);
@@ -489,7 +507,12 @@ extern "C" int dsvgp_elbo_step_f64(dsvgp_ctx* ctx, dsvgp_step_plan_f64* pl, cons
     int* info = (int*)(hyp + 4);
     double *tvar = hyp + 5, *klsum = hyp + 6, *scal = hyp + 7, *mu0 = hyp + 15;
     const double rows = io->global_rows, inv_rows = 1.0 / rows, inv_nd = 1.0 / io->num_data;
-    const bool overlap = flags & 1, add_kl = flags & 2, timed = flags & 4;
+    // deterministic mode (dsvgp_set_deterministic): the scratch serves one stream at a time, so flag 1 is ignored -- the whole step is
+    // queued on the context's stream; every launcher below then adds its partial sums in a fixed order
+    double* const det = (double*)ctx->det_slab;
+    const size_t det_doubles = ctx->det_bytes / sizeof(double);
+    if (det && (((uintptr_t)det & 7) || det_doubles < (size_t)2 * Mp)) return DSVGP_EINVAL;       // (the row partials of the variational block)
+    const bool overlap = (flags & 1) && !det, add_kl = flags & 2, timed = flags & 4;
     const hipStream_t main = ctx->stream, side = pl->side;
     hipEvent_t* tm = nullptr;
     if (timed) { tm = pl->tm_ring[pl->timed_steps % dsvgp_step_plan_f64::TM_RING]; ++pl->timed_steps; }
@@ -568,9 +591,17 @@ extern "C" int dsvgp_elbo_step_f64(dsvgp_ctx* ctx, dsvgp_step_plan_f64* pl, cons
     {
         int nch = cdiv(Mp, 64);
         if (nch > 64) nch = 64;
+        double* parts = nullptr;
+        if (det) {              // as many row chunks as the scratch holds partial rows for; below two, one chunk that stores mu0 itself
+            const size_t fit = det_doubles / (size_t)Bp;
+            if ((size_t)nch > fit) nch = fit >= 2 ? (int)fit : 1;
+            parts = nch >= 2 ? det : mu0;
+        }
         const int rpc = cdiv(Mp, nch);
-        hipLaunchKernelGGL(gemv64t_acc_kernel, dim3(cdiv(Bp, 512), cdiv(Mp, rpc)), dim3(256), 0, main, A, (int64_t)Bp, Mp, Bp, io->m, rpc, mu0);
+        nch = cdiv(Mp, rpc);
+        hipLaunchKernelGGL(gemv64t_acc_kernel, dim3(cdiv(Bp, 512), nch), dim3(256), 0, main, A, (int64_t)Bp, Mp, Bp, io->m, rpc, mu0, parts);
         S64_LAUNCHED();
+        if (parts && parts != mu0) S64_CALL(launch_det_sum_rows64(main, parts, nch, Bp, mu0));
     }
     // ---- G = A A^T (lower triangle), mirrored with tr G on the way; H = tril(G L_S); the variational block
     S64_TIME(6);
@@ -581,16 +612,18 @@ extern "C" int dsvgp_elbo_step_f64(dsvgp_ctx* ctx, dsvgp_step_plan_f64* pl, cons
     S64_TIME(7);
     {
         const int nbk = cdiv(Mp, 32);
-        hipLaunchKernelGGL(gram_epilogue64_kernel, dim3(nbk, nbk), dim3(32, 8), 0, main, Ge, Mp, (int64_t)Mp, tvar);
+        hipLaunchKernelGGL(gram_epilogue64_kernel, dim3(nbk, nbk), dim3(32, 8), 0, main, Ge, Mp, (int64_t)Mp, tvar, det);
         S64_LAUNCHED();
+        if (det) S64_CALL(launch_det_sum_scalars64(main, det, nbk, 1, tvar));     // (before the next product takes the scratch for its slabs)
     }
     {
         Zeroed64 z(ctx, prezero);
         S64_CALL(gemm64(ctx, DSVGP_GEMM_B_LOWER | DSVGP_GEMM_OUT_LOWER, Mp, Mp, Mp, 1.0, Ge, Mp, io->LS, io->ldls, H, Mp));
     }
     hipLaunchKernelGGL(variational64_kernel, dim3(cdiv(Mp, 4)), dim3(256), 0, main, io->m, io->LS, io->ldls, H, (int64_t)Mp, Mp, inv_nd,
-                       add_kl ? 1 : 0, hyp, inv_rows, tvar, klsum, io->dLS, io->lddls);
+                       add_kl ? 1 : 0, hyp, inv_rows, tvar, klsum, io->dLS, io->lddls, det);
     S64_LAUNCHED();
+    if (det) S64_CALL(launch_det_sum_scalars64(main, det, Mp, 2, tvar));          // tvar | klsum
     // ---- scalar tail (mu, mu_bar into the extra row of [A ; mu_bar^T], scal), b = A mu_bar and m-bar
     S64_CALL(dsvgp_elbo_fast_tail_f64(ctx, mu0, io->y, io->constant, Bp, B, p, hyp, tvar, rows, io->mu, mu_bar, scal));
     hipLaunchKernelGGL(bvec64_kernel, dim3(cdiv(Mp, 4)), dim3(256), 0, main, A, (int64_t)Bp, Mp, Bp, mu_bar, io->m, add_kl ? inv_nd : 0.0, bvec,

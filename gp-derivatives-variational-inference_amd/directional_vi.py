@@ -200,6 +200,9 @@ class TrainLoop:
         if not mode or need_variance or self.dp is not None or self.autograd_protocol:
             return False
         eng = self.model.engine
+        # (deferral is a float32 feature and stays off under ``deterministic``.  A float64 model never defers -- last clause -- and its loop
+        # keeps the one-call step under ``deterministic``: ElboEngine64._c_step64_eligible does not look at the flag, dsvgp_elbo_step_f64
+        # itself runs on one stream with fixed-order sums then.)
         return (eng.whitening == "cholesky" and not eng.shared_directions and self.mll.mll_type == "ELBO" and eng.collective is None
                 and getattr(eng, "c_step", True) and not getattr(eng, "deterministic", False) and not getattr(eng, "host_trace", None)
                 and _optim.can_step_together([self.variational_optimizer, self.hyperparameter_optimizer])

@@ -53,6 +53,13 @@ int dsvgp_set_stream(dsvgp_ctx* ctx, void* hip_stream);
  * stream, one stream at a time; a product whose slices do not fit it runs with fewer, longer slices (unsplit below two).
  * The reference (CPU torch) is deterministic for a fixed seed; this mode gives the HIP path the same property.          */
 int dsvgp_set_deterministic(dsvgp_ctx* ctx, void* scratch, size_t bytes);
+/* Scratch size for the FLOAT64 model mode under dsvgp_set_deterministic (pure host function, no device call): enough for the largest
+ * user on any float64 path of an (M inducing points, d, p directions, B data points) step -- split-K slabs of the [M', M' + 1]
+ * products, the per-chunk partial rows of the column sums over B' (dsvgp_colstats_f64, dsvgp_gemv_f64 transposed), the per-workgroup
+ * partials of the scalar sums, and the tiled kernel backward's dP1 slabs, one per sweep group (p > 16).  0 for a shape the float64
+ * entry points do not take.  A smaller scratch is legal: a launcher whose partials do not fit runs unsplit (one writer per address)
+ * or returns DSVGP_EINVAL; none falls back to atomics while the mode is on.                                                        */
+size_t dsvgp_deterministic_f64_scratch_bytes(int M, int d, int p, int B);
 const char* dsvgp_version(void);
 
 /* ---- hyper-parameters: gpytorch Positive / GreaterThan(1e-4) softplus constraints ------------
@@ -196,7 +203,8 @@ int dsvgp_kernel_bwd_points_f64(dsvgp_ctx* ctx, const double* dP, const double* 
  *   dsvgp_kernel_bwd_f64   G = dLoss/dOut -> d_x1[n1,d] +=, d_v1[n1*p,d] +=, d_hyp[0] += d lengthscale, d_hyp[1] += d outputscale, as
  *                          the sequence gemm, dsvgp_kernel_bwd_transform_f64, gemm, dsvgp_kernel_bwd_points_f64 (symmetric != 0: point
  *                          and direction gradients doubled).  workspace: dsvgp_kernel_bwd_f64_workspace_bytes(n1, n2, d, p) bytes of
- *                          device memory (0 = geometry not taken), cleared here; sums meet in fp64 atomics (run-order rounding).      */
+ *                          device memory (0 = geometry not taken), cleared here; sums meet in fp64 atomics (run-order rounding),
+ *                          or, under dsvgp_set_deterministic, in per-sweep-group slabs of the scratch added in a fixed order.        */
 int dsvgp_kernel_fwd_f64(dsvgp_ctx* ctx, const double* P1, const double* self1, int n1, const double* P2, const double* self2,
                          int n2, int d, int p, const double* hyp, double jitter, int symmetric, double* out, int64_t ld);
 size_t dsvgp_kernel_bwd_f64_workspace_bytes(int n1, int n2, int d, int p);
@@ -595,6 +603,8 @@ long dsvgp_elbo_step_timed_count(const dsvgp_step_plan* plan);   /* steps queued
  *   flags      1: second stream (K_ZX's assembly and S = L_S L_S^T under the Cholesky chain); 2: include the KL term; 4: record
  *              HIP-event timings (dsvgp_elbo_step_f64_timings); 8: the workspace contents are undefined (accepted for symmetry
  *              with dsvgp_elbo_step_f32: this step keeps nothing in the workspace between calls)
+ * Under dsvgp_set_deterministic (scratch of dsvgp_deterministic_f64_scratch_bytes(M, d, p, B)) every sum of the step is formed in a
+ * fixed order -- losses and gradients are bitwise equal run to run -- and flag 1 is ignored: the scratch serves one stream.
  * Gradients are those of loss = -(sum_j ll_j / global_rows - KL / num_data).  A factorisation that fails leaves NaNs in the outputs
  * and a non-zero status word: dsvgp_elbo_step_f64_status waits for the factorisation only and returns it (and the constrained
  * hyper-parameters); the caller then runs psd_safe_cholesky's jitter ladder on the piecewise entry points.

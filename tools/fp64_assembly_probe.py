@@ -11,7 +11,11 @@ Times: one pair of device events around every call, median over `--reps` (>= 20)
 Derived from the shapes, by this file: the bytes the algorithm needs (forward: 8 per output entry + the packs; backward: 8 per
 upstream entry + the packs) over the time as a share of the 8 TB/s HBM roof, the MFMA flops (forward 2 n1q n2q K4; backward that again
 + 2 n1q n2q DP for Tbar [P2 | indicator]) over the time as a share of the 78.6 TF fp64 MFMA peak, and which of the two bounds is the
-longer one for the shape.  Prints one JSON object; --out writes it to a file, --summary a ten-line text digest."""
+longer one for the shape.  Prints one JSON object; --out writes it to a file, --summary a ten-line text digest.
+
+--deterministic adds the tiled backward under ``dsvgp_set_deterministic`` to the alternation, in both forms the launcher has: one dP1
+slab per sweep group added in sweep order (a scratch of ``dsvgp_deterministic_f64_scratch_bytes``), and one workgroup owning a tile row
+over the whole column range (what a scratch too small for two slabs selects)."""
 import argparse
 import json
 import os
@@ -57,7 +61,7 @@ def shares(ms, nbytes, flops):
                 bound="hbm" if t_hbm >= t_mfma else "mfma", share_of_bound=max(t_hbm, t_mfma) / t)
 
 
-def probe(dsvgp, dev, d, M, p, B, both, warmup, reps):
+def probe(dsvgp, dev, d, M, p, B, both, warmup, reps, deterministic=False):
     ops = dsvgp._ops
     ctx = ops.Context.get(dev)
     q = p + 1
@@ -84,6 +88,19 @@ def probe(dsvgp, dev, d, M, p, B, both, warmup, reps):
         out_o, scratch = torch.empty(n1q, n2q, dtype=f64, device=dev), torch.empty(n1q, n2q, dtype=f64, device=dev)
         fwd["register"] = lambda: ops.kernel_fwd_f64(ctx, pz, M, px, B, d, p, hyp, out=out_o)
         bwd["register"] = lambda: ops.kernel_bwd_f64(ctx, G, pz, M, px, B, d, p, hyp, False, dx, dv, dh, scratch)
+    if deterministic:
+        full = torch.empty(int(dsvgp._lib.lib.dsvgp_deterministic_f64_scratch_bytes(M, d, p, B)), dtype=torch.uint8, device=dev)
+        one_slab = torch.empty(8 * n1q * DP, dtype=torch.uint8, device=dev)        # < two slabs: one sweep group per tile row
+
+        def under(scratch):
+            def run():
+                ctx.set_deterministic(scratch)
+                try:
+                    ops.kernel_bwd_f64_tiled(ctx, G, pz, M, px, B, d, p, hyp, False, dx, dv, dh, workspace=ws)
+                finally:
+                    ctx.set_deterministic(None)
+            return run
+        bwd["tiled_det_slabs"], bwd["tiled_det_owner"] = under(full), under(one_slab)
     tf, tb = medians(fwd, warmup, reps), medians(bwd, warmup, reps)
     res = dict(d=d, M=M, p=p, B=B, n1q=n1q, n2q=n2q, K4=K4, out_mb=8 * n1q * n2q / 1e6, needed_bytes=nbytes,
                fwd_flops=f_fwd, bwd_flops=f_bwd, fwd={k: shares(v, nbytes, f_fwd) for k, v in tf.items()},
@@ -108,6 +125,10 @@ def summary(res):
             return "%8.3f [%.2f %s]" % (c["ms"], c["share_of_bound"], c["bound"]) if c else "   not taken    "
         lines.append("%-12s d %3d p %2d M %4d B %4d  fwd %s | %s   bwd %s | %s" % (
             name, r["d"], r["p"], r["M"], r["B"], cell("fwd", "register"), cell("fwd", "tiled"), cell("bwd", "register"), cell("bwd", "tiled")))
+    for name, r in res["geometries"].items():
+        if "tiled_det_slabs" in r["bwd"]:
+            lines.append("%-12s bwd tiled, ms: atomics %.3f | deterministic, slab per sweep group %.3f | deterministic, one workgroup per tile row %.3f"
+                         % (name, r["bwd"]["tiled"]["ms"], r["bwd"]["tiled_det_slabs"]["ms"], r["bwd"]["tiled_det_owner"]["ms"]))
     lines.append("bounds: bytes needed / 8 TB/s HBM, MFMA flops / 78.6 TF fp64; backward times include the memset of dP1 and the points launch")
     return "\n".join(lines) + "\n"
 
@@ -119,6 +140,7 @@ def main():
     ap.add_argument("--only", default=",".join(GEOMS))
     ap.add_argument("--out", default=None)
     ap.add_argument("--summary", default=None)
+    ap.add_argument("--deterministic", action="store_true")
     args = ap.parse_args()
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import dsvgp_amd
@@ -129,7 +151,7 @@ def main():
                reps=args.reps, geometries={})
     for name in args.only.split(","):
         d, M, p, B, both = GEOMS[name]
-        res["geometries"][name] = probe(dsvgp_amd, dev, d, M, p, B, both, args.warmup, args.reps)
+        res["geometries"][name] = probe(dsvgp_amd, dev, d, M, p, B, both, args.warmup, args.reps, args.deterministic)
         print(json.dumps({name: res["geometries"][name]}), flush=True)
     print(json.dumps(res))
     if args.out:
