@@ -184,6 +184,10 @@ SIGNATURES = {
     "dsvgp_adam_step_multi": (_i, [_p, _i, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i]),
     "dsvgp_adam_step_multi_guarded": (_i, [_p, _i, _p, _p, _p, _p, _p, _f, _f, _f, _f, _i, _p]),
     "dsvgp_adam_step_multi_f64": (_i, [_p, _i, _p, _p, _p, _p, _p, _d, _d, _d, _d, _i]),
+    "dsvgp_mean_weights_bytes": (_z, [_i, _i]),
+    "dsvgp_mean_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dsvgp_mean_prepare": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    "dsvgp_mean_predict": (_i, [_p, _p, _i, _i, _p, _i, _p, _i, _p, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -717,6 +717,73 @@ def predictive_stats(ctx, A, W, p, m, constant, hyp, mu, var, workspace=None):
     return workspace
 
 
+def mean_weights_bytes(M, d):
+    return int(lib.dsvgp_mean_weights_bytes(int(M), int(d)))
+
+
+def mean_workspace_bytes(M, d, B, pd):
+    return int(lib.dsvgp_mean_workspace_bytes(int(M), int(d), int(B), int(pd)))
+
+
+def mean_prepare(ctx, alpha, Z, V, p, hyp, constant, center=None, weights=None):
+    """alpha = L^-T m (float64 [M(p+1)]) and the inducing set -> the packed fp32 weights of the posterior-mean predictor
+    (dsvgp_mean_prepare; a float32 tensor of dsvgp_mean_weights_bytes(M, d) bytes)"""
+    _req(Z, f32, "Z", 2)
+    M, d = Z.shape
+    _req(alpha, f64, "alpha", 1)
+    if alpha.shape[0] != M * (p + 1):
+        raise ValueError("alpha must have M (p + 1) = %d entries, got %d" % (M * (p + 1), alpha.shape[0]))
+    if p > 0:
+        _req(V, f32, "V", 2)
+        if V.shape != (M * p, d):
+            raise ValueError("directions must be [M*p, d] = [%d, %d], got %s" % (M * p, d, tuple(V.shape)))
+    if not Z.is_contiguous() or (p > 0 and not V.is_contiguous()):
+        raise ValueError("Z and V must be contiguous")
+    if center is not None:
+        _req(center, f32, "center", 1)
+        if center.shape != (d,):
+            raise ValueError("center must have shape [%d]" % d)
+    constant = _req(constant.reshape(-1), f32, "constant")
+    n = (mean_weights_bytes(M, d) + 3) // 4
+    if weights is None:
+        weights = torch.empty(n, dtype=f32, device=Z.device)
+    _req(weights, f32, "weights", 1)
+    if weights.numel() < n:
+        raise ValueError("weights buffer too small: %d < %d floats" % (weights.numel(), n))
+    check(lib.dsvgp_mean_prepare(ctx.h, _ptr(alpha), _ptr(Z), _ptr(V if p > 0 else None), M, d, p, _ptr(hyp), _ptr(constant),
+                                 _ptr(center), _ptr(weights)), "dsvgp_mean_prepare")
+    return weights
+
+
+def mean_predict(ctx, weights, M, d, x, D=None, pd=0, mean_out=None, grad_out=None, workspace=None):
+    """mean_out[B(pd+1)] (interleaved) and, when ``grad_out`` [B, d] is given, the gradient of the mean without the constant
+    (dsvgp_mean_predict).  ``workspace``: uint8 tensor of dsvgp_mean_workspace_bytes(M, d, B, pd) bytes (None when that is 0)."""
+    _req(x, f32, "x", 2)
+    _req(weights, f32, "weights", 1)
+    B = x.shape[0]
+    if x.shape[1] != d or not x.is_contiguous():
+        raise ValueError("x must be a contiguous [B, %d] tensor, got %s" % (d, tuple(x.shape)))
+    if pd > 0:
+        _req(D, f32, "D", 2)
+        if D.shape != (B * pd, d) or not D.is_contiguous():
+            raise ValueError("directions must be a contiguous [B*pd, d] = [%d, %d] tensor, got %s" % (B * pd, d, tuple(D.shape)))
+    if mean_out is None:
+        mean_out = torch.empty(B * (pd + 1), dtype=f32, device=x.device)
+    _req(mean_out, f32, "mean_out", 1)
+    if mean_out.numel() != B * (pd + 1):
+        raise ValueError("mean_out must have B (pd + 1) = %d entries" % (B * (pd + 1)))
+    if grad_out is not None:
+        _req(grad_out, f32, "grad_out", 2)
+        if grad_out.shape != (B, d) or not grad_out.is_contiguous():
+            raise ValueError("grad_out must be a contiguous [%d, %d] tensor" % (B, d))
+    need = mean_workspace_bytes(M, d, B, pd)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        raise ValueError("mean_predict workspace too small: %d bytes needed" % need)
+    check(lib.dsvgp_mean_predict(ctx.h, _ptr(weights), M, d, _ptr(x), B, _ptr(D if pd > 0 else None), pd, _ptr(mean_out),
+                                 _ptr(grad_out), _ptr(workspace if need else None)), "dsvgp_mean_predict")
+    return mean_out
+
+
 def likelihood_terms(ctx, mu, var, y, p, hyp, mll_type, global_rows, mu_bar, var_bar, varn, scalars):
     check(lib.dsvgp_likelihood_terms(ctx.h, _ptr(mu), _ptr(var), _ptr(_req(y, f32, "y", 1)), mu.shape[0], p, _ptr(hyp),
                                      int(mll_type), float(global_rows), _ptr(mu_bar), _ptr(var_bar), _ptr(varn),

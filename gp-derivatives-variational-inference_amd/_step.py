@@ -47,6 +47,59 @@ class _Refactored(Exception):
     """The deferred potrf status turned out non-zero: the jitter ladder must run and the step be redone."""
 
 
+class MeanPredictor:
+    """Posterior mean and its gradient of a FROZEN model: mu_f(x) = c + s sum_i k_i beta_i from packed fp32 weights
+    (``ElboEngine.mean_predictor``; csrc/predict_mean.hip).  No K_ZX, no solve, nothing of size M' x B'; O(M d) per point.
+    Holds its own buffers (the weights and, for d > 32, the [B, 2M] workspace): the engine's evaluation cache and training
+    workspaces are not used after construction.  Valid for the parameter values it was built from."""
+
+    def __init__(self, device, weights, M, d, values_only=False):
+        self.device = torch.device(device)
+        self.weights, self.M, self.d = weights, int(M), int(d)
+        self.values_only = bool(values_only)        # engine.data_outputs == "values": derivative-free data, value rows only
+        self._ws = None
+
+    def _workspace(self, B, pd):
+        need = _ops.mean_workspace_bytes(self.M, self.d, B, pd)
+        if need == 0:
+            return None
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _run(self, x, D, pd, want_grad):
+        ctx = _ops.Context.get(self.device)
+        if not x.is_cuda:
+            raise _lib.DsvgpError("x must live on the GPU: the DSVGP hot path has no CPU fallback")
+        x = x.contiguous()
+        B = x.shape[0]
+        mean = torch.empty(B * (pd + 1), dtype=f32, device=self.device)
+        grad = torch.empty(B, self.d, dtype=f32, device=self.device) if want_grad else None
+        # d > 32: the [B, 2M] intermediates are indexed with 32 bits -- very large batches go through in row blocks
+        rows = B if self.d <= 32 else max(1, min(B, (1 << 29) // max(2 * self.M + 4, self.d + 4)))
+        for r0 in range(0, B, max(rows, 1)):
+            r1 = min(B, r0 + rows)
+            _ops.mean_predict(ctx, self.weights, self.M, self.d, x[r0:r1], D[r0 * pd:r1 * pd] if pd else None, pd,
+                              mean[r0 * (pd + 1):r1 * (pd + 1)], grad[r0:r1] if want_grad else None,
+                              self._workspace(r1 - r0, pd))
+        return mean, grad
+
+    @torch.no_grad()
+    def mean(self, x, D=None):
+        """[B (pd + 1)] interleaved: the value row of every point, then c + w^ . grad mu_f for each of its pd = D.shape[0] // B
+        directions (rows of D are normalised inside).  ``D=None``: values only."""
+        B = x.shape[0]
+        pd = 0 if (D is None or self.values_only or B == 0) else D.shape[0] // B
+        if pd and not D.is_cuda:
+            raise _lib.DsvgpError("D must live on the GPU: the DSVGP hot path has no CPU fallback")
+        return self._run(x, D.contiguous() if pd else None, pd, False)[0]
+
+    @torch.no_grad()
+    def value_and_gradient(self, x):
+        """(mu_f [B], grad mu_f [B, d]); the gradient carries no constant"""
+        return self._run(x, None, 0, True)
+
+
 class ElboEngine:
     """Owns the HBM workspaces of one (M', B', d, p) configuration on one GPU."""
 
@@ -474,6 +527,35 @@ class ElboEngine:
             finally:
                 self._no_middle = False
         return self._predict_chol(ctx, params, x, D, cache, joint=True)
+
+    @torch.no_grad()
+    def mean_predictor(self, params):
+        """``MeanPredictor`` of the current parameter values: alpha = L^-T m from ONE transposed fp64 solve with the factor of
+        ``_factor`` (jitter ladder included), packed with the inducing set by dsvgp_mean_prepare.  Natural parameters, shared
+        directions, p = 0 (plain SVGP) and p = d (full-gradient SVGP) are the same code.  The factorisation runs in the engine's
+        factor buffers, so the evaluation cache of ``predict`` is dropped (it refactors on its next call)."""
+        if self.whitening == "ciq":
+            raise NotImplementedError("posterior-mean predictor with CIQ whitening: alpha there is K^{-1/2} m by msMINRES "
+                                      "(contour-integral quadrature), which is not built; use predict()")
+        ctx = _ops.Context.get(self.device)
+        self._eval_cache = None
+        if "natural_vec" in params:
+            m32, LS32, _, _ = self._natural_to_mu_chol(ctx, params["natural_vec"], params["natural_mat"])
+            params = {k: v for k, v in params.items() if not k.startswith("natural_")}
+            params["variational_mean"], params["chol_variational_covar"] = m32, LS32
+        if self.shared_directions:
+            params, _ = self._shared_expand(params)
+        hyp, packZ, L, (M, d, p, Mp) = self._factor(ctx, params, sync=True)
+        m = params["variational_mean"]
+        if m.shape[0] != Mp:
+            raise ValueError("q(u) has %d values, the inducing set M (p + 1) = %d" % (m.shape[0], Mp))
+        rhs = m.to(f64).reshape(Mp, 1).contiguous()
+        alpha = torch.empty(Mp, 1, dtype=f64, device=self.device)
+        _ops.trsm(ctx, L, rhs, True, alpha, None, self.trsm_nb, self._inverse_ws, reuse_inverse=True)      # alpha = L^-T m
+        weights = _ops.mean_prepare(ctx, alpha.reshape(Mp), params["inducing_points"].contiguous(),
+                                    params["inducing_directions"].contiguous() if p > 0 else None, p, hyp,
+                                    params["constant"], self.center)
+        return MeanPredictor(self.device, weights, M, d, values_only=self.data_outputs == "values")
 
     @torch.no_grad()
     def whiten_legacy(self, params):

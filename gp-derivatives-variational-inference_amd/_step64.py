@@ -341,6 +341,10 @@ class ElboEngine64(ElboEngine):
         return full
 
     # ---- public API -----------------------------------------------------------------------------
+    def mean_predictor(self, params):
+        raise NotImplementedError("the posterior-mean predictor (csrc/predict_mean.hip) is built for the float32 model mode only; "
+                                  "use predict() / likelihood(model(x, derivative_directions=D)).mean")
+
     @torch.no_grad()
     def predict(self, params, x, D, cache=False):
         ctx = _ops.Context.get(self.device)

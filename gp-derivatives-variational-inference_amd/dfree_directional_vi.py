@@ -89,3 +89,8 @@ def eval_gp(test_dataset, model, likelihood,
     """Predictive means / variances (with likelihood noise) of the function values, CPU vectors of length N_test
     (reference dfree_directional_vi.py:265-292)."""
     return _dvi.eval_gp(test_dataset, model, likelihood, mll_type, num_directions, minibatch_size, minibatch_dim)
+
+
+def eval_mean(test_dataset, model, num_directions=1, minibatch_size=1, minibatch_dim=1):
+    """``eval_gp(...)[0]`` without the variances: CPU vector of the N_test function-value means (``directional_vi.eval_mean``)"""
+    return _dvi.eval_mean(test_dataset, model, num_directions, minibatch_size, minibatch_dim)

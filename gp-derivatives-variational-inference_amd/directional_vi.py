@@ -642,3 +642,25 @@ def eval_gp(test_dataset, model, likelihood,
     variances = torch.cat(variances) if variances else torch.zeros(0)
     print("Done Testing!")
     return means, variances
+
+
+def eval_mean(test_dataset, model, num_directions=1, minibatch_size=1, minibatch_dim=1):
+    """``eval_gp(...)[0]`` for callers that read only the means (reference experiments/bunny/exp_bunny.py:189-195
+    ``means, _ = eval_gp(...)``): same batching, the same ``eye(d)[:p]`` directions, same ordering, CPU vector of length
+    N_test*(p+1) -- through ``model.posterior_mean`` (no K_ZX, no solve, no variances)."""
+    assert num_directions == minibatch_dim
+    dim = len(test_dataset[0][0])
+    device = model.variational_strategy.inducing_points.device
+    X, _ = _dataset_tensors(test_dataset, device, model.variational_strategy.inducing_points.dtype)
+    n_test = X.shape[0]
+
+    model.eval()
+
+    means = []
+    with torch.no_grad():
+        for start in range(0, n_test, minibatch_size):
+            x_batch = X[start:start + minibatch_size]
+            derivative_directions = torch.eye(dim, device=device)[:num_directions]
+            derivative_directions = derivative_directions.repeat(len(x_batch), 1)
+            means.append(model.posterior_mean(x_batch, derivative_directions=derivative_directions).cpu())
+    return torch.cat(means) if means else torch.zeros(0)

@@ -309,6 +309,45 @@ class ApproximateGP(torch.nn.Module):
                 for p in mod.parameters(recurse=False):
                     yield p
 
+    # ---- posterior mean without the predictive distribution (what the reference's mean-only callers read from
+    #      ``likelihood(model(x, derivative_directions=D)).mean``: experiments/bunny/exp_bunny.py:189-195,
+    #      experiments/rover/bo_traditional.py:214, experiments/GNN_bo/bo.py:172) ----
+    def _mean_predictor(self):
+        """The engine's ``MeanPredictor`` for the current parameters.  Eval mode: cached on the model, keyed by
+        (data_ptr, _version) of the parameters like the engine's evaluation cache -- an optimizer step or ``load_state_dict``
+        changes the key; training mode: rebuilt per call."""
+        engine = self.engine            # (ElboEngine64 -- a float64 model -- refuses: NotImplementedError)
+        vs = self.variational_strategy
+        if hasattr(vs, "_strategy_is_updated") and not vs._strategy_is_updated():
+            vs._whiten_legacy_parameters()
+        if self.training and hasattr(vs, "_maybe_init"):
+            vs._maybe_init()
+        params = self._param_dict(None)
+        # (the mean does not depend on the likelihood noise, whose stand-in is a fresh tensor per call)
+        key = tuple((t.data_ptr(), t._version) for k, t in params.items() if k != "raw_noise")
+        key += (engine.whitening, engine.data_outputs, engine.shared_directions)
+        cached = self.__dict__.get("_mean_cache")
+        if not self.training and cached is not None and cached[0] == key and cached[1] is engine:
+            return cached[2]
+        pred = engine.mean_predictor(params)
+        self.__dict__["_mean_cache"] = (key, engine, pred) if not self.training else None
+        return pred
+
+    def posterior_mean(self, x, derivative_directions=None):
+        """Predictive mean at x [B, d]: [B (pd + 1)] interleaved with pd = len(derivative_directions) // B rows per point
+        (``None``: function values only); equals ``likelihood(self(x, derivative_directions=D)).mean`` without assembling
+        K_ZX or solving against K_ZZ per batch (``ElboEngine.mean_predictor``).  Not differentiable."""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        return self._mean_predictor().mean(x, derivative_directions)
+
+    def posterior_mean_gradient(self, x):
+        """Gradient of the predictive mean of f at x [B, d] -> [B, d] (all d partial derivatives, whatever the number of
+        directions the model was trained with)"""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        return self._mean_predictor().value_and_gradient(x)[1]
+
     def __call__(self, inputs, prior=False, **kwargs):
         if inputs.dim() == 1:
             inputs = inputs.unsqueeze(-1)

@@ -643,6 +643,37 @@ long dsvgp_elbo_step_f64_timed_count(const dsvgp_step_plan_f64* plan);
 int dsvgp_gather_batch_f64(dsvgp_ctx* ctx, const double* X, const double* Y, const int64_t* idx, int nb, int d, int ycols,
                            const int* cols, int p, double* xb, double* yb, const double* E, double* Db);
 
+/* ---- posterior mean of a frozen model (csrc/predict_mean.hip): mean and gradient without K_ZX or a solve.
+ * What the reference's mean-only callers read from `likelihood(model(x, derivative_directions=D)).mean`
+ * (experiments/bunny/exp_bunny.py:189-195 `means, _ = eval_gp(...)`, experiments/rover/bo_traditional.py:214 `preds.mean`) for the
+ * Cholesky-whitened strategy (DirectionalGradVariationalStrategy.py:181-188: mu = K_XZ L^-T m + c).  With alpha = L^-T m (fp64: one
+ * dsvgp_trsm with trans = 1 per parameter state), a_i = alpha[i(p+1)], g_i = sum_s alpha[i(p+1)+1+s] v^_is (v^: L2-normalised inducing
+ * directions, RBFKernelDirectionalGrad.py:57), r_i = (z_i - x) / ell, k_i = exp(-|r_i|^2 / 2), beta_i = a_i - (r_i . g_i) / ell:
+ *     mu_f(x) = c + s sum_i k_i beta_i,   grad mu_f(x) = s sum_i k_i (beta_i r_i / ell + g_i / ell^2),
+ *     row of direction w at x (interleaved after the value row) = c + w^ . grad mu_f(x)          (the constant on every row: DGVS.py:126)
+ * O(M d) per point instead of O(M'^2); nothing of size M' x B' exists; the directions at the data (pd per point) are independent of the
+ * model's p (p = 0: plain SVGP, p = d: full-gradient SVGP).
+ *   dsvgp_mean_prepare   alpha[M(p+1)] (double), Z[M,d], V[M*p,d] (raw directions, normalised here; NULL when p = 0; p <= 95), hyp,
+ *                        constant (device float), center[d] (NULL = 0; the column mean of Z keeps the composed path's fp32 expansion
+ *                        accurate, as in dsvgp_pack_points) -> weights: dsvgp_mean_weights_bytes(M, d) bytes, 16-byte aligned, fp32:
+ *                        {ell, s, c, ..}, center, a, a - z~.g/ell, |z~|^2, [Z~ ; G/ell].  One launch.
+ *   dsvgp_mean_predict   x[B,d], D (NULL or [B*pd, d] raw directions, normalised here) -> mean_out[B(pd+1)] interleaved, grad_out (NULL
+ *                        or [B,d]) = grad mu_f (without the constant).  One call per batch: no host read, no synchronisation, no
+ *                        allocation, queued on the context's stream.  d <= 32: ONE fused kernel (a workgroup owns 64 test points, walks
+ *                        the inducing points in LDS-staged chunks, accumulator in registers; workspace may be NULL).  Any other d: the
+ *                        same sums through [B, 2M] intermediates in `workspace` (dsvgp_mean_workspace_bytes(M, d, B, pd) bytes, 16-byte
+ *                        aligned; 0 for d <= 32): [S1 | S2] = X~ [Z~ ; G']^T on the fp32 MFMA GEMM, a pointwise kernel, the
+ *                        [B, 2M] x [2M, d] product, an epilogue kernel; at most 2 B M + 2 B (d + 3) + 4 B + 8 floats.
+ *                        DSVGP_EINVAL when B * 2M reaches 2^31 there (split the batch).
+ * No floating-point atomics and fixed-order reductions on both paths: two identical calls return bitwise identical results.
+ * DSVGP_EINVAL for M, B or d < 1.  The two size helpers are pure host functions (0 for a shape not taken).                          */
+size_t dsvgp_mean_weights_bytes(int M, int d);
+size_t dsvgp_mean_workspace_bytes(int M, int d, int B, int pd);
+int dsvgp_mean_prepare(dsvgp_ctx* ctx, const double* alpha, const float* Z, const float* V, int M, int d, int p, const float* hyp,
+                       const float* constant, const float* center, float* weights);
+int dsvgp_mean_predict(dsvgp_ctx* ctx, const float* weights, int M, int d, const float* x, int B, const float* D, int pd,
+                       float* mean_out, float* grad_out, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
