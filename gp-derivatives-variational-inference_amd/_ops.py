@@ -558,6 +558,27 @@ def kernel_fwd_wide(ctx, pack1, n1, pack2, n2, d, p, hyp, jitter=0.0, out=None, 
     return out
 
 
+def kernel_fwd_rect(ctx, pack1, n1, p1, pack2, n2, p2, d, hyp, out=None):
+    """out[n1 (p1 + 1), n2 (p2 + 1)] = s K(x1, x2; v1, v2) for packs made with DIFFERENT direction counts p1, p2 (each by
+    ``pack_points`` with its own p and the same center); float32, forward only (csrc/assemble_rect.hip)"""
+    P1, s1 = pack1[0], pack1[1]
+    P2, s2 = pack2[0], pack2[1]
+    shape = (n1 * (p1 + 1), n2 * (p2 + 1))
+    for P, sf, n, p, name in ((P1, s1, n1, p1, "pack1"), (P2, s2, n2, p2, "pack2")):
+        _req(P, f32, name, 2)
+        _req(sf, f32, name + " self terms", 1)
+        if P.shape != (n * (p + 1), packed_width(d)) or sf.shape[0] != n * (p + 1) or not P.is_contiguous():
+            raise ValueError("%s is not the contiguous pack of %d points with %d directions at d = %d" % (name, n, p, d))
+    if out is None:
+        out = torch.empty(shape, dtype=f32, device=P1.device)
+    _req(out, f32, "out", 2)
+    if out.shape != shape:
+        raise ValueError("out has shape %s, expected %s" % (tuple(out.shape), shape))
+    check(lib.dsvgp_kernel_fwd_rect(ctx.h, _ptr(P1), _ptr(s1), n1, p1, _ptr(P2), _ptr(s2), n2, p2, d, _ptr(hyp), _ptr(out),
+                                    _ld(out)), "dsvgp_kernel_fwd_rect")
+    return out
+
+
 def kernel_bwd_wide(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp, workspace=None):
     """kernel_bwd on the wide-input kernels whatever d (see kernel_fwd_wide)"""
     P1, s1, vn1 = pack1

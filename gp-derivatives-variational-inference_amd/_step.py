@@ -353,6 +353,36 @@ class ElboEngine:
         raise NotPSDError("Matrix not positive definite after repeatedly adding jitter up to %.1e."
                           % (self.chol_jitter * 10 ** (CHOL_TRIES - 1)))
 
+    @staticmethod
+    def _direction_counts(params, x, D, shared=False):
+        """(p, pd): directions per inducing point of the model and per data point of this call (``D`` None or empty: 0).
+        ``shared``: ``params`` holds the p directions of the shared-directions variant once, not M times."""
+        M = params["inducing_points"].shape[0]
+        nv = params["inducing_directions"].shape[0]
+        p = nv if shared else (nv // M if M else 0)
+        if D is None or D.numel() == 0:
+            return p, 0
+        B, d = x.shape[0], x.shape[-1]
+        if D.dim() != 2 or D.shape[1] != d or B == 0 or D.shape[0] % B:
+            raise ValueError("derivative directions must be [B * pd, d] = [%d * pd, %d], got %s" % (B, d, tuple(D.shape)))
+        return p, D.shape[0] // B
+
+    def _rect_pd(self, params, x, D, shared=False):
+        """None when the call carries the model's own number of directions per data point (the path of the training step);
+        else pd, the number it carries (predictions only: K_ZX from the rectangular assembly, csrc/assemble_rect.hip)"""
+        p, pd = self._direction_counts(params, x, D, shared)
+        if pd == p:
+            return None
+        if pd > 95:
+            raise ValueError("at most 95 derivative directions per data point, got %d" % pd)
+        if self.whitening == "ciq":
+            raise ValueError("CIQ whitening predicts with the model's own number of directions per data point (%d), got %d: "
+                             "the msMINRES solves run on the square (p + 1)-block K_XZ only" % (p, pd))
+        if self.data_outputs == "values" and pd > 0:
+            raise ValueError("derivative-free data (data_outputs == 'values') carries function values only: pass no directions "
+                             "(or the model's own %d per point, which are ignored), got %d per point" % (p, pd))
+        return pd
+
     def _pd(self, p):
         """directional derivatives per DATA point"""
         return 0 if self.data_outputs == "values" else p
@@ -413,15 +443,21 @@ class ElboEngine:
             _ops.kernel_bwd(ctx, Kb32, packZ, M, packX, B, d, p, hyp, False, dZ, dV, d_hyp, kws)
         self._event_done("assemble_bwd", ev)
 
-    def _interp(self, ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=False):
-        """K_ZX, A = L^-1 K_ZX (fp64 + fp32 copy), W = L_S^T A, mu, var."""
+    def _interp(self, ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=False, rect_pd=None):
+        """K_ZX, A = L^-1 K_ZX (fp64 + fp32 copy), W = L_S^T A, mu, var.  ``rect_pd`` (predictions): the data carry that many
+        directions per point instead of the model's p -- the data pack and K_ZX [M', B (rect_pd + 1)] are made for it."""
         M, d, p, Mp = dims
         B = x.shape[0]
-        pd = self._pd(p)
+        pd = self._pd(p) if rect_pd is None else rect_pd
         Bp = B * (pd + 1)
-        packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if p > 0 else None, p, hyp, self.center)
-        self._zx_dirs = _ops.stated_directions(D, d, p) if p > 0 else None
-        Kzx = self._assemble_kzx(ctx, packZ, M, packX, B, d, p, hyp, Mp)
+        if rect_pd is None:
+            packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if p > 0 else None, p, hyp, self.center)
+            self._zx_dirs = _ops.stated_directions(D, d, p) if p > 0 else None
+            Kzx = self._assemble_kzx(ctx, packZ, M, packX, B, d, p, hyp, Mp)
+        else:
+            packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, hyp, self.center)
+            self._zx_dirs = None
+            Kzx = _ops.kernel_fwd_rect(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, Bp), f32))
         A64 = self._get("A64", (Mp, Bp), f64)
         A32 = self._get("A32", (Mp, Bp), f32)
         need = _lib.lib.dsvgp_trsm_workspace_bytes(Mp, max(Bp, Mp), self.trsm_nb)
@@ -456,6 +492,7 @@ class ElboEngine:
         parameters are unchanged, like the reference's ``@cached`` ``_cholesky_factor`` (DGVS.py:72)."""
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
+            self._rect_pd(params, x, D)                 # (refuses a direction count other than the model's)
             _, _, mu, varn = self._ciq_step(ctx, params, x, None, D, 1.0, "ELBO", None, False, False)
             return mu, varn
         if self.shared_directions:
@@ -513,6 +550,7 @@ class ElboEngine:
         if self.whitening == "ciq":
             # NGD-CIQ: the reference's q(f) carries a DIAGONAL covariance, DiagLazyTensor(predictive_var) (CiqDGVS.py:264-267);
             # the likelihood adds its noise on that diagonal -- joint samples are independent draws
+            self._rect_pd(params, x, D)
             _, _, mu, varn = self._ciq_step(ctx, params, x, None, D, 1.0, "ELBO", None, False, False)
             return mu, torch.diag(varn)
         if self.shared_directions:
@@ -624,6 +662,9 @@ class ElboEngine:
         return out.t().to(mu.dtype) + mu
 
     def _predict_chol(self, ctx, params, x, D, cache, joint=False):
+        # (the parameters arrive expanded; the evaluation cache below is keyed on them alone: calls with different direction
+        #  counts on an unchanged model share the factor)
+        rect_pd = self._rect_pd(params, x, D)
         key = tuple((t.data_ptr(), t._version) for t in params.values()) if cache else None
         hit = cache and self._eval_cache is not None and self._eval_cache[0] == key
         if "natural_vec" in params:
@@ -638,14 +679,16 @@ class ElboEngine:
         else:
             Mz = params["inducing_points"].shape[0]
             pz = params["inducing_directions"].shape[0] // Mz if Mz else 0
-            hyp, packZ, L, dims = self._factor(ctx, params, nrhs=x.shape[0] * (self._pd(pz) + 1))
+            hyp, packZ, L, dims = self._factor(ctx, params, nrhs=x.shape[0] * ((self._pd(pz) if rect_pd is None else rect_pd) + 1))
             self._eval_cache = (key, hyp, packZ, L, dims, params) if cache else None
-        packX, _, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=hit)
+        packX, _, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=hit, rect_pd=rect_pd)
         if joint:
             M, d, p, Mp = dims
             B = x.shape[0]
+            if rect_pd is not None:
+                p = rect_pd                                                        # (the data pack was made with it)
             Sigma = _ops.kernel_fwd(ctx, packX, B, packX, B, d, p, hyp)            # s K(X, X; D, D), all (p+1)^2 blocks
-            if self.data_outputs == "values" and p > 0:
+            if rect_pd is None and self.data_outputs == "values" and p > 0:
                 Sigma = Sigma[::p + 1, ::p + 1].contiguous()
             if not self._no_middle:
                 _ops.gemm(ctx, TRANS_A, W, W, Sigma, beta=1.0, Cin=Sigma)          # + W^T W

@@ -65,6 +65,14 @@ class ElboEngine64(ElboEngine):
         if self.whitening != "cholesky":
             raise NotImplementedError("fp64 model mode: whitening must be 'cholesky' here (CIQ goes through _ciq_step64)")
 
+    def _refuse_rect(self, params, x, D):
+        """float64 models predict with the model's own number of directions per data point: the rectangular assembly
+        (csrc/assemble_rect.hip, ElboEngine.predict) is a float32 kernel"""
+        p, pd = self._direction_counts(params, x, D, self.shared_directions)
+        if pd != p:
+            raise ValueError("float64 model mode predicts with the model's own number of directions per data point (%d), got %d: "
+                             "the rectangular kernel assembly is built in float32 only" % (p, pd))
+
     def _hyp64(self, params):
         """(raw values, hyp[4] = {lengthscale, outputscale, noise, 0}): gpytorch Positive / GreaterThan(1e-4) softplus constraints"""
         raw = [params[k].detach().reshape(()) for k in ("raw_lengthscale", "raw_outputscale", "raw_noise")]
@@ -347,6 +355,7 @@ class ElboEngine64(ElboEngine):
 
     @torch.no_grad()
     def predict(self, params, x, D, cache=False):
+        self._refuse_rect(params, x, D)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
             _, _, mu, varn = self._ciq_step64(ctx, params, x, None, D, 1.0, "ELBO", None, False, False)
@@ -372,6 +381,7 @@ class ElboEngine64(ElboEngine):
     def predict_joint(self, params, x, D, cache=False):
         """Mean [B'] and the full predictive covariance [B', B'] (fp64, likelihood noise on the diagonal):
         Sigma = s K_XX + 1e-4 I + W^T W - A^T A + noise I  (DGVS.py:199-208 + likelihood)"""
+        self._refuse_rect(params, x, D)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
             # NGD-CIQ: the reference's q(f) carries a DIAGONAL covariance (CiqDGVS.py:264-267), see ElboEngine.predict_joint

@@ -664,3 +664,27 @@ def eval_mean(test_dataset, model, num_directions=1, minibatch_size=1, minibatch
             derivative_directions = derivative_directions.repeat(len(x_batch), 1)
             means.append(model.posterior_mean(x_batch, derivative_directions=derivative_directions).cpu())
     return torch.cat(means) if means else torch.zeros(0)
+
+
+def eval_values(test_dataset, model, likelihood, minibatch_size=1):
+    """``eval_gp(...)`` followed by ``[::p+1]``: predictive means / variances (with likelihood noise) of the FUNCTION VALUES,
+    what the reference's callers keep of it (tests/test_dsvgp.py:99-101, the experiments' MSE / NLL reports).  Same batching and
+    noise handling as ``eval_gp``, CPU vectors of length N_test -- through ``model.posterior(x)``: K_ZX, the solve and W are
+    formed for B columns per batch instead of B(p+1)."""
+    device = model.variational_strategy.inducing_points.device
+    X, _ = _dataset_tensors(test_dataset, device, model.variational_strategy.inducing_points.dtype)
+    n_test = X.shape[0]
+
+    model.eval()
+    likelihood.eval()
+
+    means = []
+    variances = []
+    with torch.no_grad():
+        for start in range(0, n_test, minibatch_size):
+            preds = model.posterior(X[start:start + minibatch_size], likelihood=likelihood)
+            means.append(preds.mean.cpu())
+            variances.append(preds.variance.cpu())
+    means = torch.cat(means) if means else torch.zeros(0)
+    variances = torch.cat(variances) if variances else torch.zeros(0)
+    return means, variances

@@ -348,6 +348,32 @@ class ApproximateGP(torch.nn.Module):
             x = x.unsqueeze(-1)
         return self._mean_predictor().value_and_gradient(x)[1]
 
+    def posterior(self, x, derivative_directions=None, likelihood=None):
+        """Predictive distribution at x [B, d] over B (pd + 1) interleaved outputs, pd = len(derivative_directions) // B ANY
+        number of directions per point up to 95 (``None``: the B function values; ``eye(d)`` tiled: values and full gradients),
+        whatever number p the model was trained with.  ``likelihood`` given: with its noise, as ``likelihood(self(x, ...))``;
+        else q(f), as ``self(x, ...)``.  With pd == p it IS that distribution (``self(x, derivative_directions=D)`` keeps the
+        reference's assertion on a count mismatch); otherwise K_ZX comes from the rectangular assembly
+        (``ElboEngine.predict``: float32 Cholesky-whitened models).  ``mean``, ``variance``, ``stddev``, ``confidence_region``,
+        ``covariance_matrix``, ``rsample`` and ``sample`` work; ``value_variance`` is ``variance[::pd + 1]``."""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        vs = self.variational_strategy
+        if hasattr(vs, "_strategy_is_updated") and not vs._strategy_is_updated():
+            vs._whiten_legacy_parameters()
+        if self.training and hasattr(vs, "_maybe_init"):
+            vs._maybe_init()
+        D = derivative_directions
+        if D is not None:
+            D = D.to(x.device)
+            if D.numel() and (D.dim() != 2 or x.shape[0] == 0 or D.shape[0] % x.shape[0] or D.shape[1] != x.shape[1]):
+                raise ValueError("derivative_directions must be [B * pd, d] = [%d * pd, %d], got %s"
+                                 % (x.shape[0], x.shape[1], tuple(D.shape)))
+        out = PredictiveDistribution(self, x, D, likelihood)
+        pd = D.shape[0] // x.shape[0] if D is not None and D.numel() else 0
+        out._value_stride = 1 if getattr(vs, "data_outputs", "all") == "values" else pd + 1     # (derivative-free data: B outputs)
+        return out
+
     def __call__(self, inputs, prior=False, **kwargs):
         if inputs.dim() == 1:
             inputs = inputs.unsqueeze(-1)

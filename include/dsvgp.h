@@ -132,6 +132,20 @@ int dsvgp_kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_d
                           const float* self1, const float* vnorm1, int n1, const float* P2,
                           const float* self2, int n2, int d, int p, const float* hyp, int symmetric,
                           float* d_x1, float* d_v1, float* d_hyp, void* workspace);
+/* Rectangular assembly (csrc/assemble_rect.hip): the two sides carry DIFFERENT numbers of directions.
+ *   out[n1*(p1+1), n2*(p2+1)] (float, leading dimension ld >= n2*(p2+1)) = hyp.outputscale * K(x1, x2; v1, v2), interleaved as
+ *   dsvgp_kernel_fwd: micro-block (i, j) is k [[1, w_b/ell], [-u_a/ell, (G_ab - u_a w_b)/ell^2]] for a = 1..p1, b = 1..p2, with
+ *   r = (x1_i - x2_j)/ell, k = exp(-|r|^2/2), u_a = r.v1_ia, w_b = r.v2_jb, G_ab = v1_ia.v2_jb (unit directions).
+ * P1 / self1 and P2 / self2: what dsvgp_pack_points wrote for each side WITH THAT SIDE'S OWN p and the same center; p = 0 on a
+ * side: value rows only.  Forward only, float output, no jitter.  Any d >= 1 (the workgroup's LDS does not depend on d) and any
+ * 0 <= p1, p2 <= 95, independently.  One launch, no intermediate in device memory, every element stored once, no atomics: two
+ * identical calls give bitwise equal results; at p1 == p2 the arithmetic is that of dsvgp_kernel_fwd_wide.
+ * Alignment: P1 and P2 must be 16-byte aligned (their rows, dsvgp_packed_width(d) floats, are read 16 bytes at a time); `out` and
+ * `ld` carry no requirement beyond ld >= n2*(p2+1) (element-wise stores).
+ * DSVGP_EINVAL: a null pointer, n1 <= 0 or n2 <= 0, d < 1, p1 or p2 outside [0, 95], n*(p+1) beyond INT_MAX on a side, more than
+ * 65535 row tiles (n1*(p1+1) above ~3.1e6 at the 48-row tile), ld too small, P1 or P2 misaligned.                                */
+int dsvgp_kernel_fwd_rect(dsvgp_ctx* ctx, const float* P1, const float* self1, int n1, int p1, const float* P2,
+                          const float* self2, int n2, int p2, int d, const float* hyp, float* out, int64_t ld);
 /* 1 when dsvgp_kernel_fwd_canon / _bwd_canon take the geometry (d, p), 0 otherwise */
 int dsvgp_kernel_canon_supported(int d, int p);
 /* backward of dsvgp_kernel_fwd_canon (symmetric = 0 semantics; same workspace size as dsvgp_kernel_bwd) */
