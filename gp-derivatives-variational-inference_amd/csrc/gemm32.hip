@@ -13,6 +13,7 @@
 // of a pair then cover k0 .. k0 + 3 in the order {0, 2}, {1, 3} -- any order is fine as long as both operands use the same.
 // An mn-contiguous operand sits as [BK][128 + 4] and is read with two 4-byte reads at rows k0 + 2h, k0 + 2h + 1.
 // Staging stores: 8-byte stores for the k-contiguous image (rows are 8-byte aligned), 16-byte for the other.
+#include <cstdlib>
 #include <type_traits>
 
 #include "common.h"
@@ -43,6 +44,12 @@ constexpr int TM = 128, TN = 128;
 #endif
 #ifndef G32_SK_MINK
 #define G32_SK_MINK 512     // shortest K that may be split (slices of >= 256)
+#endif
+#ifndef G32_WIDE_ROUNDS
+#define G32_WIDE_ROUNDS 3   // the 256 x 192 kernel is chosen from this many rounds of 256 x 192 tiles over the CUs on ...
+#endif
+#ifndef G32_WIDE_FILL
+#define G32_WIDE_FILL 90    // ... when the tiles fill their rounds to this many per cent
 #endif
 #ifndef G32_SK_SLOTS
 #define G32_SK_SLOTS 256    // work units per round in the split-K cost model: one per CU (a CU's matrix pipe is shared by its resident workgroups)
@@ -122,6 +129,7 @@ struct FetchMC {
 // Tried and removed (build-variant clean-up; last present in 8a953b7): the lower triangle walked in SB x SB super-blocks (G32_TRI_SB; round 4,
 // same box: Gram at C4 2.169 (1) / 2.193 (8) / 2.222 ms (4) -- no gain); lower-triangular split-K products in eight K slices, one per XCD
 // (G32_XCDK; round 6, profiles/r06_b_gemm32_gram_xcd.txt: 2.29 -> 2.33-2.35 ms, the launch is not bound by its traffic).
+template <int TM_ = TM, int TN_ = TN>
 __device__ __forceinline__ bool pick_unit(const G32& g, int& m0, int& n0, int& kbeg, int& kend) {
     const int u = (blockIdx.x >> 3) + (blockIdx.x & 7) * ((gridDim.x + 7) >> 3);
     if (u >= g.ntiles * g.splitk) return false;
@@ -147,23 +155,24 @@ __device__ __forceinline__ bool pick_unit(const G32& g, int& m0, int& n0, int& k
         tm = q / wcols;
         tn = band * G32_BAND + q - tm * wcols;
     }
-    m0 = tm * TM; n0 = tn * TN;
+    m0 = tm * TM_; n0 = tn * TN_;
     kbeg = slice * g.kslice; kend = min(g.K, kbeg + g.kslice);
     return true;
 }
 
 // C/D layout of the 32 x 32 MFMA: col = lane & 31, row = (c & 3) + 8 (c >> 2) + 4 (lane >> 5)
-__device__ __forceinline__ void store_tile(const G32& g, const acc16 (&acc)[2][2], int m0, int n0, int wr, int wc, int h, int r,
+template <int NI, int NJ>
+__device__ __forceinline__ void store_tile(const G32& g, const acc16 (&acc)[NI][NJ], int m0, int n0, int wr, int wc, int h, int r,
                                            float* Cb, int64_t ldcb, bool atomic_) {
     const bool atomic = atomic_, out_lower = g.flags & DSVGP_GEMM_OUT_LOWER;
 #pragma unroll
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < NI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < NJ; ++j)
 #pragma unroll
             for (int c = 0; c < 16; ++c) {
-                const int m = m0 + wr * 64 + i * 32 + (c & 3) + 8 * (c >> 2) + 4 * h;
-                const int n = n0 + wc * 64 + j * 32 + r;
+                const int m = m0 + wr * (32 * NI) + i * 32 + (c & 3) + 8 * (c >> 2) + 4 * h;
+                const int n = n0 + wc * (32 * NJ) + j * 32 + r;
                 if (m >= g.M || n >= g.N) continue;
                 if (out_lower && n > m) continue;                // (the caller zero-fills m < n)
                 const float v = g.alpha * acc[i][j][c];
@@ -502,6 +511,157 @@ __global__ __launch_bounds__(256, BK == 16 ? 3 : 2) void gemm32_dma_kernel(const
     }
 }
 
+// -------------------------------------------------------------------------------------------------
+// Large plain dense products (K_ZX-bar at C4: 12 x 128 tiles = six rounds of the 256 CUs): 256 x 192 output tiles, ONE workgroup
+// per CU, one wave per SIMD.  Waves 2 x 2, each 128 x 96 = 4 x 3 tiles of v_mfma_f32_32x32x2_f32 (192 accumulator registers): 7
+// fragment registers feed 12 MFMAs (the 64 x 64 wave tile above: 4 feed 4) and a stage brings in 448 bytes per output row + column
+// pair of 256 + 192 where two 128 x 128 tiles bring in 512.  Left operand k-contiguous, right operand n-contiguous, no split-K.
+// Stages: the same two LDS images as gemm32_dma_kernel<32, true, false, 32> -- [256 rows][32 k] with chunk c of row R at position
+// c ^ ((R >> 1) & 7) and [32 k][192] linear -- 56 KB per stage, two buffers (dynamic LDS, 112 KB).  Per stage a wave issues 14 DMA
+// instructions (8 + 6 pieces of 1 KB; a piece of the right image is 64 consecutive 16-byte chunks = 1 1/3 rows of 48).
+// With one wave per SIMD nothing hides a stall, so the wave's instruction stream is laid out by hand (sched_barrier(0) fences: an
+// asm statement belongs to no sched_group_barrier class): after every second MFMA ONE other item -- a DMA instruction of the
+// next stage (5 / 5 / 4 in k-groups 0 / 1 / 2: they have the rest of the stage to land) or a fragment read of k-group j + 1 (4
+// 16-byte reads of the left image, 6 pairs of 4-byte reads of the right) -- so that the matrix pipe always has its next MFMA
+// before the current one (16 passes) retires.  One vmcnt(0) and one barrier per stage; no branch inside a stage: the stage that
+// issues the DMA crossing K (zero chunk selects) and the last one (no DMA) are copies of their own.
+// Arithmetic: each output element meets k in the same order as in gemm32_dma_kernel<32, true, false, 32> (stage by stage, MFMA e of
+// chunk pair j takes k = 8 j + 4 h + e) -- the two kernels return the same bits.
+// -------------------------------------------------------------------------------------------------
+constexpr int WTM = 256, WTN = 192, WBK = 32;
+constexpr int W_AWORDS = WTM * WBK, W_BWORDS = WBK * WTN, W_STAGE = W_AWORDS + W_BWORDS;      // 8192 + 6144 words = 56 KB
+constexpr int W_NA = W_AWORDS / 1024, W_NB = W_BWORDS / 1024;                                  // 1 KB pieces per wave and stage: 8 + 6
+constexpr int W_LDS_BYTES = 2 * W_STAGE * 4;
+
+__global__ __launch_bounds__(256, 1) void gemm32_wide_kernel(const G32 g) {
+    extern __shared__ __attribute__((aligned(16))) float wlds[];        // [2][W_STAGE]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int h = lane >> 5, r = lane & 31;
+    int m0, n0, kbeg, kend;
+    if (!pick_unit<WTM, WTN>(g, m0, n0, kbeg, kend)) return;
+
+    // ---- DMA sources: piece i of wave w is the 1 KB block W_NA w + i (left image) / W_NB w + i (right image)
+    const float* asrc[W_NA];
+    const float* bsrc[W_NB];
+    int akk[W_NA], bkk[W_NB];                             // k of the lane's chunk / row inside a stage (for the K tail)
+    const int K4 = (g.K + 3) / 4 * 4;
+#pragma unroll
+    for (int i = 0; i < W_NA; ++i) {
+        const int R = (wave * W_NA + i) * 8 + (lane >> 3), c = (lane & 7) ^ ((R >> 1) & 7);
+        asrc[i] = g.A + (int64_t)min(m0 + R, g.M - 1) * g.lda + kbeg + 4 * c;
+        akk[i] = 4 * c;
+    }
+#pragma unroll
+    for (int i = 0; i < W_NB; ++i) {
+        const int ch = (wave * W_NB + i) * 64 + lane, k = ch / (WTN / 4), n4 = ch % (WTN / 4);
+        bsrc[i] = g.B + (int64_t)(kbeg + k) * g.ldb + min(n0 + 4 * n4, (g.N + 3) / 4 * 4 - 4);
+        bkk[i] = k;
+    }
+    const int64_t bstep = (int64_t)WBK * g.ldb;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)&wlds[0];
+    const unsigned wave_u = __builtin_amdgcn_readfirstlane(wave);
+
+    acc16 acc[4][3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+#pragma unroll
+            for (int c = 0; c < 16; ++c) acc[i][j][c] = 0.f;
+
+    // per-lane fragment offsets (words) inside the images; MFMA tile i adds 32 rows / columns, element e of the right image one row
+    const int q7 = h ^ ((r >> 1) & 7);
+    int aoff[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) aoff[j] = (wr * 128 + r) * WBK + 4 * ((2 * j) ^ q7);
+    const int boff = (4 * h) * WTN + wc * 96 + r;
+
+    // one stage: the MFMAs on buffer buf with, between them, the DMA of the stage at knext into the other buffer.
+    // MODE 0: no DMA (the last stage); 1: a whole stage; 2: the stage that may cross K (chunks / rows past it come from the zero chunk)
+    auto stage = [&](auto mode_, int buf, int knext) {
+        constexpr int MODE = decltype(mode_)::value;
+        const float* As = wlds + buf * W_STAGE;
+        const float* Bs = As + W_AWORDS;
+        const unsigned dst = lds_base + (unsigned)(buf ^ 1) * (W_STAGE * 4);      // byte address, wave-uniform
+        float fa[2][4][4], fb[2][3][4];                   // fragments of k-groups j (even / odd): plain arrays
+        auto rd_a = [&](int j, int i) {
+            const float4 v = *reinterpret_cast<const float4*>(As + aoff[j] + i * 32 * WBK);
+            fa[j & 1][i][0] = v.x; fa[j & 1][i][1] = v.y; fa[j & 1][i][2] = v.z; fa[j & 1][i][3] = v.w;
+        };
+        auto rd_b = [&](int j, int jn, int ep) {          // elements 2 ep, 2 ep + 1 of tile jn
+#pragma unroll
+            for (int e = 2 * ep; e < 2 * ep + 2; ++e) fb[j & 1][jn][e] = Bs[boff + (8 * j + e) * WTN + jn * 32];
+        };
+        auto dma1 = [&](int d) {                          // DMA instruction d of the stage: 0..7 left image, 8..13 right image
+            if (d < W_NA) {
+                const float* s = asrc[d];
+                if (MODE == 2) s = (knext + akk[d] >= K4) ? g32_zero_chunk : s;
+                lds_dma16(s, dst + (wave_u * W_NA + d) * 1024);
+                asrc[d] += WBK;
+            } else {
+                const int i = d - W_NA;
+                const float* s = bsrc[i];
+                if (MODE == 2) s = (knext + bkk[i] >= g.K) ? g32_zero_chunk : s;
+                lds_dma16(s, dst + W_AWORDS * 4 + (wave_u * W_NB + i) * 1024);
+                bsrc[i] += bstep;
+            }
+        };
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rd_a(0, i);
+#pragma unroll
+        for (int q = 0; q < 6; ++q) rd_b(0, q >> 1, q & 1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int nd = MODE == 0 ? 0 : (j < 2 ? 5 : (j == 2 ? 4 : 0)), d0 = j < 2 ? 5 * j : 10;
+#pragma unroll
+            for (int n = 0; n < 48; ++n) {
+                const int e = n / 12, i = (n / 3) % 4, jn = n % 3;
+                acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[j & 1][i][e], fb[j & 1][jn][e], acc[i][jn], 0, 0, 0);
+                if (n & 1) {
+                    const int t = n >> 1;
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (t < nd) {
+                        dma1(d0 + t);
+                    } else if (j < 3) {
+                        const int q = t - nd;
+                        if (q < 4) rd_a(j + 1, q);
+                        else if (q < 10) rd_b(j + 1, (q - 4) >> 1, (q - 4) & 1);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+        if (MODE != 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of the next stage has landed ...
+            __syncthreads();                                   // ... and every wave's; this buffer is free for stage + 2
+        }
+    };
+
+    if (kbeg < kend) {
+        const int nst = (kend - kbeg + WBK - 1) / WBK;
+        {   // stage 0 (tail-checked: it is also the last one when K <= 32)
+            const unsigned dst = lds_base;
+#pragma unroll
+            for (int i = 0; i < W_NA; ++i) {
+                lds_dma16((kbeg + akk[i] >= K4) ? g32_zero_chunk : asrc[i], dst + (wave_u * W_NA + i) * 1024);
+                asrc[i] += WBK;
+            }
+#pragma unroll
+            for (int i = 0; i < W_NB; ++i) {
+                lds_dma16((kbeg + bkk[i] >= g.K) ? g32_zero_chunk : bsrc[i], dst + W_AWORDS * 4 + (wave_u * W_NB + i) * 1024);
+                bsrc[i] += bstep;
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                   // stage 0 has landed for every wave
+        int buf = 0, k0 = kbeg + WBK;                      // k0: the stage whose DMA the next call issues
+        for (int s = 0; s + 2 < nst; ++s, buf ^= 1, k0 += WBK) stage(std::integral_constant<int, 1>{}, buf, k0);
+        if (nst >= 2) { stage(std::integral_constant<int, 2>{}, buf, k0); buf ^= 1; }
+        stage(std::integral_constant<int, 0>{}, buf, 0);
+    }
+    store_tile(g, acc, m0, n0, wr, wc, h, r, g.C, g.ldc, false);
+}
+
 template <int BK>
 int dispatch32(hipStream_t st, const G32& a, dim3 grid, bool akc, bool bkc) {
     if (akc && bkc) hipLaunchKernelGGL((gemm32_kernel<BK, true, true>), grid, dim3(256), 0, st, a);
@@ -558,6 +718,42 @@ int launch_gemm32(hipStream_t st, const GemmArgs& g) {
             if (tcost < best * 0.999) { best = tcost; sk = c; }
         }
     }
+    const bool akc = !(fl & DSVGP_GEMM_TRANS_A), bkc = (fl & DSVGP_GEMM_TRANS_B) != 0;
+    // LDS-DMA kernels: a k-contiguous operand needs K % 4 == 0 or caller-zeroed padding up to it (the chunk that straddles K
+    // is read as it lies in memory)
+    const bool dma_ok = !((akc || bkc) && g.K % 4 != 0 && !(g.flags & DSVGP_GEMM_K_PADDED));
+    // The 256 x 192 kernel (gemm32_wide_kernel) takes plain dense products with a k-contiguous left and an n-contiguous right operand,
+    // unsplit and outside deterministic mode.  The rule: the cost model above leaves K whole and the 256 x 192 tiles fill at least
+    // G32_WIDE_ROUNDS rounds of the CUs to G32_WIDE_FILL per cent (one workgroup per CU: a ragged last round idles whole CUs, and
+    // every tile pays its first stage and its epilogue in the open -- C3's 390 tiles = 1.5 rounds, the data-parallel shares' 192 and
+    // CIQ's split products stay on the 128 x 128 kernel).  DSVGP_G32_WIDE, read at every launch: 0 = never (the launch is the one of
+    // the 128 x 128 kernel alone); 1 = for every product it can take, K whole; 2 = as 1, and a product it cannot take is an error
+    // (hipErrorInvalidValue: how a test knows which kernel ran); -1 = the 128 x 128 kernel, K whole, for the products 1 would take (the bitwise
+    // reference of 1: split-K meets in atomics, in no fixed order); unset = the rule.
+    const char* wenv = getenv("DSVGP_G32_WIDE");
+    const int wmode = wenv ? atoi(wenv) : 3;
+    const bool wide_can = !out_lower && akc && !bkc && dma_ok && !g.slab;
+    bool wide = false;
+    if (wmode == 3) {
+        const int64_t wt = (int64_t)cdiv(g.M, WTM) * cdiv(g.N, WTN), rounds = (wt + G32_SK_SLOTS - 1) / G32_SK_SLOTS;
+        wide = wide_can && sk == 1 && wt >= (int64_t)G32_WIDE_ROUNDS * G32_SK_SLOTS && wt * 100 >= rounds * G32_SK_SLOTS * G32_WIDE_FILL;
+    } else if (wmode != 0) {
+        if (wmode == 2 && !wide_can) return 1000 + (int)hipErrorInvalidValue;
+        if (wide_can) sk = 1;
+        wide = wide_can && wmode > 0;
+    }
+    if (wide) {
+        a.tiles_m = cdiv(g.M, WTM); a.tiles_n = cdiv(g.N, WTN);
+        a.ntiles = a.tiles_m * a.tiles_n;
+        a.splitk = 1;
+        a.kslice = cdiv(g.K, 32) * 32;
+        // per call: the attribute belongs to the CURRENT device's copy of the kernel; a host-side table write, no device work
+        hipError_t e = hipFuncSetAttribute((const void*)gemm32_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, W_LDS_BYTES);
+        if (e != hipSuccess) return 1000 + (int)e;
+        hipLaunchKernelGGL(gemm32_wide_kernel, dim3(cdiv(a.ntiles, 8) * 8), dim3(256), W_LDS_BYTES, st, a);
+        e = hipGetLastError();
+        return e == hipSuccess ? 1 : 1000 + (int)e;
+    }
     sk = slab_slices(g, sk, sizeof(float));         // deterministic mode: as many slices as the caller's scratch holds
     a.splitk = sk;
     a.kslice = cdiv(cdiv(g.K, sk), 32) * 32;
@@ -570,10 +766,7 @@ int launch_gemm32(hipStream_t st, const GemmArgs& g) {
         if (e != hipSuccess) return 1000 + (int)e;
     }
     const dim3 grid(cdiv((int64_t)a.ntiles * a.splitk, 8) * 8);
-    const bool akc = !(fl & DSVGP_GEMM_TRANS_A), bkc = (fl & DSVGP_GEMM_TRANS_B) != 0;
-    // LDS-DMA kernel: a k-contiguous operand needs K % 4 == 0 or caller-zeroed padding up to it (the chunk that straddles K
-    // is read as it lies in memory)
-    if (!((akc || bkc) && g.K % 4 != 0 && !(g.flags & DSVGP_GEMM_K_PADDED))) {
+    if (dma_ok) {
         if (akc && bkc) hipLaunchKernelGGL((gemm32_dma_kernel<G32_MF, true, true, G32_DMA_BK>), grid, dim3(256), 0, st, a);
         else if (akc) hipLaunchKernelGGL((gemm32_dma_kernel<G32_MF, true, false, G32_DMA_BK>), grid, dim3(256), 0, st, a);
         else if (bkc) hipLaunchKernelGGL((gemm32_dma_kernel<G32_MF, false, true, G32_DMA_BK>), grid, dim3(256), 0, st, a);

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include "common.h"
 
@@ -44,6 +45,9 @@ int main(int argc, char** argv) {
         {"C4/8 Gram  K=3072                                    ", TB | OL, 3001, 3000, 3072, 3072, 3072, 1.0 * 3001 * 3000 * 3072.0},
         {"C3 dense  [3300x3301]x[3301x5632]                    ", 0, 3300, 5632, 3301, 3304, 5632, 2.0 * 3300 * 3301 * 5632.0},
         {"C3 Gram   K=5632                                     ", TB | OL, 3301, 3300, 5632, 5632, 5632, 1.0 * 3301 * 3300 * 5632.0},
+        {"rule      [3000x3001]x[3001x12288] (768 wide tiles)   ", 0, 3000, 12288, 3001, 3004, 12288, 2.0 * 3000 * 3001 * 12288.0},
+        {"rule      [3000x3001]x[3001x8192]  (516 wide tiles)   ", 0, 3000, 8192, 3001, 3004, 8192, 2.0 * 3000 * 3001 * 8192.0},
+        {"rule      [3000x3001]x[3001x16384] (1032 wide tiles)  ", 0, 3000, 16384, 3001, 3004, 16384, 2.0 * 3000 * 3001 * 16384.0},
         {"odd       M=700 N=1100 K=1300 (ragged everything)    ", 0, 700, 1100, 1300, 1300, 1100, 2.0 * 700 * 1100 * 1300.0},
         {"odd TT    M=700 N=1100 K=1300                        ", TA | TB, 700, 1100, 1300, 700, 1300, 2.0 * 700 * 1100 * 1300.0},
     };
@@ -74,6 +78,31 @@ int main(int argc, char** argv) {
             CK(hipEventElapsedTime(&ms_mine, e0, e1)); ms_mine /= n;
         }
         if (rc != 1) { printf("%s  launch_gemm32 rc=%d (not taken)\n", c.name, rc); continue; }
+        // the 256 x 192 kernel (DSVGP_G32_WIDE=1) against the 128 x 128 one with K whole (-1) on the products it takes: time and bits
+        if (!ta && !tb && !ol && !getenv("DSVGP_G32_WIDE")) {
+            std::vector<float> out[2];
+            float ms_w[2] = {0.f, 0.f};
+            const char* modes[2] = {"-1", "1"};
+            for (int w = 0; w < 2; ++w) {
+                setenv("DSVGP_G32_WIDE", modes[w], 1);
+                for (int rep = 0; rep < 2; ++rep) {
+                    CK(hipEventRecord(e0, st));
+                    const int n = rep ? reps : 1;
+                    for (int i = 0; i < n; ++i) rc = launch_gemm32(st, g);
+                    CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
+                    CK(hipEventElapsedTime(&ms_w[w], e0, e1)); ms_w[w] /= n;
+                }
+                out[w].resize(nc);
+                CK(hipMemcpy(out[w].data(), C, nc * 4, hipMemcpyDeviceToHost));
+            }
+            unsetenv("DSVGP_G32_WIDE");
+            size_t diff = 0;
+            for (size_t i = 0; i < nc; ++i) diff += memcmp(&out[0][i], &out[1][i], 4) != 0;
+            printf("    128x128 K whole %8.3f ms %7.2f TF | 256x192 %8.3f ms %7.2f TF | %zu of %zu elements differ in bits\n", ms_w[0],
+                   c.flops / ms_w[0] / 1e9, ms_w[1], c.flops / ms_w[1] / 1e9, diff, nc);
+            rc = launch_gemm32(st, g);      // (the rule's own choice again, for the comparison below)
+            CK(hipStreamSynchronize(st));
+        }
         // reference: row-major C = op(A) op(B)  <=>  column-major C^T = op(B)^T op(A)^T
         const float alpha = 0.75f, beta = 0.f;
         for (int rep = 0; rep < 2; ++rep) {
