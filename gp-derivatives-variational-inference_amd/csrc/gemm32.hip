@@ -17,6 +17,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "gram_walk.h"
 
 namespace {
 
@@ -50,6 +51,15 @@ constexpr int TM = 128, TN = 128;
 #endif
 #ifndef G32_WIDE_FILL
 #define G32_WIDE_FILL 90    // ... when the tiles fill their rounds to this many per cent
+#endif
+#ifndef G32_GRAM_STAGES
+#define G32_GRAM_STAGES 160 // the 256 x 256 stream-K kernel is chosen for lower k-contiguous products from this many stages per workgroup on (C4: 234; the 2-rank share: 117)
+#endif
+#ifndef G32_GRAM_INFLIGHT
+#define G32_GRAM_INFLIGHT 16 // atomics of a wave's earlier MFMA tiles that may be in flight when it issues the next tile's 16 (0..62; 63 = uncounted)
+#endif
+#ifndef G32_GRAM_KCHUNKS
+#define G32_GRAM_KCHUNKS 1  // K chunks of the stream-K walk (gram_walk.h); DSVGP_G32_GRAM_KCHUNKS overrides it at a launch
 #endif
 #ifndef G32_SK_SLOTS
 #define G32_SK_SLOTS 256    // work units per round in the split-K cost model: one per CU (a CU's matrix pipe is shared by its resident workgroups)
@@ -662,6 +672,181 @@ __global__ __launch_bounds__(256, 1) void gemm32_wide_kernel(const G32 g) {
     store_tile(g, acc, m0, n0, wr, wc, h, r, g.C, g.ldc, false);
 }
 
+// -------------------------------------------------------------------------------------------------
+// Lower-triangular products of two k-contiguous operands with a long K (the Gram product [G ; b^T] = tril([A ; mu_bar^T] A^T) at C4:
+// 3001 x 3000 x 24576): 256 x 256 output tiles, ONE workgroup per CU, one wave per SIMD, and a stream-K walk in place of split-K.
+// Waves 2 x 2, each 128 x 128 = 4 x 4 tiles of v_mfma_f32_32x32x2_f32 (256 accumulator registers): 8 fragment registers feed 16 MFMAs.
+// Stages: two images [256 rows][32 k] with chunk c of row R at position c ^ ((R >> 1) & 7) (the k-contiguous image of the kernels
+// above), 64 KB per stage, two buffers (dynamic LDS, 128 KB).  Per stage a wave issues 16 DMA instructions (8 + 8 pieces of 1 KB) and,
+// per k-group of 8 k, 8 fragment reads of 16 bytes for 64 MFMAs.  The stage is laid out like the one of gemm32_wide_kernel: after every
+// second MFMA ONE other item -- a DMA instruction of the next stage (6 / 5 / 5 in k-groups 0 / 1 / 2) or a fragment read of k-group
+// j + 1 --, one vmcnt(0) and one barrier per stage, no branch inside a stage; the stage whose DMA may cross K and the last stage of a
+// unit are copies of their own.
+// Work: the 256 x 256 tiles of the lower triangle (78 at M' = 3000: 13.4 % of their outputs are dead, against 9.2 % on 128 x 128
+// tiles) cannot be cut evenly over the CUs by any uniform K split, so every workgroup walks an equal, contiguous share of the
+// (tile, stage) sequence (gram_walk.h) and adds its accumulators into C -- atomics onto zeros, as the split-K launch does -- whenever
+// its share leaves a tile and at its end.  A share may start and end mid-tile and, when K is short, span several tiles.
+// Epilogue: 256 atomic instructions per wave, each 2 x 128 contiguous bytes; at most 32 of a wave are in flight (a counted vmcnt
+// after every MFMA tile's 16), which is where the issue of float atomics stalls anyway.
+// -------------------------------------------------------------------------------------------------
+constexpr int GT = 256, GBK = 32;
+constexpr int G_OPWORDS = GT * GBK, G_STAGE = 2 * G_OPWORDS;                                   // 2 x 8192 words = 64 KB
+constexpr int G_NP = G_OPWORDS / 1024;                                                         // 1 KB pieces per operand, wave and stage: 8
+constexpr int G_LDS_BYTES = 2 * G_STAGE * 4;
+
+struct G32Gram {
+    const float* A; const float* B; float* C;
+    int64_t lda, ldb, ldc;
+    int M, N, K, nwg;
+    float alpha;
+    GramWalk walk;
+};
+
+__global__ __launch_bounds__(256, 1) void gemm32_gram_kernel(const G32Gram g) {
+    extern __shared__ __attribute__((aligned(16))) float glds[];        // [2][G_STAGE]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave >> 1, wc = wave & 1;
+    const int h = lane >> 5, r = lane & 31;
+    const int wg = gram_walk_wg(blockIdx.x, gridDim.x);
+    if (wg >= g.nwg) return;
+    long long gi, gend;
+    gram_walk_range(g.walk, wg, g.nwg, gi, gend);
+
+    const int K4 = (g.K + 3) / 4 * 4;
+    const unsigned lds_base = (unsigned)(uintptr_t)(lds_ptr_t)&glds[0];
+    const unsigned wave_u = __builtin_amdgcn_readfirstlane(wave);
+    // per-lane fragment offsets (words) inside an image; MFMA tile i adds 32 rows
+    const int q7 = h ^ ((r >> 1) & 7);
+    int aoff[4], boff[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        aoff[j] = (wr * 128 + r) * GBK + 4 * ((2 * j) ^ q7);
+        boff[j] = (wc * 128 + r) * GBK + 4 * ((2 * j) ^ q7);
+    }
+    // DMA: piece i of wave w is the 1 KB block 8 w + i of either image -- rows 8 (8 w + i) .. + 7, lane -> (row, swizzled chunk)
+    int drow[G_NP], dkk[G_NP];
+#pragma unroll
+    for (int i = 0; i < G_NP; ++i) {
+        drow[i] = (wave * G_NP + i) * 8 + (lane >> 3);
+        dkk[i] = 4 * ((lane & 7) ^ ((drow[i] >> 1) & 7));
+    }
+
+    while (gi < gend) {                                    // one unit: stages [s0, s1) of one tile into one accumulator set
+        const GramUnit u = gram_walk_unit(g.walk, gi, gend);
+        gi += u.s1 - u.s0;
+        const int m0 = u.tm * GT, n0 = u.tn * GT, nst = u.s1 - u.s0, kbeg = u.s0 * GBK;
+        const float* asrc[G_NP];
+        const float* bsrc[G_NP];
+#pragma unroll
+        for (int i = 0; i < G_NP; ++i) {
+            asrc[i] = g.A + (int64_t)min(m0 + drow[i], g.M - 1) * g.lda + kbeg + dkk[i];
+            bsrc[i] = g.B + (int64_t)min(n0 + drow[i], g.N - 1) * g.ldb + kbeg + dkk[i];
+        }
+        acc16 acc[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int c = 0; c < 16; ++c) acc[i][j][c] = 0.f;
+
+        // one stage: the MFMAs on buffer buf with, between them, the DMA of the stage at knext into the other buffer.
+        // MODE 0: no DMA (the last stage of the unit); 1: a whole stage; 2: the stage that may cross K (chunks past it come from the zero chunk)
+        auto stage = [&](auto mode_, int buf, int knext) {
+            constexpr int MODE = decltype(mode_)::value;
+            const float* As = glds + buf * G_STAGE;
+            const float* Bs = As + G_OPWORDS;
+            const unsigned dst = lds_base + (unsigned)(buf ^ 1) * (G_STAGE * 4);      // byte address, wave-uniform
+            float fa[2][4][4], fb[2][4][4];                   // fragments of k-groups j (even / odd): plain arrays
+            auto rd_a = [&](int j, int i) {
+                const float4 v = *reinterpret_cast<const float4*>(As + aoff[j] + i * 32 * GBK);
+                fa[j & 1][i][0] = v.x; fa[j & 1][i][1] = v.y; fa[j & 1][i][2] = v.z; fa[j & 1][i][3] = v.w;
+            };
+            auto rd_b = [&](int j, int i) {
+                const float4 v = *reinterpret_cast<const float4*>(Bs + boff[j] + i * 32 * GBK);
+                fb[j & 1][i][0] = v.x; fb[j & 1][i][1] = v.y; fb[j & 1][i][2] = v.z; fb[j & 1][i][3] = v.w;
+            };
+            auto dma1 = [&](int d) {                          // DMA instruction d of the stage: 0..7 left image, 8..15 right image
+                if (d < G_NP) {
+                    const float* s = asrc[d];
+                    if (MODE == 2) s = (knext + dkk[d] >= K4) ? g32_zero_chunk : s;
+                    lds_dma16(s, dst + (wave_u * G_NP + d) * 1024);
+                    asrc[d] += GBK;
+                } else {
+                    const int i = d - G_NP;
+                    const float* s = bsrc[i];
+                    if (MODE == 2) s = (knext + dkk[i] >= K4) ? g32_zero_chunk : s;
+                    lds_dma16(s, dst + G_OPWORDS * 4 + (wave_u * G_NP + i) * 1024);
+                    bsrc[i] += GBK;
+                }
+            };
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rd_a(0, i);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) rd_b(0, i);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int nd = MODE == 0 ? 0 : (j == 0 ? 6 : (j < 3 ? 5 : 0)), d0 = j == 0 ? 0 : (j == 1 ? 6 : 11);
+#pragma unroll
+                for (int n = 0; n < 64; ++n) {
+                    const int e = n / 16, i = (n / 4) % 4, jn = n % 4;
+                    acc[i][jn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[j & 1][i][e], fb[j & 1][jn][e], acc[i][jn], 0, 0, 0);
+                    if (n & 1) {
+                        const int t = n >> 1;
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (t < nd) {
+                            dma1(d0 + t);
+                        } else if (j < 3) {
+                            const int q = t - nd;
+                            if (q < 4) rd_a(j + 1, q);
+                            else if (q < 8) rd_b(j + 1, q - 4);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+            if (MODE != 0) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA of the next stage has landed ...
+                __syncthreads();                                   // ... and every wave's; this buffer is free for stage + 2
+            }
+        };
+
+        __syncthreads();                                   // every wave has left the buffers of the previous unit
+        {   // stage 0 of the unit (tail-checked: it may be the last stage of K)
+#pragma unroll
+            for (int i = 0; i < G_NP; ++i) {
+                const bool z = kbeg + dkk[i] >= K4;
+                lds_dma16(z ? g32_zero_chunk : asrc[i], lds_base + (wave_u * G_NP + i) * 1024);
+                lds_dma16(z ? g32_zero_chunk : bsrc[i], lds_base + G_OPWORDS * 4 + (wave_u * G_NP + i) * 1024);
+                asrc[i] += GBK;
+                bsrc[i] += GBK;
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                   // stage 0 has landed for every wave
+        int buf = 0, k0 = kbeg + GBK;                      // k0: the stage whose DMA the next call issues
+        for (int s = 0; s + 2 < nst; ++s, buf ^= 1, k0 += GBK) stage(std::integral_constant<int, 1>{}, buf, k0);
+        if (nst >= 2) { stage(std::integral_constant<int, 2>{}, buf, k0); buf ^= 1; }
+        stage(std::integral_constant<int, 0>{}, buf, 0);
+
+        // the unit's partial sum into C.  C/D layout of the 32 x 32 MFMA: col = lane & 31, row = (c & 3) + 8 (c >> 2) + 4 (lane >> 5)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int mt = m0 + wr * 128 + i * 32, nt = n0 + wc * 128 + j * 32;
+                if (mt >= g.M || nt >= g.N || nt > mt + 31) continue;          // (wave-uniform: an MFMA tile with no live element)
+                const int n = nt + r;
+                float* dst = g.C + (int64_t)(mt + 4 * h) * g.ldc + n;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int mo = (c & 3) + 8 * (c >> 2), m = mt + 4 * h + mo;
+                    if (m < g.M && n < g.N && n <= m) atomicAdd(dst + (int64_t)mo * g.ldc, g.alpha * acc[i][j][c]);
+                }
+                if (G32_GRAM_INFLIGHT < 63) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G32_GRAM_INFLIGHT) : "memory");
+            }
+    }
+}
+
 template <int BK>
 int dispatch32(hipStream_t st, const G32& a, dim3 grid, bool akc, bool bkc) {
     if (akc && bkc) hipLaunchKernelGGL((gemm32_kernel<BK, true, true>), grid, dim3(256), 0, st, a);
@@ -683,15 +868,21 @@ int g32_read_stamps(unsigned long long* out) { return (int)hipMemcpyFromSymbol(o
 // of work per tile; OUT_LOWER (square tile grids) zero-fills the strict upper triangle like gemm.hip does.
 int launch_gemm32(hipStream_t st, const GemmArgs& g) {
     const int fl = g.flags;
-    if (fl & ~(DSVGP_GEMM_TRANS_A | DSVGP_GEMM_TRANS_B | DSVGP_GEMM_OUT_LOWER | DSVGP_GEMM_K_PADDED | DSVGP_GEMM_C_ZEROED | DSVGP_GEMM_UPPER_UNDEF)) return 0;
-    if (g.batch != 1 || g.splitk != 1 || g.Cin || g.kscale || g.C32 || !g.C || g.beta != 0.0) return 0;
-    if (g.M < 512 || g.N < 512 || g.K < 512) return 0;
-    if (g.lda % 4 || g.ldb % 4 || ((uintptr_t)g.A % 16) || ((uintptr_t)g.B % 16)) return 0;     // 16-byte vector loads
+    // DSVGP_G32_GRAM (the 256 x 256 stream-K kernel for lower k-contiguous products, gemm32_gram_kernel), read at every launch:
+    // 0 = never; 1 = for every product it can take; 2 = as 1, and a lower-triangular product it cannot take -- by its layout or by any
+    // gate of this function -- is an error (hipErrorInvalidValue: how a test knows which kernel ran); unset = the rule below.
+    const char* genv = getenv("DSVGP_G32_GRAM");
+    const int gmode = genv ? atoi(genv) : 3;
+    const int not_taken = (gmode == 2 && (fl & DSVGP_GEMM_OUT_LOWER)) ? 1000 + (int)hipErrorInvalidValue : 0;
+    if (fl & ~(DSVGP_GEMM_TRANS_A | DSVGP_GEMM_TRANS_B | DSVGP_GEMM_OUT_LOWER | DSVGP_GEMM_K_PADDED | DSVGP_GEMM_C_ZEROED | DSVGP_GEMM_UPPER_UNDEF)) return not_taken;
+    if (g.batch != 1 || g.splitk != 1 || g.Cin || g.kscale || g.C32 || !g.C || g.beta != 0.0) return not_taken;
+    if (g.M < 512 || g.N < 512 || g.K < 512) return not_taken;
+    if (g.lda % 4 || g.ldb % 4 || ((uintptr_t)g.A % 16) || ((uintptr_t)g.B % 16)) return not_taken;     // 16-byte vector loads
     {   // the clamped vector loads of ragged edges stay inside the rows: ld covers the minor extent rounded up to 4
         const int64_t a_minor = (fl & DSVGP_GEMM_TRANS_A) ? g.M : g.K, b_minor = (fl & DSVGP_GEMM_TRANS_B) ? g.K : g.N;
-        if (g.lda < (a_minor + 3) / 4 * 4 || g.ldb < (b_minor + 3) / 4 * 4) return 0;
+        if (g.lda < (a_minor + 3) / 4 * 4 || g.ldb < (b_minor + 3) / 4 * 4) return not_taken;
         const int64_t a_rows = (fl & DSVGP_GEMM_TRANS_A) ? g.K : g.M, b_rows = (fl & DSVGP_GEMM_TRANS_B) ? g.N : g.K;
-        if (a_rows * g.lda >= (int64_t)1 << 31 || b_rows * g.ldb >= (int64_t)1 << 31) return 0;     // 32-bit row offsets
+        if (a_rows * g.lda >= (int64_t)1 << 31 || b_rows * g.ldb >= (int64_t)1 << 31) return not_taken;     // 32-bit row offsets
     }
     const bool out_lower = fl & DSVGP_GEMM_OUT_LOWER;
     G32 a{};
@@ -753,6 +944,41 @@ int launch_gemm32(hipStream_t st, const GemmArgs& g) {
         hipLaunchKernelGGL(gemm32_wide_kernel, dim3(cdiv(a.ntiles, 8) * 8), dim3(256), W_LDS_BYTES, st, a);
         e = hipGetLastError();
         return e == hipSuccess ? 1 : 1000 + (int)e;
+    }
+    // The 256 x 256 stream-K kernel (gemm32_gram_kernel) takes lower-triangular products of two k-contiguous operands outside
+    // deterministic mode.  The rule, from the table of profiles/gram_wide_ab.txt section 1: every workgroup (one per CU) gets at least
+    // G32_GRAM_STAGES stages of the (tile, stage) sequence -- each workgroup pays two first stages and two 256 KB atomic epilogues in
+    // the open and all CUs flush together at the end, which a short walk does not earn back.
+    const bool gram_can = out_lower && akc && bkc && dma_ok && !g.slab;
+    if (gmode == 2 && out_lower && !gram_can) return 1000 + (int)hipErrorInvalidValue;
+    if (gram_can && gmode != 0) {
+        static int cus[64];                          // CUs of each device (0 = not asked yet; the same value whoever writes it)
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return 1000 + (int)e;
+        int ncu = (dev >= 0 && dev < 64) ? cus[dev] : 0;
+        if (ncu <= 0) {
+            e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+            if (e != hipSuccess || ncu <= 0) return 1000 + (int)(e != hipSuccess ? e : hipErrorInvalidValue);
+            if (dev >= 0 && dev < 64) cus[dev] = ncu;
+        }
+        const char* cenv = getenv("DSVGP_G32_GRAM_KCHUNKS");
+        const int kchunks = cenv ? atoi(cenv) : G32_GRAM_KCHUNKS;
+        G32Gram w{};
+        w.walk = gram_walk_make(g.M, g.N, g.K, GT, GBK, kchunks);
+        if (gmode != 3 || w.walk.G >= (long long)G32_GRAM_STAGES * ncu) {
+            w.A = a.A; w.B = a.B; w.C = a.C; w.lda = g.lda; w.ldb = g.ldb; w.ldc = g.ldc;
+            w.M = g.M; w.N = g.N; w.K = g.K; w.nwg = ncu; w.alpha = a.alpha;
+            if (!(fl & DSVGP_GEMM_C_ZEROED)) {       // the units accumulate onto zeros (and the strict upper triangle is defined as zero)
+                e = zero_block(a.C, sizeof(float), a.ldc, a.M, a.N, st);
+                if (e != hipSuccess) return 1000 + (int)e;
+            }
+            e = hipFuncSetAttribute((const void*)gemm32_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS_BYTES);   // (per call: as above)
+            if (e != hipSuccess) return 1000 + (int)e;
+            hipLaunchKernelGGL(gemm32_gram_kernel, dim3(cdiv(ncu, 8) * 8), dim3(256), G_LDS_BYTES, st, w);
+            e = hipGetLastError();
+            return e == hipSuccess ? 1 : 1000 + (int)e;
+        }
     }
     sk = slab_slices(g, sk, sizeof(float));         // deterministic mode: as many slices as the caller's scratch holds
     a.splitk = sk;

@@ -43,6 +43,8 @@ int main(int argc, char** argv) {
         {"C4 Gram   A k-contig, transposed copy as B (m-contig)", OL, 3001, 3000, 24576, 24576, 3000, 1.0 * 3001 * 3000 * 24576.0},
         {"C4/8 dense N=3072                                    ", 0, 3000, 3072, 3001, 3004, 3072, 2.0 * 3000 * 3001 * 3072.0},
         {"C4/8 Gram  K=3072                                    ", TB | OL, 3001, 3000, 3072, 3072, 3072, 1.0 * 3001 * 3000 * 3072.0},
+        {"C4/4 Gram  K=6144                                    ", TB | OL, 3001, 3000, 6144, 6144, 6144, 1.0 * 3001 * 3000 * 6144.0},
+        {"C4/2 Gram  K=12288                                   ", TB | OL, 3001, 3000, 12288, 12288, 12288, 1.0 * 3001 * 3000 * 12288.0},
         {"C3 dense  [3300x3301]x[3301x5632]                    ", 0, 3300, 5632, 3301, 3304, 5632, 2.0 * 3300 * 3301 * 5632.0},
         {"C3 Gram   K=5632                                     ", TB | OL, 3301, 3300, 5632, 5632, 5632, 1.0 * 3301 * 3300 * 5632.0},
         {"rule      [3000x3001]x[3001x12288] (768 wide tiles)   ", 0, 3000, 12288, 3001, 3004, 12288, 2.0 * 3000 * 3001 * 12288.0},
@@ -52,7 +54,9 @@ int main(int argc, char** argv) {
         {"odd TT    M=700 N=1100 K=1300                        ", TA | TB, 700, 1100, 1300, 700, 1300, 2.0 * 700 * 1100 * 1300.0},
     };
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    const char* only = getenv("PROBE_ONLY");               // run only the cases whose name contains this text
     for (auto& c : cases) {
+        if (only && !strstr(c.name, only)) continue;
         const bool ta = c.flags & TA, tb = c.flags & TB, ol = c.flags & OL;
         const size_t na = (size_t)(ta ? c.K : c.M) * c.lda, nb = (size_t)(tb ? c.N : c.K) * c.ldb, nc = (size_t)c.M * c.N;
         float *A, *B, *C, *R;
@@ -100,6 +104,37 @@ int main(int argc, char** argv) {
             for (size_t i = 0; i < nc; ++i) diff += memcmp(&out[0][i], &out[1][i], 4) != 0;
             printf("    128x128 K whole %8.3f ms %7.2f TF | 256x192 %8.3f ms %7.2f TF | %zu of %zu elements differ in bits\n", ms_w[0],
                    c.flops / ms_w[0] / 1e9, ms_w[1], c.flops / ms_w[1] / 1e9, diff, nc);
+            rc = launch_gemm32(st, g);      // (the rule's own choice again, for the comparison below)
+            CK(hipStreamSynchronize(st));
+        }
+        // the 256 x 256 stream-K kernel (DSVGP_G32_GRAM=1, K whole and in 3 chunks) against the split-K launch of the 128 x 128 one (0) on the
+        // products it takes: time, and the largest difference (both meet in atomics: no fixed order, no bitwise comparison)
+        if (!ta && tb && ol && !getenv("DSVGP_G32_GRAM")) {
+            std::vector<float> out[3];
+            float ms_w[3] = {0.f, 0.f, 0.f};
+            const char* modes[3] = {"0", "1", "1"};
+            const char* chunks[3] = {nullptr, "1", "3"};
+            for (int w = 0; w < 3; ++w) {
+                setenv("DSVGP_G32_GRAM", modes[w], 1);
+                if (chunks[w]) setenv("DSVGP_G32_GRAM_KCHUNKS", chunks[w], 1);
+                for (int rep = 0; rep < 2; ++rep) {
+                    CK(hipEventRecord(e0, st));
+                    const int n = rep ? reps : 1;
+                    for (int i = 0; i < n; ++i) rc = launch_gemm32(st, g);
+                    CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
+                    CK(hipEventElapsedTime(&ms_w[w], e0, e1)); ms_w[w] /= n;
+                }
+                out[w].resize(nc);
+                CK(hipMemcpy(out[w].data(), C, nc * 4, hipMemcpyDeviceToHost));
+            }
+            unsetenv("DSVGP_G32_GRAM"); unsetenv("DSVGP_G32_GRAM_KCHUNKS");
+            double d1 = 0, d3 = 0, mx = 0;
+            for (size_t i = 0; i < nc; ++i) {
+                d1 = fmax(d1, fabs((double)out[1][i] - out[0][i])); d3 = fmax(d3, fabs((double)out[2][i] - out[0][i]));
+                mx = fmax(mx, fabs((double)out[0][i]));
+            }
+            printf("    128x128 split-K %8.3f ms %7.2f TF | 256x256 stream-K %8.3f ms %7.2f TF | in 3 K chunks %8.3f ms %7.2f TF | max diff / max %.1e %.1e (launches incl. the clear of C)\n",
+                   ms_w[0], c.flops / ms_w[0] / 1e9, ms_w[1], c.flops / ms_w[1] / 1e9, ms_w[2], c.flops / ms_w[2] / 1e9, d1 / mx, d3 / mx);
             rc = launch_gemm32(st, g);      // (the rule's own choice again, for the comparison below)
             CK(hipStreamSynchronize(st));
         }
