@@ -85,10 +85,18 @@ class DirectionalGradVariationalStrategy(torch.nn.Module):
             self._updated_known = True
 
     def forward(self, x, inducing_points=None, inducing_values=None, variational_inducing_covar=None, **kwargs):
-        derivative_directions = kwargs["derivative_directions"]
         num_induc = self.inducing_points.size(-2)
         num_directions = int(self.inducing_directions.size(-2) / num_induc)
         num_data = x.size(-2)
+        data_directions = getattr(self.model, "data_directions", None)
+        if data_directions is not None and int(data_directions) != num_directions:
+            # the model says its data carry another number of directions per point than it has inducing directions: exactly that many
+            D = kwargs.get("derivative_directions")
+            got = 0 if D is None or D.numel() == 0 else D.size(-2) / num_data
+            assert got == int(data_directions), \
+                "Need %d derivative directions per data point (model.data_directions), got %s" % (int(data_directions), got)
+            return PredictiveDistribution(self.model, x, D.to(x.device) if got else None)
+        derivative_directions = kwargs["derivative_directions"]
         num_derivative_directions = int(derivative_directions.size(-2) / num_data)
         assert num_derivative_directions == num_directions, \
             "Need minibatch dim to be same as number of directions for kernel"

@@ -129,6 +129,8 @@ SIGNATURES = {
     "dsvgp_kernel_bwd_wide_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "dsvgp_kernel_bwd_wide": (_i, [_p, _p, _l, _i, _p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p, _p]),
     "dsvgp_kernel_fwd_rect": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _l]),
+    "dsvgp_kernel_bwd_rect_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dsvgp_kernel_bwd_rect": (_i, [_p, _p, _l, _i, _p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
     "dsvgp_kernel_canon_supported": (_i, [_i, _i]),
     "dsvgp_kernel_canon2_supported": (_i, [_i, _i]),
     "dsvgp_kernel_fwd_canon2": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i, _p, _f, _p, _l, _i]),

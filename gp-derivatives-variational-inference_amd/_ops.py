@@ -560,7 +560,7 @@ def kernel_fwd_wide(ctx, pack1, n1, pack2, n2, d, p, hyp, jitter=0.0, out=None, 
 
 def kernel_fwd_rect(ctx, pack1, n1, p1, pack2, n2, p2, d, hyp, out=None):
     """out[n1 (p1 + 1), n2 (p2 + 1)] = s K(x1, x2; v1, v2) for packs made with DIFFERENT direction counts p1, p2 (each by
-    ``pack_points`` with its own p and the same center); float32, forward only (csrc/assemble_rect.hip)"""
+    ``pack_points`` with its own p and the same center); float32 (csrc/assemble_rect.hip; backward: ``kernel_bwd_rect``)"""
     P1, s1 = pack1[0], pack1[1]
     P2, s2 = pack2[0], pack2[1]
     shape = (n1 * (p1 + 1), n2 * (p2 + 1))
@@ -577,6 +577,35 @@ def kernel_fwd_rect(ctx, pack1, n1, p1, pack2, n2, p2, d, hyp, out=None):
     check(lib.dsvgp_kernel_fwd_rect(ctx.h, _ptr(P1), _ptr(s1), n1, p1, _ptr(P2), _ptr(s2), n2, p2, d, _ptr(hyp), _ptr(out),
                                     _ld(out)), "dsvgp_kernel_fwd_rect")
     return out
+
+
+def kernel_bwd_rect_workspace_bytes(n1, p1, n2, p2, d):
+    """bytes of the workspace of ``kernel_bwd_rect`` (pure host arithmetic); 0 for a shape it does not take"""
+    return int(lib.dsvgp_kernel_bwd_rect_workspace_bytes(int(n1), int(p1), int(n2), int(p2), int(d)))
+
+
+def kernel_bwd_rect(ctx, G, pack1, n1, p1, pack2, n2, p2, d, hyp, d_x1, d_v1, d_hyp, workspace=None):
+    """backward of ``kernel_fwd_rect`` with respect to side 1 (x1, v1) and (lengthscale, outputscale), given G = dLoss/dOut
+    [n1 (p1 + 1), n2 (p2 + 1)] (float32 or float64, unit inner stride); accumulates (+=) into d_x1, d_v1, d_hyp[0:2].  Side 2 is data:
+    no gradient (csrc/assemble_rect.hip)"""
+    P1, s1, vn1 = pack1[0], pack1[1], (pack1[2] if len(pack1) > 2 else None)
+    P2, s2 = pack2[0], pack2[1]
+    isd = G.dtype == f64
+    _req(G, f64 if isd else f32, "G", 2)
+    if G.shape != (n1 * (p1 + 1), n2 * (p2 + 1)):
+        raise ValueError("G has shape %s, expected %s" % (tuple(G.shape), (n1 * (p1 + 1), n2 * (p2 + 1))))
+    for P, sf, n, p, name in ((P1, s1, n1, p1, "pack1"), (P2, s2, n2, p2, "pack2")):
+        _req(P, f32, name, 2)
+        _req(sf, f32, name + " self terms", 1)
+        if P.shape != (n * (p + 1), packed_width(d)) or sf.shape[0] != n * (p + 1) or not P.is_contiguous():
+            raise ValueError("%s is not the contiguous pack of %d points with %d directions at d = %d" % (name, n, p, d))
+    nbytes = kernel_bwd_rect_workspace_bytes(n1, p1, n2, p2, d)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
+    check(lib.dsvgp_kernel_bwd_rect(ctx.h, _ptr(G), _ld(G), 1 if isd else 0, _ptr(P1), _ptr(s1), _ptr(vn1 if p1 > 0 else None), n1, p1,
+                                    _ptr(P2), _ptr(s2), n2, p2, d, _ptr(hyp), _ptr(d_x1), _ptr(d_v1 if p1 > 0 else None), _ptr(d_hyp),
+                                    _ptr(workspace)), "dsvgp_kernel_bwd_rect")
+    return workspace
 
 
 def kernel_bwd_wide(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp, workspace=None):

@@ -219,6 +219,9 @@ class ElboEngine:
         # (deferred_check): the ~100 us the host waited per step at M' = 600 leave its critical path
         self.defer_status = False
         self._deferred = None                   # (plan, workspace) of a step whose status has not been read yet
+        # the rectangular TRAINING step (loss_and_grads with pd != p directions per data point, csrc/assemble_rect.hip): pd while such a
+        # step is being queued, None otherwise -- the data side's direction count wherever the piecewise path reads ``_pd``
+        self._train_pd = None
         self._zx_dirs = None                    # (idx, base) of the batch in flight when its directions were stated one-hot (_ops.state_directions)
         self.c_step_used = False        # whether the last step ran through the one-call path
         self.c_step_timed = []          # plans of the steps queued with record_events on, in order
@@ -385,10 +388,43 @@ class ElboEngine:
 
     def _pd(self, p):
         """directional derivatives per DATA point"""
+        if self._train_pd is not None:
+            return self._train_pd
         return 0 if self.data_outputs == "values" else p
+
+    def _train_rect_pd(self, params, x, D):
+        """None when the training step carries the model's own number of directions per data point (today's paths, untouched), else
+        pd: the rectangular training step (K_ZX and its backward from csrc/assemble_rect.hip, piecewise path, one rank).  What that
+        step is not built for is refused here, on the shapes alone, before any device work."""
+        if self.data_outputs == "values":
+            return None                                 # the derivative-free engine stays exactly as it is
+        p, pd = self._direction_counts(params, x, D, self.shared_directions)
+        if pd == p:
+            return None
+        what = "a training step with %d directions per data point on a model with %d" % (pd, p)
+        if pd > 95:
+            raise ValueError("at most 95 derivative directions per data point, got %d" % pd)
+        if self.whitening == "ciq":
+            raise ValueError("CIQ whitening trains with the model's own number of directions per data point: %s needs the square "
+                             "(p + 1)-block K_XZ of the msMINRES solves" % what)
+        if self.shared_directions:
+            raise ValueError("shared inducing directions train with the model's own number of directions per data point: %s is "
+                             "built for the per-point parameterisation only" % what)
+        coll = self.collective
+        if coll is not None and coll.world > 1:
+            raise ValueError("%s runs on one rank: a collective with world = %d is not built for it" % (what, coll.world))
+        if self.capture_mode:
+            raise ValueError("%s runs on the piecewise path, which is not captured into a HIP graph (capture_mode)" % what)
+        return pd
 
     def _assemble_kzx(self, ctx, packZ, M, packX, B, d, p, hyp, Mp):
         """K_ZX [M', B(pd+1)].  Derivative-free data: the value columns (every (p+1)-th) of the full block matrix."""
+        if self._train_pd is not None:                   # rectangular training step: (p + 1) x (pd + 1) micro-blocks, one launch
+            pd = self._train_pd
+            ev = self._event_pair()
+            Kzx = _ops.kernel_fwd_rect(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, B * (pd + 1)), f32))
+            self._event_done("assemble_fwd", ev)
+            return Kzx
         if self.data_outputs == "values" and p > 0:
             full = self._get("Kzx_full", (Mp, B * (p + 1)), f32)
             _ops.kernel_fwd(ctx, packZ, M, packX, B, d, p, hyp, out=full)
@@ -429,7 +465,18 @@ class ElboEngine:
             ev[1].record()
             self.events.append((name, ev[0], ev[1]))
 
+    def _kernel_bwd_zx_bytes(self, M, B, d, p):
+        """workspace bytes of ``_kernel_bwd_zx``"""
+        if self._train_pd is not None:
+            return _ops.kernel_bwd_rect_workspace_bytes(M, p, B, self._train_pd, d)
+        return _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, B, d, p)
+
     def _kernel_bwd_zx(self, ctx, Kb32, packZ, M, packX, B, d, p, hyp, dZ, dV, d_hyp, kws):
+        if self._train_pd is not None:                   # rectangular training step: the upstream [M', B(pd+1)] as it is
+            ev = self._event_pair()
+            _ops.kernel_bwd_rect(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, hyp, dZ, dV, d_hyp, kws)
+            self._event_done("assemble_bwd", ev)
+            return
         if self.data_outputs == "values" and p > 0:
             full = self._get("Kzx_full", (Kb32.shape[0], B * (p + 1)), f32)
             full.zero_()
@@ -705,6 +752,19 @@ class ElboEngine:
         ``include_kl=False`` leaves the (replicated) KL term out so exactly one rank adds it.
         ``fast`` (default ``self.elbo_fast``): in ELBO mode use the Gram-matrix formulation, which does not
         produce per-output variances (``varn`` is then an empty tensor; ``predict`` gives them on demand)."""
+        train_pd = self._train_rect_pd(params, x, D)       # (refusals first: shapes only, no device work)
+        if train_pd is None:
+            return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
+        B = x.shape[0]
+        if y.shape != (B * (train_pd + 1),):
+            raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % (B * (train_pd + 1)))
+        self._train_pd = train_pd
+        try:
+            return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
+        finally:
+            self._train_pd = None
+
+    def _loss_and_grads_checked(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
         ctx = _ops.Context.get(self.device)
         self._eval_cache = None
         if fast is None:
@@ -1377,14 +1437,15 @@ class ElboEngine:
         self._ctx = ctx
         self.c_step_used = False
         self._last_fast = None
-        if self._c_step_eligible(params, x, use_fast, sync):
+        rect = self._train_pd is not None                  # (never a one-call step: K_ZX and its backward are the rectangular kernels)
+        if not rect and self._c_step_eligible(params, x, use_fast, sync):
             pz = params["inducing_directions"].shape[0] // params["inducing_points"].shape[0]
             Bq = x.shape[0] * (pz + 1)
             if y.shape != (Bq,):
                 raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % Bq)
             return self._c_step(ctx, params, x, y.contiguous(), D, num_data, float(Bq if global_rows is None else global_rows),
                                 include_kl)
-        if not use_fast and mll_type in ("ELBO", "PLL") and self._c_step_po_eligible(params, x, sync):
+        if not rect and not use_fast and mll_type in ("ELBO", "PLL") and self._c_step_po_eligible(params, x, sync):
             pz = params["inducing_directions"].shape[0] // params["inducing_points"].shape[0]
             Bq = x.shape[0] * (pz + 1)
             if y.shape != (Bq,):
@@ -1436,7 +1497,7 @@ class ElboEngine:
                                         scal, kl_buf, dm, dLS, Kb32, Lbar, side)
             varn = torch.empty(0, dtype=f32, device=dev)
         else:
-            packX, A64, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D)
+            packX, A64, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, rect_pd=self._train_pd)
             mu_bar = torch.empty(Bp, dtype=f32, device=dev)
             var_bar = torch.empty(Bp, dtype=f32, device=dev)
             varn = torch.empty(Bp, dtype=f32, device=dev)
@@ -1462,7 +1523,7 @@ class ElboEngine:
             _ops.gemm(ctx, TRANS_B | OUT_LOWER, Kb64, A64, Lbar, alpha=-1.0)    # L-bar = -tril(K_ZX-bar A^T)
 
         dZ, dV = grads["inducing_points"], grads["inducing_directions"]
-        kws = self._bytes("kbwd_ws", max(_lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, B, d, p),
+        kws = self._bytes("kbwd_ws", max(self._kernel_bwd_zx_bytes(M, B, d, p),
                                          _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, M, d, p)))
         # K_ZX-bar's kernel backward (HBM-bound read of 4 M' B' bytes) next to the fp64 products of L-bar and the Cholesky backward
         # (matrix-pipe bound): on the side stream from the moment the dense product is done, joined before the K_ZZ kernel backward
@@ -1472,7 +1533,7 @@ class ElboEngine:
         bwd_overlap = self.bwd_overlap if self.bwd_overlap is not None else (Bp <= 2 * Mp and self.collective is None)
         bwd_overlap = bwd_overlap and not self.deterministic
         if bwd_overlap and use_fast and dense_done is not None and self._side is not None and not self.capture_mode:
-            kws2 = self._bytes("kbwd_ws_zx", _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, B, d, p))
+            kws2 = self._bytes("kbwd_ws_zx", self._kernel_bwd_zx_bytes(M, B, d, p))
             with torch.cuda.stream(self._side):
                 self._side.wait_event(dense_done)
                 ctx.bind()
@@ -1524,8 +1585,13 @@ class ElboEngine:
         m = params["variational_mean"]
         LS = params["chol_variational_covar"]
         packZ = self._pending_packZ
-        packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if p > 0 else None, p, hyp, self.center)
-        self._zx_dirs = _ops.stated_directions(D, d, p) if p > 0 else None
+        if self._train_pd is None:
+            packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if p > 0 else None, p, hyp, self.center)
+            self._zx_dirs = _ops.stated_directions(D, d, p) if p > 0 else None
+        else:                                            # rectangular training step: the data pack with ITS count, same centre
+            pd = self._train_pd
+            packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, hyp, self.center)
+            self._zx_dirs = None
         Kzx = self._assemble_kzx(ctx, packZ, M, packX, B, d, p, hyp, Mp)
         # [S - I | m / (2 vbar)]: one solve gives [Q' | a / (2 vbar)].  Rows padded to a multiple of 4 floats: the lean fp64
         # kernel (gemm64.hip) streams a float right-hand side with 16-byte loads

@@ -415,6 +415,11 @@ class ElboEngine64(ElboEngine):
     def loss_and_grads(self, params, x, y, D, num_data, mll_type="ELBO", global_rows=None, include_kl=True, fast=None):
         """(loss, grads dict, mu, varn), all fp64; see ``ElboEngine.loss_and_grads`` for the arguments.  With natural parameters
         (``natural_vec``, ``natural_mat``) the gradients of those two slots are the expectation-parameter gradients NGD steps along."""
+        if self.data_outputs != "values":
+            p, pd = self._direction_counts(params, x, D, self.shared_directions)
+            if pd != p:
+                raise ValueError("float64 model mode trains with the model's own number of directions per data point (%d), got %d: "
+                                 "the rectangular kernel backward is built in float32 only" % (p, pd))
         if self.whitening == "ciq":
             if mll_type not in ("ELBO", "PLL"):
                 raise ValueError("mll_type must be 'ELBO' or 'PLL'")

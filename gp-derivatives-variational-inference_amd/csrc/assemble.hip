@@ -3226,6 +3226,13 @@ static int kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_
     return finish_points(ctx, g, slab, ns, P1, vnorm1, n1, d, p, hyp, symmetric ? 2.f : 1.f, d_x1, d_v1, partials, nparts, d_hyp);
 }
 
+int kernel_bwd_finish_points(dsvgp_ctx* ctx, int d, int p, const float* slab, int ns, const float* P1, const float* vnorm1, int n1,
+                             const float* hyp, float sym, float* d_x1, float* d_v1, const float* partials, int nparts, float* d_hyp) {
+    Geom g;
+    if (int rc = make_geom_any(d, p, g)) return rc;
+    return finish_points(ctx, g, slab, ns, P1, vnorm1, n1, d, p, hyp, sym, d_x1, d_v1, partials, nparts, d_hyp);
+}
+
 extern "C" int dsvgp_kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1,
                                      const float* self1, const float* vnorm1, int n1, const float* P2,
                                      const float* self2, int n2, int d, int p, const float* hyp, int symmetric,

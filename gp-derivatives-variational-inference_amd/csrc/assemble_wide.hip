@@ -267,21 +267,30 @@ inline WideTiles wide_tiles(int q) {
     return t;
 }
 
-struct WideBwdPlan { int ns, kper, nparts, gx, gy; size_t slab_f, part_f, tb_f; };
-inline WideBwdPlan wide_bwd_plan(int n1q, int n2q, int q, int NP) {
-    WideBwdPlan w;
-    const WideTiles t = wide_tiles(q);
-    w.gx = cdiv(n2q, t.Tc); w.gy = cdiv(n1q, t.Tr);
-    w.nparts = w.gx * w.gy;
+// the contraction's cut of the n2q range: ns pieces of kper columns, one slab [n1q][NP] each
+struct WideContractPlan { int ns, kper; size_t slab_f; };
+inline WideContractPlan wide_contract_plan(int n1q, int n2q, int NP) {
+    WideContractPlan c;
     // split the contraction over n2q until ~2048 workgroups run (a few per CU), pieces of at least 256 columns
     const int tiles = cdiv(n1q, CM) * cdiv(NP, CN);
     int ns = cdiv(2048, tiles);
     const int smax = cdiv(n2q, 256);
     if (ns > smax) ns = smax;
     if (ns < 1) ns = 1;
-    w.kper = cdiv(cdiv(n2q, ns), CK) * CK;
-    w.ns = cdiv(n2q, w.kper);
-    w.slab_f = ((size_t)w.ns * n1q * NP + 63) & ~(size_t)63;
+    c.kper = cdiv(cdiv(n2q, ns), CK) * CK;
+    c.ns = cdiv(n2q, c.kper);
+    c.slab_f = ((size_t)c.ns * n1q * NP + 63) & ~(size_t)63;
+    return c;
+}
+
+struct WideBwdPlan { int ns, kper, nparts, gx, gy; size_t slab_f, part_f, tb_f; };
+inline WideBwdPlan wide_bwd_plan(int n1q, int n2q, int q, int NP) {
+    WideBwdPlan w;
+    const WideTiles t = wide_tiles(q);
+    w.gx = cdiv(n2q, t.Tc); w.gy = cdiv(n1q, t.Tr);
+    w.nparts = w.gx * w.gy;
+    const WideContractPlan c = wide_contract_plan(n1q, n2q, NP);
+    w.kper = c.kper; w.ns = c.ns; w.slab_f = c.slab_f;
     w.part_f = ((size_t)2 * w.nparts + 63) & ~(size_t)63;
     w.tb_f = (size_t)n1q * n2q;
     return w;
@@ -292,6 +301,20 @@ inline WideBwdPlan wide_bwd_plan(int n1q, int n2q, int q, int NP) {
 size_t kernel_bwd_wide_workspace(int n1q, int n2q, int q, int NP) {
     const WideBwdPlan w = wide_bwd_plan(n1q, n2q, q, NP);
     return sizeof(float) * (w.slab_f + w.part_f + w.tb_f) + 64;
+}
+
+size_t kernel_bwd_wide_slab_floats(int n1q, int n2q, int NP) { return wide_contract_plan(n1q, n2q, NP).slab_f; }
+
+int launch_kernel_bwd_wide_contract(hipStream_t st, const float* TB, int n1q, int n2q, const float* P2, int DP, int NP, float* slab,
+                                    int* ns) {
+    const WideContractPlan c = wide_contract_plan(n1q, n2q, NP);
+    const int gy = cdiv(n1q, CM);
+    if (gy > 65535 || c.ns > 65535) return DSVGP_EINVAL;
+    hipLaunchKernelGGL(kernel_bwd_wide_contract_kernel, dim3(cdiv(NP, CN), gy, c.ns), dim3(WNT), 0, st, TB, n1q, n2q, P2, DP, NP, c.kper,
+                       slab);
+    DSVGP_LAUNCH_CHECK();
+    *ns = c.ns;
+    return 0;
 }
 
 int launch_kernel_fwd_wide(hipStream_t st, const float* P1, const float* self1, int n1q, const float* P2, const float* self2, int n2q,

@@ -143,6 +143,14 @@ size_t kernel_bwd_wide_workspace(int n1q, int n2q, int q, int NP);
 int launch_kernel_bwd_wide(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1q,
                            const float* P2, const float* self2, int n2q, int q, int K4, int DP, int NP, const float* hyp, void* workspace,
                            float** slab, int* ns, float** partials, int* nparts);
+// the contraction launch alone, for a Tbar[n1q, n2q] made elsewhere (assemble_rect.hip: its two sides have different micro-block periods,
+// which the contraction never sees): slab[*ns][n1q][NP], kernel_bwd_wide_slab_floats floats (a multiple of 64)
+size_t kernel_bwd_wide_slab_floats(int n1q, int n2q, int NP);
+int launch_kernel_bwd_wide_contract(hipStream_t st, const float* TB, int n1q, int n2q, const float* P2, int DP, int NP, float* slab,
+                                    int* ns);
+// the points launch of the kernel backwards (assemble.hip: finish_points) for side 1's geometry (d, p): d_x1 / d_v1 / d_hyp[0..1] +=
+int kernel_bwd_finish_points(dsvgp_ctx* ctx, int d, int p, const float* slab, int ns, const float* P1, const float* vnorm1, int n1,
+                             const float* hyp, float sym, float* d_x1, float* d_v1, const float* partials, int nparts, float* d_hyp);
 int launch_widen_sym_f32_f64(hipStream_t st, const float* src, int64_t lds, double* dst, int64_t ldd, int n);    // elbo.hip: fp64 mirror of an fp32 lower triangle
 int launch_mirror_sminus_i_col(hipStream_t st, float* A, int n, int64_t lda, const float* m, const float* hyp, float rows, double* W = nullptr,
                                int64_t ldw = 0);   // elbo.hip

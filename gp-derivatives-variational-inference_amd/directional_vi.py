@@ -57,6 +57,7 @@ class GPModel(ApproximateGP):
         self.variational_strategy = variational_strategy
         self._engine = None
         self.data_parallel = None
+        self.data_directions = None             # int: the data carry that many directions per point, not num_directions (ApproximateGP)
         self.mean_module = ConstantMean()
         self.covar_module = ScaleKernel(RBFKernelDirectionalGrad())
         if self._ciq:
@@ -146,6 +147,9 @@ class TrainLoop:
         self._graphs, self._graph_seen, self._graph_pending = {}, {}, None
         self._deferred_pending = None       # (idx, idx_y, learning rates) of an eager step whose factorisation status has not been read yet
         self.defer_status = None            # None: DSVGP_DEFER_STATUS (default off); True / False
+        # int: every minibatch carries that many derivative columns (canonical directions) per point instead of the model's
+        # ``minibatch_dim`` -- the rectangular training step of the engine (eager piecewise path: no graph replay, no deferred status)
+        self.data_directions = None
 
     def epoch_permutation(self):
         return torch.randperm(self.X.shape[0], device=self.device, generator=self.perm_gen)   # DataLoader(shuffle=True)
@@ -166,6 +170,8 @@ class TrainLoop:
             self._values_only, need_variance = ok, not ok
         eng.elbo_fast = not need_variance
         dim, p, dp = self.dim, self.minibatch_dim, self.dp
+        if self.data_directions is not None:
+            p = self.data_directions                    # columns drawn per minibatch (their directions: the matching rows of E_canonical)
         if dp is not None:
             dp.global_batch = idx.shape[0]
             dp.replicated_step = idx.shape[0] < dp.world      # tail smaller than the world: no empty shards (see parallel.py)
@@ -197,7 +203,7 @@ class TrainLoop:
         mode = getattr(self, "defer_status", None)
         if mode is None:
             mode = os.environ.get("DSVGP_DEFER_STATUS", "0") == "1"
-        if not mode or need_variance or self.dp is not None or self.autograd_protocol:
+        if not mode or need_variance or self.dp is not None or self.autograd_protocol or self.data_directions is not None:
             return False
         eng = self.model.engine
         # (deferral is a float32 feature and stays off under ``deterministic``.  A float64 model never defers -- last clause -- and its loop
@@ -322,7 +328,9 @@ class TrainLoop:
         kwargs = {}
         # (the directions are rows of E_canonical, the same p of them for every point: said to the engine as an index list next to
         #  the matrix itself -- _ops.state_directions -- so that K_ZX runs on the canonical-direction assembly kernels)
-        if self.dfree:                          # dfree_directional_vi.py:224-227
+        if self.data_directions is not None:    # py canonical directions per point, py != the model's count: nothing to state
+            kwargs["derivative_directions"] = self.E_canonical.index_select(0, cols[1:].long() - 1).repeat(nb, 1) if py else None
+        elif self.dfree:                        # dfree_directional_vi.py:224-227
             kwargs["derivative_directions"] = _ops.state_directions(self.E_canonical[:p].repeat(nb, 1), self._arange_p(p), 0)
         elif not self.full_gradient:
             if Db is not None:
@@ -354,7 +362,7 @@ class TrainLoop:
         if mode is None:
             env = os.environ.get("DSVGP_GRAPH")
             mode = None if env is None else env == "1"
-        if mode is False or need_variance or self.dp is not None or self.autograd_protocol:
+        if mode is False or need_variance or self.dp is not None or self.autograd_protocol or self.data_directions is not None:
             return False
         eng = self.model.engine
         ok = (eng.whitening == "cholesky" and not eng.shared_directions and self.mll.mll_type == "ELBO"
@@ -461,9 +469,19 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
                    num_epochs=1, learning_rate_hypers=0.01, inducing_data_initialization=True, lr_sched=None,
                    mll_type="ELBO", gamma=0.1, fixed_inducing_locations=None, seed=None, tensors=None,
                    use_ngd=False, learning_rate_ngd=0.1, use_ciq=False, num_contour_quadrature=15, model_class=None,
-                   dfree=False, shared=False):
-    """Everything ``train_gp`` does before its loop (directional_vi.py:130-219); returns a TrainLoop."""
+                   dfree=False, shared=False, data_directions=None):
+    """Everything ``train_gp`` does before its loop (directional_vi.py:130-219); returns a TrainLoop.
+    ``data_directions`` (int, default None = ``num_directions``): derivative columns of y per minibatch point, whatever the number of
+    inducing directions (0: function values only; ``dim``: the full gradient) -- the engine's rectangular training step."""
     assert num_directions == minibatch_dim
+    if data_directions is not None:
+        data_directions = int(data_directions)
+        if dfree or shared or use_ciq:
+            raise ValueError("data_directions is built for the Cholesky-whitened per-point DSVGP model (not dfree / shared / CIQ)")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("data_directions runs on one rank (dp): the rectangular training step is not built for a collective")
+        if torch.get_default_dtype() == torch.float64 or (tensors is not None and tensors[0].dtype == torch.float64):
+            raise ValueError("data_directions with a float64 dataset: the rectangular kernel backward is built in float32 only")
     if not torch.cuda.is_available():
         raise RuntimeError("train_gp needs an MI355X (HIP) device: the DSVGP hot path has no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -552,8 +570,15 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
         mll = PredictiveLogLikelihood(likelihood, model, num_data=num_data)
     else:
         raise ValueError("mll_type must be 'ELBO' or 'PLL'")
-    return TrainLoop(X, Y, model, likelihood, mll, (variational_optimizer, hyperparameter_optimizer),
+    loop = TrainLoop(X, Y, model, likelihood, mll, (variational_optimizer, hyperparameter_optimizer),
                      (variational_scheduler, hyperparameter_scheduler), minibatch_dim, dp, col_rng, perm_gen, dfree=dfree)
+    if data_directions is not None:
+        if not 0 <= data_directions <= min(dim, 95) or Y.shape[1] != dim + 1:
+            raise ValueError("data_directions must lie in [0, min(dim, 95)] = [0, %d] on targets with dim + 1 columns, got %d"
+                             % (min(dim, 95), data_directions))
+        if data_directions != num_directions:            # (equal counts: today's step, nothing to set)
+            loop.data_directions = model.data_directions = data_directions
+    return loop
 
 
 def train_gp(train_dataset, num_inducing=128,
@@ -568,9 +593,13 @@ def train_gp(train_dataset, num_inducing=128,
              watch_model=False, gamma=0.1,
              verbose=True,
              fixed_inducing_locations=None,
+             data_directions=None,
              **args):
     """Train a Derivative GP with the Directional Derivative Variational Inference method
     (argument meaning identical to the reference, directional_vi.py:106-129).
+
+    ``data_directions`` (int, not in the reference; default None = ``num_directions``): every minibatch carries that many derivative
+    columns of y per point -- 0: function values only, ``dim``: the full gradient -- whatever the number of inducing directions.
 
     Extra keyword arguments understood through ``**args`` (all optional, ignored by the reference):
       ``seed`` (int): seeds the minibatch permutation and the derivative-column sampling (must be equal
@@ -583,8 +612,9 @@ def train_gp(train_dataset, num_inducing=128,
                           fixed_inducing_locations, seed=args.get("seed"), use_ngd=use_ngd,
                           learning_rate_ngd=learning_rate_ngd, use_ciq=use_ciq,
                           num_contour_quadrature=num_contour_quadrature, model_class=args.get("_model_class"),
-                          shared=bool(args.get("_shared")))
+                          shared=bool(args.get("_shared")), data_directions=data_directions)
     n_samples = loop.X.shape[0]
+    stride = (num_directions if loop.data_directions is None else loop.data_directions) + 1      # outputs per minibatch point
     max_steps = args.get("max_steps")
     total_step = 0
     loss = None
@@ -594,9 +624,9 @@ def train_gp(train_dataset, num_inducing=128,
             report = (total_step % 50 == 0) and verbose
             loss, output, y_batch = loop.step(perm[start:start + minibatch_size], need_variance="values" if report else False)
             if report:
-                means = output.mean[::num_directions + 1]
+                means = output.mean[::stride]
                 stds = output.value_variance.sqrt()          # = output.variance.sqrt()[::num_directions + 1]
-                nll = -torch.distributions.Normal(means, stds).log_prob(y_batch[::num_directions + 1]).mean()
+                nll = -torch.distributions.Normal(means, stds).log_prob(y_batch[::stride]).mean()
                 print(f"Epoch: {i}; total_step: {total_step}, loss: {loss.item()}, nll: {nll}")
                 sys.stdout.flush()
             total_step += 1

@@ -286,6 +286,10 @@ class ApproximateGP(torch.nn.Module):
         super().__init__()
         self.variational_strategy = variational_strategy
         self._engine = None
+        # None: ``self(x, derivative_directions=D)`` takes the model's own number of directions per data point (the reference's
+        # assertion).  int pd: the call takes exactly pd per point (``None`` / empty for 0) and the ``mll(...)`` / ``backward_step``
+        # route trains on them (ElboEngine.loss_and_grads with pd != p: float32, Cholesky whitening, one rank)
+        self.data_directions = None
 
     @property
     def engine(self):

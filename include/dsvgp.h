@@ -137,7 +137,7 @@ int dsvgp_kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_d
  *   dsvgp_kernel_fwd: micro-block (i, j) is k [[1, w_b/ell], [-u_a/ell, (G_ab - u_a w_b)/ell^2]] for a = 1..p1, b = 1..p2, with
  *   r = (x1_i - x2_j)/ell, k = exp(-|r|^2/2), u_a = r.v1_ia, w_b = r.v2_jb, G_ab = v1_ia.v2_jb (unit directions).
  * P1 / self1 and P2 / self2: what dsvgp_pack_points wrote for each side WITH THAT SIDE'S OWN p and the same center; p = 0 on a
- * side: value rows only.  Forward only, float output, no jitter.  Any d >= 1 (the workgroup's LDS does not depend on d) and any
+ * side: value rows only.  Float output, no jitter (backward: dsvgp_kernel_bwd_rect below).  Any d >= 1 (the workgroup's LDS does not depend on d) and any
  * 0 <= p1, p2 <= 95, independently.  One launch, no intermediate in device memory, every element stored once, no atomics: two
  * identical calls give bitwise equal results; at p1 == p2 the arithmetic is that of dsvgp_kernel_fwd_wide.
  * Alignment: P1 and P2 must be 16-byte aligned (their rows, dsvgp_packed_width(d) floats, are read 16 bytes at a time); `out` and
@@ -146,6 +146,23 @@ int dsvgp_kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_d
  * 65535 row tiles (n1*(p1+1) above ~3.1e6 at the 48-row tile), ld too small, P1 or P2 misaligned.                                */
 int dsvgp_kernel_fwd_rect(dsvgp_ctx* ctx, const float* P1, const float* self1, int n1, int p1, const float* P2,
                           const float* self2, int n2, int p2, int d, const float* hyp, float* out, int64_t ld);
+/* Backward of dsvgp_kernel_fwd_rect with respect to side 1 (x1, v1) and (lengthscale, outputscale), given G = dLoss/dOut
+ * [n1*(p1+1), n2*(p2+1)] with leading dimension ldg >= n2*(p2+1); g_is_double selects G's dtype (float / double).  Side 2 is data and
+ * receives no gradient; there is no symmetric case (the square K_ZZ goes through dsvgp_kernel_bwd).
+ * Accumulates (+=) into d_x1[n1, d], d_v1[n1*p1, d] and d_hyp[0..1] (lengthscale, outputscale), as dsvgp_kernel_bwd does; p1 = 0 needs
+ * neither vnorm1 nor d_v1 (both may be null).  P1 / self1 / vnorm1 and P2 / self2: what dsvgp_pack_points wrote for each side with that
+ * side's own p and the same center.  Any d >= 1 and any 0 <= p1, p2 <= 95, independently.
+ * Three launches -- Tbar tiles [n1*(p1+1), n2*(p2+1)] into the workspace, their contraction with the packed rows of side 2 into split
+ * slabs, the points launch that adds slabs and per-workgroup partial sums in a fixed order -- and no floating-point atomics: two
+ * identical calls give bitwise equal results.  At p1 == p2 > 0 tiles and arithmetic are those of dsvgp_kernel_bwd_wide (symmetric = 0).
+ * workspace: dsvgp_kernel_bwd_rect_workspace_bytes bytes of device memory for these shapes, 4-byte aligned (a pure host function; 0 for
+ * n1 <= 0, n2 <= 0, d < 1, p1 or p2 outside [0, 95] or a grid beyond the limits below).  Alignment: P1 and P2 16 bytes, G its element size.
+ * DSVGP_EINVAL: a null pointer, d < 1, p1 or p2 outside [0, 95], negative n1 / n2, n*(p+1) beyond INT_MAX on a side, more than 65535
+ * row tiles or 64-row contraction tiles, ldg too small, P1 or P2 misaligned.  n1 == 0 or n2 == 0: returns 0, nothing is touched. */
+size_t dsvgp_kernel_bwd_rect_workspace_bytes(int n1, int p1, int n2, int p2, int d);
+int dsvgp_kernel_bwd_rect(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
+                          const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
+                          const float* hyp, float* d_x1, float* d_v1, float* d_hyp, void* workspace);
 /* 1 when dsvgp_kernel_fwd_canon / _bwd_canon take the geometry (d, p), 0 otherwise */
 int dsvgp_kernel_canon_supported(int d, int p);
 /* backward of dsvgp_kernel_fwd_canon (symmetric = 0 semantics; same workspace size as dsvgp_kernel_bwd) */
