@@ -767,6 +767,45 @@ def predictive_stats(ctx, A, W, p, m, constant, hyp, mu, var, workspace=None):
     return workspace
 
 
+def predictive_blocks(ctx, A, W, pd, packX, d, hyp, with_noise, out=None):
+    """out[B, pd + 1, pd + 1] = the diagonal blocks of s K_XX + (1e-4 + noise) I + W^T W - A^T A, one per data point, from
+    A = L^-1 K_ZX and W = L_S^T A [Mp, B (pd + 1)] (float32, interleaved columns); ``W`` None (or ``A`` itself): zero middle term.
+    ``packX``: the data pack of ``pack_points`` made with ``pd`` directions per point (its unit direction rows are read; may be
+    None at pd = 0).  Nothing of size B (pd + 1) squared is formed (dsvgp_predictive_blocks, csrc/predict_blocks.hip)."""
+    _req(A, f32, "A", 2)
+    Mp, nc = A.shape
+    q = int(pd) + 1
+    if pd < 0 or pd > 95:
+        raise ValueError("at most 95 derivative directions per data point, got %d" % pd)
+    if nc == 0 or nc % q:
+        raise ValueError("A has %d columns, not a positive multiple of pd + 1 = %d" % (nc, q))
+    B = nc // q
+    if W is not None:
+        _req(W, f32, "W", 2)
+        if W.shape != A.shape:
+            raise ValueError("W has shape %s, A %s" % (tuple(W.shape), tuple(A.shape)))
+    PX = None
+    if pd > 0:
+        if packX is None:
+            raise ValueError("the data pack is needed at pd > 0 (its unit direction rows)")
+        PX = _req(packX[0], f32, "packX", 2)
+        if PX.shape != (nc, packed_width(d)) or not PX.is_contiguous():
+            raise ValueError("packX is not the contiguous pack of %d points with %d directions at d = %d" % (B, pd, d))
+    _req(hyp, f32, "hyp", 1)
+    shape = (B, q, q)
+    if out is None:
+        out = torch.empty(shape, dtype=f32, device=A.device)
+    if not out.is_cuda or out.dtype != f32 or out.shape != shape or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 GPU tensor of shape %s" % (shape,))
+    nbytes = int(lib.dsvgp_predictive_blocks_workspace_bytes(Mp, B, int(pd)))
+    if nbytes == 0:
+        raise ValueError("dsvgp_predictive_blocks does not take Mp = %d, B = %d, pd = %d" % (Mp, B, pd))
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=A.device)
+    check(lib.dsvgp_predictive_blocks(ctx.h, _ptr(A), _ld(A), _ptr(W), _ld(W) if W is not None else 0, Mp, B, int(pd), _ptr(PX), int(d),
+                                      _ptr(hyp), 1 if with_noise else 0, _ptr(out), _ptr(workspace), nbytes), "dsvgp_predictive_blocks")
+    return out
+
+
 def mean_weights_bytes(M, d):
     return int(lib.dsvgp_mean_weights_bytes(int(M), int(d)))
 

@@ -614,6 +614,32 @@ class ElboEngine:
         return self._predict_chol(ctx, params, x, D, cache, joint=True)
 
     @torch.no_grad()
+    def predict_blocks(self, params, x, D, cache=False):
+        """Mean [B'] and the PER-POINT predictive covariance blocks [B, pd + 1, pd + 1] (fp32; likelihood noise and the 1e-4 jitter
+        on the block diagonals, as ``predict_joint`` has them on its diagonal): Var f(x), Cov(f(x), D f(x)) and Cov D f(x) at every
+        point -- the diagonal blocks of ``predict_joint``'s Sigma without K_XX, the two Gram products or anything of size B' x B'
+        (csrc/predict_blocks.hip).  Everything up to A = L^-1 K_ZX and W = L_S^T A is ``predict``'s, evaluation cache included, so any
+        direction count per data point goes (``D`` None: [B, 1, 1], the variances)."""
+        ctx = _ops.Context.get(self.device)
+        if self.whitening == "ciq":
+            # NGD-CIQ: q(f) carries a diagonal covariance (``predict_joint``): the blocks are diagonal too
+            self._rect_pd(params, x, D)
+            _, _, mu, varn = self._ciq_step(ctx, params, x, None, D, 1.0, "ELBO", None, False, False)
+            return mu, torch.diag_embed(varn.reshape(x.shape[0], -1))
+        if self.shared_directions:
+            if "natural_vec" in params:
+                m32, LS32, _, _ = self._natural_to_mu_chol(ctx, params["natural_vec"], params["natural_mat"])
+                params = {k: v for k, v in params.items() if not k.startswith("natural_")}
+                params["variational_mean"], params["chol_variational_covar"] = m32, LS32
+            params, _ = self._shared_expand(params)
+            self._no_middle = True
+            try:
+                return self._predict_chol(ctx, params, x, D, cache, blocks=True)
+            finally:
+                self._no_middle = False
+        return self._predict_chol(ctx, params, x, D, cache, blocks=True)
+
+    @torch.no_grad()
     def mean_predictor(self, params):
         """``MeanPredictor`` of the current parameter values: alpha = L^-T m from ONE transposed fp64 solve with the factor of
         ``_factor`` (jitter ladder included), packed with the inducing set by dsvgp_mean_prepare.  Natural parameters, shared
@@ -708,7 +734,7 @@ class ElboEngine:
         _ops.gemm(ctx, A_LOWER, root, eps.t().contiguous(), out)
         return out.t().to(mu.dtype) + mu
 
-    def _predict_chol(self, ctx, params, x, D, cache, joint=False):
+    def _predict_chol(self, ctx, params, x, D, cache, joint=False, blocks=False):
         # (the parameters arrive expanded; the evaluation cache below is keyed on them alone: calls with different direction
         #  counts on an unchanged model share the factor)
         rect_pd = self._rect_pd(params, x, D)
@@ -729,6 +755,9 @@ class ElboEngine:
             hyp, packZ, L, dims = self._factor(ctx, params, nrhs=x.shape[0] * ((self._pd(pz) if rect_pd is None else rect_pd) + 1))
             self._eval_cache = (key, hyp, packZ, L, dims, params) if cache else None
         packX, _, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=hit, rect_pd=rect_pd)
+        if blocks:                                                                 # (predict_blocks: no K_XX, nothing B' x B')
+            pd = self._pd(dims[2]) if rect_pd is None else rect_pd
+            return mu, _ops.predictive_blocks(ctx, A32, None if self._no_middle else W, pd, packX if pd > 0 else None, dims[1], hyp, True)
         if joint:
             M, d, p, Mp = dims
             B = x.shape[0]

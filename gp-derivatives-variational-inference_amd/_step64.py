@@ -377,6 +377,10 @@ class ElboEngine64(ElboEngine):
         var = self._prior_diag(x.shape[0], p, self._pd(p), ell, s, x) + KXX_JITTER + cs
         return mu0 + params["constant"].reshape(()), (var + noise).clamp_min(MIN_VARIANCE)
 
+    def predict_blocks(self, params, x, D, cache=False):
+        raise NotImplementedError("per-point covariance blocks in float64: dsvgp_predictive_blocks is a float32 kernel "
+                                  "(csrc/predict_blocks.hip); use the float32 engine, or the diagonal blocks of predict_joint")
+
     @torch.no_grad()
     def predict_joint(self, params, x, D, cache=False):
         """Mean [B'] and the full predictive covariance [B', B'] (fp64, likelihood noise on the diagonal):

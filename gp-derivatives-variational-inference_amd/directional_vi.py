@@ -718,3 +718,25 @@ def eval_values(test_dataset, model, likelihood, minibatch_size=1):
     means = torch.cat(means) if means else torch.zeros(0)
     variances = torch.cat(variances) if variances else torch.zeros(0)
     return means, variances
+
+
+def eval_gradients(test_dataset, model, likelihood, minibatch_size=1):
+    """Value and full gradient of f at every test point WITH their joint uncertainty: ``model.posterior_gradient`` over the
+    dataset in the batches of ``eval_values``.  Returns its named tuple -- value_mean [N], value_variance [N], gradient_mean
+    [N, d], gradient_covariance [N, d, d], value_gradient_covariance [N, d] (with likelihood noise on the variances) --
+    concatenated ON THE DEVICE: N d^2 floats stay where the caller's next step (descent probabilities, normal cones,
+    gradient-norm bounds) runs.  Whatever number of directions the model was trained with; d <= 95."""
+    device = model.variational_strategy.inducing_points.device
+    X, _ = _dataset_tensors(test_dataset, device, model.variational_strategy.inducing_points.dtype)
+    n_test = X.shape[0]
+
+    model.eval()
+    likelihood.eval()
+
+    parts = []
+    with torch.no_grad():
+        for start in range(0, n_test, minibatch_size):
+            parts.append(model.posterior_gradient(X[start:start + minibatch_size], likelihood=likelihood))
+    if not parts:
+        raise ValueError("eval_gradients needs at least one test point")
+    return type(parts[0])(*[torch.cat(field) for field in zip(*parts)])

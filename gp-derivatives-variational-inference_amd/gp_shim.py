@@ -6,6 +6,8 @@ protocol (``model(x, derivative_directions=D)`` -> distribution, ``likelihood(di
 ``mll(output, y)``) that ``directional_vi.train_gp`` relies on (directional_vi.py:25-65,172,216-219,245-246),
 and route the arithmetic to the HIP engine (``_step.ElboEngine``).  They contain no math of their own.
 """
+import collections
+
 import torch
 
 from . import _ops
@@ -135,6 +137,10 @@ class _ElboFunction(torch.autograd.Function):
         return tuple([None] * 8 + list(grads))
 
 
+PosteriorGradient = collections.namedtuple("PosteriorGradient", ["value_mean", "value_variance", "gradient_mean", "gradient_covariance",
+                                                                 "value_gradient_covariance"])
+
+
 class PredictiveDistribution:
     """What ``model(x, derivative_directions=D)`` returns: a handle whose ``mean`` / ``variance``
     (length B(p+1), interleaved) are produced on the GPU on demand."""
@@ -202,6 +208,20 @@ class PredictiveDistribution:
     def covariance_matrix(self):
         self._ensure_joint()
         return self._Sigma
+
+    @property
+    def point_covariances(self):
+        """[B, pd + 1, pd + 1]: the covariance of (f(x), D_1 f(x), ..., D_pd f(x)) at every point of the batch -- the diagonal
+        blocks of ``covariance_matrix`` without forming it (``ElboEngine.predict_blocks``: nothing of size B' x B').  With the
+        likelihood's noise on the block diagonals when the distribution carries a likelihood, q(f) itself otherwise."""
+        if getattr(self, "_blocks", None) is None:
+            lik = self.likelihood
+            params = self.model._param_dict(lik)
+            mu, blocks = self.model.engine.predict_blocks(params, self.x, self.D, cache=not self.model.training)
+            if lik is None:   # q(f) itself: remove the noise again
+                blocks.diagonal(dim1=1, dim2=2).sub_(torch.nn.functional.softplus(params["raw_noise"].reshape(())) + 1e-4)
+            self._mu, self._blocks = mu, blocks
+        return self._blocks
 
     def rsample(self, sample_shape=torch.Size(), base_samples=None):
         """mean + chol(Sigma) eps: exact Cholesky root on the GPU (fp64 blocked MFMA factorisation) where gpytorch switches
@@ -351,6 +371,22 @@ class ApproximateGP(torch.nn.Module):
         if x.dim() == 1:
             x = x.unsqueeze(-1)
         return self._mean_predictor().value_and_gradient(x)[1]
+
+    def posterior_gradient(self, x, likelihood=None):
+        """The distribution of (f(x), grad f(x)) at every point of x [B, d], whatever number of directions the model was trained
+        with: a named tuple of value_mean [B], value_variance [B], gradient_mean [B, d], gradient_covariance [B, d, d] and
+        value_gradient_covariance [B, d] (``likelihood`` given: with its noise on the variances).  ``posterior`` with ``eye(d)``
+        tiled over the points and its ``point_covariances``: u^T gradient_covariance u is the variance of the derivative along
+        u.  d <= 95 (float32 Cholesky-whitened models; CIQ whitening at d == p gives diagonal blocks)."""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        B, d = x.shape
+        if d > 95:
+            raise ValueError("posterior_gradient takes all d partial derivatives as data directions: at most 95, got d = %d" % d)
+        post = self.posterior(x, torch.eye(d, dtype=x.dtype, device=x.device).repeat(B, 1), likelihood)
+        blocks = post.point_covariances
+        mu = post.mean.reshape(B, d + 1)
+        return PosteriorGradient(mu[:, 0], blocks[:, 0, 0], mu[:, 1:], blocks[:, 1:, 1:], blocks[:, 1:, 0])
 
     def posterior(self, x, derivative_directions=None, likelihood=None):
         """Predictive distribution at x [B, d] over B (pd + 1) interleaved outputs, pd = len(derivative_directions) // B ANY

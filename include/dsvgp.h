@@ -314,6 +314,24 @@ size_t dsvgp_stats_workspace_bytes(int Mp, int ncols);
 int dsvgp_predictive_stats(dsvgp_ctx* ctx, const float* A, int64_t lda, const float* W, int64_t ldw,
                            int Mp, int ncols, int p, const float* m, const float* constant,
                            const float* hyp, float* mu, float* var, void* workspace);
+/* dsvgp_predictive_blocks: the q x q DIAGONAL BLOCKS (q = pd + 1) of the joint predictive covariance, one per data point, without
+ * K_XX and without anything of size B q x B q:
+ *   blocks[b] = s K_bb + (1e-4 + (with_noise ? noise : 0)) I + W_b^T W_b - A_b^T A_b        [B, q, q] float, contiguous
+ * with A = L^-1 K_ZX, W = L_S^T A, both [Mp, B q] float with interleaved columns (point b owns columns b q .. b q + pd), and the RBF
+ * block at r = 0, K_bb = [[1, 0], [0, v^_a . v^_b / ell^2]] (RBFKernelDirectionalGrad.py:96-102 with x1 = x2); its diagonal is the
+ * closed form of dsvgp_predictive_stats (s for the value row, s / ell^2 for a derivative row), so blocks[b][a][a] is var + noise of
+ * that call up to the order of the sums.  W == NULL or W == A: zero middle term (shared directions), nothing is read from A.
+ * PX: the data pack of dsvgp_pack_points made with pd directions per point ([B q, dsvgp_packed_width(d)]; only its unit direction
+ * rows are read; may be NULL at pd = 0).  The Gram of every strip of max(1, 96 / q) points runs on v_mfma_f32_16x16x4_f32 over
+ * row slices whose partial blocks go to `workspace` (dsvgp_predictive_blocks_workspace_bytes; 4-byte aligned) and are added in slice
+ * order: no floating-point atomics, every sum in an order fixed by (Mp, B, pd) alone -- two identical calls are bitwise equal and the
+ * result does not depend on the card.  The blocks are exactly symmetric.  The helper is a pure host function and returns 0 for
+ * arguments the entry refuses; the entry returns DSVGP_EINVAL for a null A / blocks / hyp (PX at pd > 0), Mp < 1, B < 1, d < 1, pd
+ * outside [0, 95], lda (ldw, with a W) below B q, or a workspace smaller than the helper's answer.                                 */
+size_t dsvgp_predictive_blocks_workspace_bytes(int Mp, int B, int pd);
+int dsvgp_predictive_blocks(dsvgp_ctx* ctx, const float* A, int64_t lda, const float* W, int64_t ldw, int Mp, int B, int pd,
+                            const float* PX, int d, const float* hyp, int with_noise, float* blocks, void* workspace,
+                            size_t workspace_bytes);
 /* per-output log-likelihood terms and their gradients.  mll_type 0 = ELBO, 1 = PLL.
  * out_scalars (device float[8]): {sum_ll, d_noise, d_constant, d_outputscale(diag part),
  *  d_lengthscale(diag part), 0,0,0}; mu_bar/var_bar are dLoss/dmu, dLoss/dvar with
