@@ -19,7 +19,7 @@ from . import shared_directional_vi  # noqa: F401
 from . import traditional_vi  # noqa: F401
 from ._step import ElboEngine, MeanPredictor, NotPSDError, NGD_PARAM_NAMES, PARAM_NAMES  # noqa: F401
 from ._step64 import ElboEngine64  # noqa: F401
-from .directional_vi import GPModel, TrainLoop, eval_gp, eval_gradients, eval_mean, eval_values, select_cols_of_y, setup_training, train_gp  # noqa: F401
+from .directional_vi import GPModel, TrainLoop, eval_gp, eval_gradient_nll, eval_gradients, eval_mean, eval_values, select_cols_of_y, setup_training, train_gp  # noqa: F401
 from .gp_shim import (GaussianLikelihood, NaturalVariationalDistribution, PredictiveLogLikelihood,  # noqa: F401
                       VariationalELBO)
 from .optim import NGD, FusedAdam  # noqa: F401

@@ -164,6 +164,9 @@ SIGNATURES = {
     "dsvgp_predictive_stats": (_i, [_p, _p, _l, _p, _l, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "dsvgp_predictive_blocks_workspace_bytes": (_z, [_i, _i, _i]),
     "dsvgp_predictive_blocks": (_i, [_p, _p, _l, _p, _l, _i, _i, _i, _p, _i, _p, _i, _p, _p, _z]),
+    "dsvgp_blocks_factor": (_i, [_p, _p, _i, _i, _d, _p, _p, _p, _p]),
+    "dsvgp_blocks_draw": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
+    "dsvgp_blocks_logpdf": (_i, [_p, _p, _p, _p, _p, _i, _i, _p, _p]),
     "dsvgp_likelihood_terms": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _d, _p, _p, _p, _p]),
     "dsvgp_abar": (_i, [_p, _p, _l, _p, _l, _i, _i, _p, _p, _p, _p, _l]),
     "dsvgp_rowdot": (_i, [_p, _p, _l, _i, _i, _p, _p]),

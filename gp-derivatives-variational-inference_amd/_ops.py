@@ -806,6 +806,94 @@ def predictive_blocks(ctx, A, W, pd, packX, d, hyp, with_noise, out=None):
     return out
 
 
+def _req_blocks(t, dtype, name, shape=None, dims=None):
+    # (dtype, shape and contiguity first: a bad argument is refused before any device is asked for)
+    if t.dtype != dtype:
+        raise TypeError("%s must be %s, got %s" % (name, dtype, t.dtype))
+    if dims is not None and t.dim() != dims:
+        raise ValueError("%s must be %d-D, got shape %s" % (name, dims, tuple(t.shape)))
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must have shape %s, got %s" % (name, tuple(shape), tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    return t
+
+
+def _blocks_q(t, name):
+    if t.dim() != 3 or t.shape[1] != t.shape[2]:
+        raise ValueError("%s must be [B, q, q], got shape %s" % (name, tuple(t.shape)))
+    B, q = int(t.shape[0]), int(t.shape[1])
+    if q < 1 or q > 96:
+        raise ValueError("at most 95 derivative directions per data point, got %d" % (q - 1))
+    return B, q
+
+
+def _on_gpu(*named):
+    for name, t in named:
+        if t is not None and not t.is_cuda:
+            raise _lib.DsvgpError("%s must live on the GPU: the DSVGP hot path has no CPU fallback" % name)
+
+
+def blocks_factor(ctx, blocks, jitter=0.0):
+    """(roots f64 [B, q, q], logdet f64 [B], info i32 [B], status i32 [1]) of float32 ``blocks`` [B, q, q], q <= 96: roots[b] the lower
+    Cholesky factor of (double) blocks[b] + jitter I (strict upper part 0), logdet[b] = 2 sum log diag, info[b] = 0 or k + 1 for a
+    failed pivot k (that block's root and logdet are NaN, every other block is unaffected), status = max(info).  Nothing is read
+    back here (dsvgp_blocks_factor, csrc/block_roots.hip)."""
+    _req_blocks(blocks, f32, "blocks")
+    B, q = _blocks_q(blocks, "blocks")
+    _on_gpu(("blocks", blocks))
+    roots = torch.empty(B, q, q, dtype=f64, device=blocks.device)
+    logdet = torch.empty(B, dtype=f64, device=blocks.device)
+    info = torch.empty(B, dtype=torch.int32, device=blocks.device)
+    status = torch.zeros(1, dtype=torch.int32, device=blocks.device)
+    if B == 0:                                                                        # (an empty tensor has no address to pass)
+        return roots, logdet, info, status
+    check(lib.dsvgp_blocks_factor(ctx.h, _ptr(blocks), B, q, float(jitter), _ptr(roots), _ptr(logdet), _ptr(info), _ptr(status)),
+          "dsvgp_blocks_factor")
+    return roots, logdet, info, status
+
+
+def blocks_draw(ctx, roots, mu, eps):
+    """out[n, B q] (float32) = mu + the per-point product roots[b] eps[i, b q : (b + 1) q]: ``roots`` f64 [B, q, q] of
+    ``blocks_factor``, ``mu`` float32 with B q entries, ``eps`` float32 [n, B q] (dsvgp_blocks_draw)."""
+    _req_blocks(roots, f64, "roots")
+    B, q = _blocks_q(roots, "roots")
+    _req_blocks(mu, f32, "mu")
+    if mu.numel() != B * q:
+        raise ValueError("mu has %d entries, not B q = %d x %d" % (mu.numel(), B, q))
+    _req_blocks(eps, f32, "eps", dims=2)
+    if eps.shape[1] != B * q:
+        raise ValueError("eps has %d columns, not B q = %d x %d" % (eps.shape[1], B, q))
+    _on_gpu(("roots", roots), ("mu", mu), ("eps", eps))
+    n = int(eps.shape[0])
+    out = torch.empty(n, B * q, dtype=f32, device=roots.device)
+    if n == 0 or B == 0:
+        return out
+    check(lib.dsvgp_blocks_draw(ctx.h, _ptr(roots), _ptr(mu), _ptr(eps), B, q, n, _ptr(out)), "dsvgp_blocks_draw")
+    return out
+
+
+def blocks_logpdf(ctx, roots, logdet, mu, y, want_z=True):
+    """(z float32 [B, q] or None, logp float32 [B]): z[b] = roots[b]^-1 (y[b] - mu[b]) and the joint normal log-density
+    -|z|^2 / 2 - logdet[b] / 2 - q log(2 pi) / 2 of every block; ``mu`` and ``y`` float32 with B q entries (dsvgp_blocks_logpdf)."""
+    _req_blocks(roots, f64, "roots")
+    B, q = _blocks_q(roots, "roots")
+    _req_blocks(logdet, f64, "logdet", shape=(B,))
+    _req_blocks(mu, f32, "mu")
+    _req_blocks(y, f32, "y")
+    if mu.numel() != B * q:
+        raise ValueError("mu has %d entries, not B q = %d x %d" % (mu.numel(), B, q))
+    if y.numel() != B * q:
+        raise ValueError("y has %d entries, not B q = %d x %d" % (y.numel(), B, q))
+    _on_gpu(("roots", roots), ("logdet", logdet), ("mu", mu), ("y", y))
+    z = torch.empty(B, q, dtype=f32, device=roots.device) if want_z else None
+    logp = torch.empty(B, dtype=f32, device=roots.device)
+    if B == 0:
+        return z, logp
+    check(lib.dsvgp_blocks_logpdf(ctx.h, _ptr(roots), _ptr(logdet), _ptr(mu), _ptr(y), B, q, _ptr(z), _ptr(logp)), "dsvgp_blocks_logpdf")
+    return z, logp
+
+
 def mean_weights_bytes(M, d):
     return int(lib.dsvgp_mean_weights_bytes(int(M), int(d)))
 

@@ -734,6 +734,36 @@ class ElboEngine:
         _ops.gemm(ctx, A_LOWER, root, eps.t().contiguous(), out)
         return out.t().to(mu.dtype) + mu
 
+    @torch.no_grad()
+    def block_roots(self, blocks):
+        """(roots f64 [B, q, q], logdet f64 [B]): the lower Cholesky factor and the log-determinant of every per-point block of
+        ``predict_blocks`` (float32 [B, q, q]; q <= 96), in fp64, with ``covariance_root``'s jitter ladder on the whole batch: plain
+        first, then chol_jitter 10^t (t = 0, 1, 2) on every block's diagonal; one host read per attempt.  A pure function of the
+        blocks (csrc/block_roots.hip): the diagonal blocks of a CIQ engine go through it as well."""
+        if blocks.dtype != f32:
+            raise TypeError("block_roots takes the float32 blocks of predict_blocks, got %s" % blocks.dtype)
+        ctx = _ops.Context.get(self.device) if blocks.is_cuda else None          # (a bad argument is refused before any device work)
+        jit = 0.0
+        for t in range(-1, 3):
+            if t >= 0:
+                jit = self.chol_jitter * 10.0 ** t
+            roots, logdet, _, status = _ops.blocks_factor(ctx, blocks, jit)
+            if blocks.shape[0] == 0 or int(status.item()) == 0:
+                return roots, logdet
+        raise NotPSDError("Matrix not positive definite after repeatedly adding jitter up to %g" % jit)
+
+    @torch.no_grad()
+    def block_draw(self, mu, roots, eps):
+        """mu + roots[b] eps_i[b] at every point b for every row eps_i of eps [n, B q]: draws that are exact within a point and
+        independent between points.  Returns float32 [n, B q]."""
+        return _ops.blocks_draw(_ops.Context.get(self.device) if roots.is_cuda else None, roots, mu, eps)
+
+    @torch.no_grad()
+    def block_log_prob(self, mu, roots, logdet, y):
+        """(z float32 [B, q], logp float32 [B]): the whitened residual roots[b]^-1 (y[b] - mu[b]) and the joint normal log-density
+        of y[b] under N(mu[b], roots[b] roots[b]^T) at every point."""
+        return _ops.blocks_logpdf(_ops.Context.get(self.device) if roots.is_cuda else None, roots, logdet, mu, y)
+
     def _predict_chol(self, ctx, params, x, D, cache, joint=False, blocks=False):
         # (the parameters arrive expanded; the evaluation cache below is keyed on them alone: calls with different direction
         #  counts on an unchanged model share the factor)

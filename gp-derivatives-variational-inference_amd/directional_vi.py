@@ -15,6 +15,7 @@ What is different underneath (MI355X-first):
 same engine; ``use_ciq=True`` additionally whitens with K_ZZ^{-1/2} by contour-integral quadrature + msMINRES
 (``CiqDirectionalGradVariationalStrategy``, ``csrc/ciq.hip``).
 """
+import collections
 import os
 import random
 import sys
@@ -740,3 +741,45 @@ def eval_gradients(test_dataset, model, likelihood, minibatch_size=1):
     if not parts:
         raise ValueError("eval_gradients needs at least one test point")
     return type(parts[0])(*[torch.cat(field) for field in zip(*parts)])
+
+
+GradientNLL = collections.namedtuple("GradientNLL", ["nll", "whitened", "value_nll"])
+
+
+def eval_gradient_nll(test_dataset, model, likelihood, minibatch_size=1):
+    """How well the model predicts the gradient JOINTLY with the value: for a test set whose ``y`` carries [f, grad f] (d + 1
+    columns, as the reference's datasets do), a named tuple, concatenated ON THE DEVICE, of
+    nll [N]: minus the joint log-density of [f, grad f] at every point under the likelihood (``model.gradient_log_prob``);
+    whitened [N, d + 1]: L^-1 (y - mean) with L the root of the point's covariance block -- standard normal if the joint
+    uncertainty is calibrated; value_nll [N]: the same for the function value alone (the q = 1 marginal), the per-point form of
+    the NLL the reference's harness prints.  Points are scored one by one, in the batches of ``eval_gradients``: nothing of size
+    B (d + 1) squared is formed.  Whatever number of directions the model was trained with; d <= 95."""
+    device = model.variational_strategy.inducing_points.device
+    X, Y = _dataset_tensors(test_dataset, device, model.variational_strategy.inducing_points.dtype)
+    n_test, d = X.shape
+    if Y.dim() != 2 or Y.shape[1] != d + 1:
+        raise ValueError("eval_gradient_nll needs y = [f, grad f] with d + 1 = %d columns, got %s" % (d + 1, tuple(Y.shape)))
+    if d > 95:
+        raise ValueError("eval_gradient_nll takes all d partial derivatives as data directions: at most 95, got d = %d" % d)
+    if n_test == 0:
+        raise ValueError("eval_gradient_nll needs at least one test point")
+
+    model.eval()
+    likelihood.eval()
+
+    nll, whitened, value_nll = [], [], []
+    with torch.no_grad():
+        for start in range(0, n_test, minibatch_size):
+            x, y = X[start:start + minibatch_size], Y[start:start + minibatch_size]
+            B = x.shape[0]
+            post = model.posterior(x, torch.eye(d, dtype=x.dtype, device=device).repeat(B, 1), likelihood)
+            z, logp = post._point_density(y)
+            # the value alone: the [0, 0] entries as B blocks of 1 x 1 through the same kernels
+            engine = model.engine
+            roots1, logdet1 = engine.block_roots(post.point_covariances[:, :1, :1].contiguous())
+            _, logp1 = engine.block_log_prob(post.mean.reshape(B, d + 1)[:, 0].contiguous(), roots1, logdet1,
+                                             y[:, 0].to(torch.float32).contiguous())
+            nll.append(-logp)
+            whitened.append(z)
+            value_nll.append(-logp1)
+    return GradientNLL(torch.cat(nll), torch.cat(whitened), torch.cat(value_nll))

@@ -223,6 +223,55 @@ class PredictiveDistribution:
             self._mu, self._blocks = mu, blocks
         return self._blocks
 
+    @property
+    def point_roots(self):
+        """(roots f64 [B, pd + 1, pd + 1], logdet f64 [B]): the lower Cholesky factor and the log-determinant of every block of
+        ``point_covariances`` (with the noise when the distribution carries a likelihood, q(f) otherwise), factorised in fp64 on
+        the GPU with the jitter ladder of ``rsample``'s root (``ElboEngine.block_roots``).  Formed once per distribution."""
+        if getattr(self, "_point_roots", None) is None:
+            self._point_roots = self.model.engine.block_roots(self.point_covariances)
+        return self._point_roots
+
+    def rsample_points(self, sample_shape=torch.Size(), base_samples=None):
+        """mean + L_b eps_b at every point b, L_b the root of the point's block (``point_roots``): draws of
+        (f(x), D_1 f(x), ..., D_pd f(x)) that are EXACT WITHIN a point and INDEPENDENT BETWEEN points -- nothing of size
+        B' x B' is formed.  ``sample`` / ``rsample`` are the jointly correlated form (and pay for the whole covariance).  Shape
+        ``sample_shape + [B(pd+1)]``, in the interleaved order of ``sample``; ``base_samples`` (that many standard normal numbers)
+        replaces ``torch.randn`` on the device."""
+        roots, _ = self.point_roots
+        mu = self._mu
+        n_out = mu.shape[0]
+        sample_shape = torch.Size(sample_shape)
+        n = int(sample_shape.numel()) if len(sample_shape) else 1
+        if base_samples is None:
+            eps = torch.randn(n, n_out, dtype=torch.float32, device=mu.device)
+        else:
+            eps = base_samples.to(device=mu.device, dtype=torch.float32).reshape(n, n_out).contiguous()
+        return self.model.engine.block_draw(mu, roots, eps).reshape(tuple(sample_shape) + (n_out,))
+
+    def sample_points(self, sample_shape=torch.Size(), base_samples=None):
+        """``rsample_points`` without a graph: per-point draws, independent between points (``sample``: jointly correlated)"""
+        with torch.no_grad():
+            return self.rsample_points(sample_shape, base_samples)
+
+    def _point_density(self, y):
+        roots, logdet = self.point_roots
+        mu = self._mu
+        y = y.to(device=mu.device, dtype=torch.float32).reshape(-1).contiguous()
+        if y.numel() != mu.numel():
+            raise ValueError("y has %d entries, the distribution B (pd + 1) = %d" % (y.numel(), mu.numel()))
+        return self.model.engine.block_log_prob(mu, roots, logdet, y)
+
+    def point_log_prob(self, y):
+        """[B]: the joint log-density of (y_b0, ..., y_b,pd) under N(mean_b, point_covariances[b]) at every point; ``y`` has
+        B (pd + 1) entries, interleaved or as [B, pd + 1].  Points are scored one by one: no correlation between points enters."""
+        return self._point_density(y)[1]
+
+    def point_whitened_residuals(self, y):
+        """[B, pd + 1]: L_b^-1 (y_b - mean_b) with L_b the root of the point's block -- standard normal entries if the joint
+        uncertainty of value and derivatives is calibrated.  ``y`` as for ``point_log_prob``."""
+        return self._point_density(y)[0]
+
     def rsample(self, sample_shape=torch.Size(), base_samples=None):
         """mean + chol(Sigma) eps: exact Cholesky root on the GPU (fp64 blocked MFMA factorisation) where gpytorch switches
         to a Lanczos root above ``max_cholesky_size``.  Shape ``sample_shape + [B(p+1)]``."""
@@ -387,6 +436,33 @@ class ApproximateGP(torch.nn.Module):
         blocks = post.point_covariances
         mu = post.mean.reshape(B, d + 1)
         return PosteriorGradient(mu[:, 0], blocks[:, 0, 0], mu[:, 1:], blocks[:, 1:, 1:], blocks[:, 1:, 0])
+
+    def _gradient_posterior(self, x, likelihood, what):
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        B, d = x.shape
+        if d > 95:
+            raise ValueError("%s takes all d partial derivatives as data directions: at most 95, got d = %d" % (what, d))
+        return self.posterior(x, torch.eye(d, dtype=x.dtype, device=x.device).repeat(B, 1), likelihood), B, d
+
+    def sample_gradients(self, x, num_samples, likelihood=None, base_samples=None):
+        """``num_samples`` draws of (f(x), grad f(x)) at every point of x [B, d]: (values [n, B], gradients [n, B, d]), exact
+        within a point (value and all d partial derivatives jointly) and independent between points
+        (``posterior(...).sample_points``; ``sample`` is the jointly correlated form).  q(f) without a ``likelihood``, with its
+        noise otherwise; ``base_samples``: n B (d + 1) standard normal numbers instead of ``torch.randn``.  Whatever number of
+        directions the model was trained with, through ``posterior_gradient``'s tiled ``eye(d)``; d <= 95."""
+        post, B, d = self._gradient_posterior(x, likelihood, "sample_gradients")
+        draws = post.sample_points(torch.Size([int(num_samples)]), base_samples).reshape(int(num_samples), B, d + 1)
+        return draws[:, :, 0], draws[:, :, 1:]
+
+    def gradient_log_prob(self, x, y, likelihood):
+        """[B]: the joint log-density of y[b] = (value, d partial derivatives) [B, d + 1] under the model's predictive
+        distribution of (f(x_b), grad f(x_b)) with the likelihood's noise, point by point (``posterior(...).point_log_prob``).
+        Whatever number of directions the model was trained with; d <= 95."""
+        post, B, d = self._gradient_posterior(x, likelihood, "gradient_log_prob")
+        if tuple(y.shape) != (B, d + 1):
+            raise ValueError("y must be [B, d + 1] = [%d, %d], got %s" % (B, d + 1, tuple(y.shape)))
+        return post.point_log_prob(y)
 
     def posterior(self, x, derivative_directions=None, likelihood=None):
         """Predictive distribution at x [B, d] over B (pd + 1) interleaved outputs, pd = len(derivative_directions) // B ANY

@@ -332,6 +332,25 @@ size_t dsvgp_predictive_blocks_workspace_bytes(int Mp, int B, int pd);
 int dsvgp_predictive_blocks(dsvgp_ctx* ctx, const float* A, int64_t lda, const float* W, int64_t ldw, int Mp, int B, int pd,
                             const float* PX, int d, const float* hyp, int with_noise, float* blocks, void* workspace,
                             size_t workspace_bytes);
+/* Per-point covariance roots (csrc/block_roots.hip): B blocks of q x q (q = pd + 1 in [1, 96]), such as those of
+ * dsvgp_predictive_blocks, used as distributions.  One team of 8 / 16 / 32 / 64 lanes per block, the block in LDS as [q][q + 1]
+ * doubles; float inputs are widened, every sum is a serial fp64 fma chain in ascending column order, the float outputs are rounded
+ * once.  A block's result is a function of that block alone: no floating-point atomics, two identical calls are bitwise equal, and the
+ * result of a sub-batch is bitwise the corresponding part of the whole batch's, on any card.
+ * dsvgp_blocks_factor: roots[b] = lower Cholesky factor (fp64, [B, q, q] contiguous, strict upper part written as 0) of
+ *   (double)blocks[b] + jitter I;  logdet[b] = 2 sum_i log roots[b][i][i];  info[b] = 0, or k + 1 when pivot k is <= 0 or not finite --
+ *   a numerical outcome: roots[b] and logdet[b] are then NaN and every other block is unaffected.  *status (device int, zeroed by the
+ *   call): max over info.
+ * dsvgp_blocks_draw: out[i, b q + a] = mu[b q + a] + sum_{c <= a} roots[b][a][c] eps[i, b q + c], i < n (mu [B q], eps and out
+ *   [n, B q] float, contiguous).
+ * dsvgp_blocks_logpdf: z[b] = roots[b]^-1 (y[b] - mu[b]) ([B, q] float; z may be NULL) and
+ *   logp[b] = -0.5 |z[b]|^2 - 0.5 logdet[b] - 0.5 q log(2 pi) ([B] float; |z|^2 from the unrounded z).
+ * DSVGP_EINVAL for a null pointer (z excepted), q outside [1, 96], B < 0 or n < 0; B == 0 or n == 0 returns 0 without a launch.   */
+int dsvgp_blocks_factor(dsvgp_ctx* ctx, const float* blocks, int B, int q, double jitter, double* roots, double* logdet, int* info,
+                        int* status);
+int dsvgp_blocks_draw(dsvgp_ctx* ctx, const double* roots, const float* mu, const float* eps, int B, int q, int n, float* out);
+int dsvgp_blocks_logpdf(dsvgp_ctx* ctx, const double* roots, const double* logdet, const float* mu, const float* y, int B, int q,
+                        float* z, float* logp);
 /* per-output log-likelihood terms and their gradients.  mll_type 0 = ELBO, 1 = PLL.
  * out_scalars (device float[8]): {sum_ll, d_noise, d_constant, d_outputscale(diag part),
  *  d_lengthscale(diag part), 0,0,0}; mu_bar/var_bar are dLoss/dmu, dLoss/dvar with
