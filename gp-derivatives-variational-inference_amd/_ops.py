@@ -961,6 +961,77 @@ def mean_predict(ctx, weights, M, d, x, D=None, pd=0, mean_out=None, grad_out=No
     return mean_out
 
 
+def paths_weights_bytes(M, d, F, n):
+    return int(lib.dsvgp_paths_weights_bytes(int(M), int(d), int(F), int(n)))
+
+
+def paths_workspace_bytes(M, d, F, n, B, want_grad):
+    return int(lib.dsvgp_paths_workspace_bytes(int(M), int(d), int(F), int(n), int(B), 1 if want_grad else 0))
+
+
+def paths_prepare(ctx, nu, w, omega, phase, Z, V, p, hyp, constant, center=None, weights=None):
+    """nu [n, M(p+1)], w [n, F], omega [F, d], phase [F] (float64) and the inducing set -> the packed fp32 weights of n posterior
+    paths (dsvgp_paths_prepare; a float32 tensor of dsvgp_paths_weights_bytes(M, d, F, n) bytes)"""
+    _req(Z, f32, "Z", 2)
+    M, d = Z.shape
+    _req(nu, f64, "nu", 2)
+    _req(w, f64, "w", 2)
+    _req(omega, f64, "omega", 2)
+    _req(phase, f64, "phase", 1)
+    n, F = w.shape
+    if nu.shape != (n, M * (p + 1)):
+        raise ValueError("nu must be [n, M (p + 1)] = [%d, %d], got %s" % (n, M * (p + 1), tuple(nu.shape)))
+    if omega.shape != (F, d) or phase.shape != (F,):
+        raise ValueError("omega / phase must be [F, d] / [F] = [%d, %d] / [%d], got %s / %s"
+                         % (F, d, F, tuple(omega.shape), tuple(phase.shape)))
+    if p > 0:
+        _req(V, f32, "V", 2)
+        if V.shape != (M * p, d):
+            raise ValueError("directions must be [M*p, d] = [%d, %d], got %s" % (M * p, d, tuple(V.shape)))
+    if not (Z.is_contiguous() and nu.is_contiguous() and w.is_contiguous() and omega.is_contiguous()) or (p > 0 and not V.is_contiguous()):
+        raise ValueError("Z, V, nu, w and omega must be contiguous")
+    if center is not None:
+        _req(center, f32, "center", 1)
+        if center.shape != (d,):
+            raise ValueError("center must have shape [%d]" % d)
+    constant = _req(constant.reshape(-1), f32, "constant")
+    nfl = (paths_weights_bytes(M, d, F, n) + 3) // 4
+    if nfl == 0:
+        raise ValueError("paths_prepare: M, d, F, n = %d, %d, %d, %d is not a shape the entry takes" % (M, d, F, n))
+    if weights is None:
+        weights = torch.empty(nfl, dtype=f32, device=Z.device)
+    _req(weights, f32, "weights", 1)
+    if weights.numel() < nfl:
+        raise ValueError("weights buffer too small: %d < %d floats" % (weights.numel(), nfl))
+    check(lib.dsvgp_paths_prepare(ctx.h, _ptr(nu), _ptr(w), _ptr(omega), _ptr(phase), _ptr(Z), _ptr(V if p > 0 else None), M, d, p, F, n,
+                                  _ptr(hyp), _ptr(constant), _ptr(center), _ptr(weights)), "dsvgp_paths_prepare")
+    return weights
+
+
+def paths_eval(ctx, weights, M, d, F, n, x, values=None, grads=None, workspace=None):
+    """values [n, B] and, when ``grads`` [n, B, d] is given, the gradients of n posterior paths at x [B, d] (dsvgp_paths_eval).
+    ``workspace``: uint8 tensor of dsvgp_paths_workspace_bytes(M, d, F, n, B, grads is not None) bytes (None when that is 0)."""
+    _req(x, f32, "x", 2)
+    _req(weights, f32, "weights", 1)
+    B = x.shape[0]
+    if x.shape[1] != d or not x.is_contiguous():
+        raise ValueError("x must be a contiguous [B, %d] tensor, got %s" % (d, tuple(x.shape)))
+    if values is None:
+        values = torch.empty(n, B, dtype=f32, device=x.device)
+    _req(values, f32, "values", 2)
+    if values.shape != (n, B) or not values.is_contiguous():
+        raise ValueError("values must be a contiguous [%d, %d] tensor" % (n, B))
+    if grads is not None:
+        if not grads.is_cuda or grads.dtype != f32 or grads.shape != (n, B, d) or not grads.is_contiguous():
+            raise ValueError("grads must be a contiguous float32 [%d, %d, %d] tensor on the GPU" % (n, B, d))
+    need = paths_workspace_bytes(M, d, F, n, B, grads is not None)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        raise ValueError("paths_eval workspace too small: %d bytes needed" % need)
+    check(lib.dsvgp_paths_eval(ctx.h, _ptr(weights), M, d, F, n, _ptr(x), B, _ptr(values), _ptr(grads),
+                               _ptr(workspace if need else None)), "dsvgp_paths_eval")
+    return values
+
+
 def likelihood_terms(ctx, mu, var, y, p, hyp, mll_type, global_rows, mu_bar, var_bar, varn, scalars):
     check(lib.dsvgp_likelihood_terms(ctx.h, _ptr(mu), _ptr(var), _ptr(_req(y, f32, "y", 1)), mu.shape[0], p, _ptr(hyp),
                                      int(mll_type), float(global_rows), _ptr(mu_bar), _ptr(var_bar), _ptr(varn),

@@ -15,6 +15,7 @@ K_XZ is not assembled (it is K_ZX^T) and the second triangular solve of the refe
 repeated (A_t == A); everything else keeps the reference's arithmetic precision: fp32 model, fp64
 Cholesky / triangular solves.
 """
+import math
 import os
 import time
 
@@ -98,6 +99,103 @@ class MeanPredictor:
     def value_and_gradient(self, x):
         """(mu_f [B], grad mu_f [B, d]); the gradient carries no constant"""
         return self._run(x, None, 0, True)
+
+
+class SamplePaths:
+    """n draws of the posterior FUNCTION of a frozen model (``ElboEngine.sample_paths``; csrc/paths.hip): each can be evaluated, with
+    its exact gradient, at any number of points in any number of batches -- f_s(x) = c + sum_j w_js phi_j(x) + K_xZ' nu_s (Matheron's
+    rule with a random-Fourier-feature prior), O((M + F) d) per point and sample, nothing of size B' x B'.  Holds its own weights and
+    (d > 32) workspace; valid for the parameter values and the draws it was built from.  d <= 32: the result of (sample, point) does
+    not depend on the batch it is evaluated in."""
+
+    def __init__(self, device, weights, M, d, F, n, constant, workspace_budget=1 << 30):
+        self.device = torch.device(device)
+        self.weights, self.M, self.d = weights, int(M), int(d)
+        self.num_features, self.num_samples = int(F), int(n)
+        self.constant = constant                    # device scalar: the c on every derivative row of ``__call__``
+        self.workspace_budget = int(workspace_budget)
+        self._ws = None
+
+    def _rows(self, B, want_grad):
+        """rows per call of the C entry: all of them when the workspace fits the budget (d <= 32: it is empty), else the largest
+        block that does (sample groups are cut inside the entry)"""
+        need = lambda r: _ops.paths_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, r, want_grad)
+        if self.d <= 32 or 0 < need(B) <= self.workspace_budget:
+            return B
+        lo, hi = 1, B                               # need(r) grows with r; 0 = refused (an intermediate past 2^31 entries)
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if 0 < need(mid) <= self.workspace_budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
+    def _workspace(self, rows, want_grad):
+        need = _ops.paths_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, rows, want_grad)
+        if need == 0:
+            return None
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _run(self, x, want_grad):
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        if not x.is_cuda:
+            raise _lib.DsvgpError("x must live on the GPU: the DSVGP hot path has no CPU fallback")
+        ctx = _ops.Context.get(self.device)
+        x = x.contiguous()
+        B, n, d = x.shape[0], self.num_samples, self.d
+        values = torch.empty(n, B, dtype=f32, device=self.device)
+        grads = torch.empty(n, B, d, dtype=f32, device=self.device) if want_grad else None
+        if B == 0:
+            return values, grads
+        rows = self._rows(B, want_grad)
+        if rows >= B:
+            _ops.paths_eval(ctx, self.weights, self.M, d, self.num_features, n, x, values, grads, self._workspace(B, want_grad))
+            return values, grads
+        for r0 in range(0, B, rows):                # row blocks: the entry writes [n, rows] contiguous
+            r1 = min(B, r0 + rows)
+            v = torch.empty(n, r1 - r0, dtype=f32, device=self.device)
+            g = torch.empty(n, r1 - r0, d, dtype=f32, device=self.device) if want_grad else None
+            _ops.paths_eval(ctx, self.weights, self.M, d, self.num_features, n, x[r0:r1], v, g, self._workspace(r1 - r0, want_grad))
+            values[:, r0:r1] = v
+            if want_grad:
+                grads[:, r0:r1] = g
+        return values, grads
+
+    @torch.no_grad()
+    def values(self, x):
+        """f_s(x) [n, B]"""
+        return self._run(x, False)[0]
+
+    @torch.no_grad()
+    def values_and_gradients(self, x):
+        """(f_s(x) [n, B], grad f_s(x) [n, B, d]); the gradient carries no constant"""
+        return self._run(x, True)
+
+    @torch.no_grad()
+    def __call__(self, x, derivative_directions=None):
+        """[n, B (pd + 1)] in ``sample``'s interleaved layout: the value row of every point, then c + w^ . grad f_s for each of its
+        pd = len(derivative_directions) // B directions (rows normalised; the constant on every row, as the predictive mean has it).
+        ``None``: the values."""
+        D = derivative_directions
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        B = x.shape[0]
+        if D is None or D.numel() == 0 or B == 0:
+            return self.values(x)
+        if D.dim() != 2 or D.shape[1] != self.d or D.shape[0] % B:
+            raise ValueError("derivative directions must be [B * pd, d] = [%d * pd, %d], got %s" % (B, self.d, tuple(D.shape)))
+        if not D.is_cuda:
+            raise _lib.DsvgpError("derivative_directions must live on the GPU: the DSVGP hot path has no CPU fallback")
+        pd = D.shape[0] // B
+        vals, grads = self._run(x, True)
+        Dn = (D / D.norm(dim=1, keepdim=True)).to(f32).reshape(B, pd, self.d)
+        rows = torch.einsum("nbk,bak->nba", grads, Dn) + self.constant.reshape(())
+        return torch.cat([vals.unsqueeze(-1), rows], dim=2).reshape(self.num_samples, B * (pd + 1))
 
 
 class ElboEngine:
@@ -197,6 +295,7 @@ class ElboEngine:
         self.ciq_stats = {}                 # lmin / lmax / iterations of the last CIQ forward + backward
         self.ciq_eig_bounds = None          # (lmin, lmax) to build the quadrature on instead of the 20-step Lanczos estimate
         self._eval_cache = None
+        self._ladder_jitter = 0.0
         # True while a step is being captured into / replayed from a HIP graph (directional_vi.TrainLoop): nothing may read
         # device results on the host -- the potrf status is checked by the caller one step later, and the Adam kernels of the
         # captured step are guarded by the status word instead
@@ -341,6 +440,7 @@ class ElboEngine:
             return
         hyp, packZ, L, (M, d, p, Mp), info = self._pending
         self._pending = None
+        self._ladder_jitter = 0.0                       # diagonal the ladder added on top of kzz_jitter (sample_paths reads it)
         self._status_ready.synchronize()
         self._hyp_host = self._host_status[:hyp.numel()].tolist()      # host copy of (ell, s, noise)
         if int(self._host_info[0]) == 0:
@@ -352,6 +452,7 @@ class ElboEngine:
             _ops.add_diag_(ctx, L, self.chol_jitter * (10 ** t))
             self._potrf_ws = self._potrf_and_inverse(ctx, L, info, self._inverse_ws, Mp + 1, "kzz")
             if int(info.item()) == 0:
+                self._ladder_jitter = self.chol_jitter * (10 ** t)
                 return
         raise NotPSDError("Matrix not positive definite after repeatedly adding jitter up to %.1e."
                           % (self.chol_jitter * 10 ** (CHOL_TRIES - 1)))
@@ -667,6 +768,76 @@ class ElboEngine:
                                     params["inducing_directions"].contiguous() if p > 0 else None, p, hyp,
                                     params["constant"], self.center)
         return MeanPredictor(self.device, weights, M, d, values_only=self.data_outputs == "values")
+
+    @torch.no_grad()
+    def sample_paths(self, params, num_samples, num_features=2048, generator=None, base_samples=None):
+        """``SamplePaths``: ``num_samples`` draws of the posterior function of the current parameter values, by Matheron's rule with
+        ``num_features`` random Fourier features:  f_s(x) = c + sum_j w_js phi_j(x) + K_xZ' nu_s,
+            nu_s = L^-T [m + L_S eps_s - L^-1 (Phi_Z' w_s + sqrt(j) eta_s)],   K~ = s K_ZZ + j I = L L^T  (j: every diagonal added)
+        ``base_samples``: dict of omega [F, d], phase [F], w [n, F], eps [n, M'], eta [n, M'] (any float dtype, CPU or device);
+        absent: drawn on the device with ``generator``.  The factor is ``_factor``'s (jitter ladder included); Phi_Z' and the two
+        solves run in float64 once per call, dsvgp_paths_prepare packs the fp32 weights.  Natural parameters, shared directions, p = 0
+        and p = d are the same code; the evaluation cache of ``predict`` is dropped (it refactors on its next call)."""
+        if self.whitening == "ciq":
+            raise NotImplementedError("pathwise posterior samples with CIQ whitening: nu there needs K^{-1/2} by msMINRES "
+                                      "(contour-integral quadrature), which is not built; use predict_joint() and its samples")
+        n, F = int(num_samples), int(num_features)
+        if n < 1 or F < 1:
+            raise ValueError("sample_paths needs num_samples >= 1 and num_features >= 1, got %d and %d" % (n, F))
+        ctx = _ops.Context.get(self.device)
+        self._eval_cache = None
+        if "natural_vec" in params:
+            m32, LS32, _, _ = self._natural_to_mu_chol(ctx, params["natural_vec"], params["natural_mat"])
+            params = {k: v for k, v in params.items() if not k.startswith("natural_")}
+            params["variational_mean"], params["chol_variational_covar"] = m32, LS32
+        if self.shared_directions:
+            params, _ = self._shared_expand(params)
+        Z, V = params["inducing_points"].contiguous(), params["inducing_directions"].contiguous()
+        M, d = Z.shape
+        p = V.shape[0] // M if M else 0
+        Mp = M * (p + 1)
+        m, LS = params["variational_mean"], params["chol_variational_covar"]
+        if m.shape[0] != Mp:
+            raise ValueError("q(u) has %d values, the inducing set M (p + 1) = %d" % (m.shape[0], Mp))
+        dev = self.device
+        if base_samples is not None:
+            shapes = {"omega": (F, d), "phase": (F,), "w": (n, F), "eps": (n, Mp), "eta": (n, Mp)}
+            draws = {}
+            for k, shp in shapes.items():
+                if k not in base_samples:
+                    raise ValueError("base_samples needs %s, missing %r" % (sorted(shapes), k))
+                t = torch.as_tensor(base_samples[k]).to(device=dev, dtype=f64)
+                if tuple(t.shape) != shp:
+                    raise ValueError("base_samples[%r] must have shape %s, got %s" % (k, shp, tuple(t.shape)))
+                draws[k] = t.contiguous()
+        else:
+            rn = lambda *shape: torch.randn(*shape, dtype=f64, device=dev, generator=generator)
+            draws = {"omega": rn(F, d), "phase": 2.0 * math.pi * torch.rand(F, dtype=f64, device=dev, generator=generator),
+                     "w": rn(n, F), "eps": rn(n, Mp), "eta": rn(n, Mp)}
+        hyp, packZ, L, _ = self._factor(ctx, params, sync=True, nrhs=max(n, Mp + 1))
+        jitter = float(self.kzz_jitter) + float(self._ladder_jitter)
+        # Phi_Z' [M', F] (float64, interleaved like K_ZZ): phi_j(z_i), then per direction -sqrt(2 s / F) sin(.) (omega_j . v^_ia) / ell
+        ell, s = hyp[0].to(f64), hyp[1].to(f64)
+        amp = torch.sqrt(2.0 * s / F)
+        Z64 = Z.to(f64)
+        arg = Z64 @ draws["omega"].t() / ell + draws["phase"]
+        Phi = torch.empty(M, p + 1, F, dtype=f64, device=dev)
+        Phi[:, 0] = amp * torch.cos(arg)
+        if p > 0:
+            V64 = V.to(f64)
+            Vn = (V64 / V64.norm(dim=1, keepdim=True)).reshape(M, p, d)
+            Phi[:, 1:] = (-amp / ell) * torch.sin(arg).unsqueeze(1) * (Vn @ draws["omega"].t())
+        rhs = (Phi.reshape(Mp, F) @ draws["w"].t() + math.sqrt(jitter) * draws["eta"].t()).contiguous()
+        X = torch.empty(Mp, n, dtype=f64, device=dev)
+        _ops.trsm(ctx, L, rhs, False, X, None, self.trsm_nb, self._inverse_ws, reuse_inverse=True)      # L^-1 (Phi_Z' W^T + sqrt(j) H^T)
+        # (shared directions: q(u)'s covariance does not reach the predictive -- the unit factor of ``_shared_expand`` stands in)
+        LSe = draws["eps"].t() if self.shared_directions else torch.tril(LS).to(f64) @ draws["eps"].t()
+        T = (m.to(f64).reshape(Mp, 1) + LSe - X).contiguous()
+        nu = torch.empty(Mp, n, dtype=f64, device=dev)
+        _ops.trsm(ctx, L, T, True, nu, None, self.trsm_nb, self._inverse_ws, reuse_inverse=True)        # all n columns of nu
+        weights = _ops.paths_prepare(ctx, nu.t().contiguous(), draws["w"], draws["omega"], draws["phase"], Z, V if p > 0 else None, p,
+                                     hyp, params["constant"], self.center)
+        return SamplePaths(self.device, weights, M, d, F, n, params["constant"].detach().reshape(()).to(f32).clone())
 
     @torch.no_grad()
     def whiten_legacy(self, params):

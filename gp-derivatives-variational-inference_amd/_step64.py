@@ -353,6 +353,10 @@ class ElboEngine64(ElboEngine):
         raise NotImplementedError("the posterior-mean predictor (csrc/predict_mean.hip) is built for the float32 model mode only; "
                                   "use predict() / likelihood(model(x, derivative_directions=D)).mean")
 
+    def sample_paths(self, params, num_samples, num_features=2048, generator=None, base_samples=None):
+        raise NotImplementedError("pathwise posterior samples (csrc/paths.hip) are built for the float32 model mode only, not for "
+                                  "float64 models; use predict_joint() and its samples")
+
     @torch.no_grad()
     def predict(self, params, x, D, cache=False):
         self._refuse_rect(params, x, D)

@@ -1,0 +1,112 @@
+// Index arithmetic of the pathwise posterior sampler (paths.hip): the layout of the packed weights, the chunking / ownership / LDS
+// offsets of the fused kernel (d <= 32) and the workspace layout and sample grouping of the GEMM-composed route (any other d).  Plain
+// integer arithmetic, shared between the kernels, their launcher and the host check tools/paths_check.cpp (which emulates every thread of
+// the fused kernel serially and shows that every (sample, point, i) and (sample, point, j) is visited exactly once and that every LDS
+// and global offset stays in bounds).
+//
+// Fused kernel: a workgroup of PP_NW waves owns PP_TP = 64 test points (lane = point) and a GROUP of NS = paths_ns(D) samples
+// (grid = [point tiles, sample groups]).  The M inducing points and then the F features go through LDS in chunks of PP_CH = 64; wave w
+// owns the entries w, w + PP_NW, ... of every chunk.  One LDS array serves three images in turn:
+//   inducing chunk   Z~[CH][D] | G'[NS][CH][D] | a[NS][CH]
+//   feature chunk    Om[CH][D] | phase[CH] | wq[NS][CH]
+//   reduction        red[NS][TP][D + 1]  (row stride D + 1 is odd: lane-strided accesses fall on distinct banks)
+// the first is the largest.  Every rule below depends on the shapes alone, never on B, n or the card: the order of every sum of a
+// (sample, point) is fixed by M, F and d.
+#pragma once
+#include <stddef.h>
+
+constexpr int PP_FUSED_MAX_D = 32;  // the fused kernel's bound on d
+constexpr int PP_TP = 64;           // test points per workgroup (one per lane)
+constexpr int PP_NW = 8;            // waves per workgroup = slices of every chunk
+constexpr int PP_CH = 64;           // inducing points / features per LDS chunk
+constexpr int PP_NS_MAX = 8;        // samples per group at most
+constexpr int PP_MAX_P = 95;        // directions per inducing point (the bound of dsvgp_pack_points)
+
+constexpr int paths_pad4(int v) { return (v + 3) & ~3; }
+constexpr size_t paths_pad4z(size_t v) { return (v + 3) & ~(size_t)3; }
+
+// samples per group of the fused kernel at row length D = pad4(d): NS (D + 1) accumulators next to x~[D], r[D] and ~50 registers of
+// addresses and temporaries inside the 256 a wave has at two waves per SIMD
+constexpr int paths_ns(int D) {
+    int ns = (176 - 2 * D) / (D + 1);
+    ns = ns < PP_NS_MAX ? ns : PP_NS_MAX;
+    return ns > 1 ? ns : 1;
+}
+
+// LDS float offsets of the three images (template parameter D)
+struct PathsLds { int o_z, o_g, o_a, o_om, o_ph, o_w, o_red, floats; };
+constexpr PathsLds paths_lds(int D) {
+    const int NS = paths_ns(D);
+    PathsLds l{};
+    l.o_z = 0; l.o_g = PP_CH * D; l.o_a = l.o_g + NS * PP_CH * D;
+    l.o_om = 0; l.o_ph = PP_CH * D; l.o_w = l.o_ph + PP_CH;
+    l.o_red = 0;
+    l.floats = l.o_a + NS * PP_CH;                        // >= PP_CH (D + 1 + NS) and >= NS PP_TP (D + 1)
+    return l;
+}
+
+// packed weights (floats): hdr[8] = {ell, s, c, 1/ell, s/ell, 0, 0, 0} | center[ldw] | nz[Mr] = |z~|^2 | Z~[M][ldw] |
+// Om[F][ldw] = omega / 2 pi | phase[Fr] (revolutions, in [0, 1]) | a[n][Mr] | a'[n][Mr] = a - z~.G' | wq[n][Fr] = sqrt(2 / (s F)) w |
+// G'[n][M][ldw] = g / ell;   ldw = pad4(d), Mr = pad4(M), Fr = pad4(F); padding columns are zero
+struct PathsWeights { int ldw, Mr, Fr; size_t o_center, o_nz, o_z, o_om, o_ph, o_a, o_ap, o_wq, o_g, total; };
+inline PathsWeights paths_weights(int M, int d, int F, int n) {
+    PathsWeights w{};
+    w.ldw = paths_pad4(d); w.Mr = paths_pad4(M); w.Fr = paths_pad4(F);
+    w.o_center = 8;
+    w.o_nz = w.o_center + w.ldw;
+    w.o_z = w.o_nz + w.Mr;
+    w.o_om = w.o_z + (size_t)M * w.ldw;
+    w.o_ph = w.o_om + (size_t)F * w.ldw;
+    w.o_a = w.o_ph + w.Fr;
+    w.o_ap = w.o_a + (size_t)n * w.Mr;
+    w.o_wq = w.o_ap + (size_t)n * w.Mr;
+    w.o_g = w.o_wq + (size_t)n * w.Fr;
+    w.total = w.o_g + (size_t)n * M * w.ldw;
+    return w;
+}
+
+// composed route: workspace (floats) of one call on B rows; samples go through in groups of ng.
+//   shared   X~[B][ldw] | xn[Br] | K[B][ldM] | C[B][ldF] | VP[B][ldn]                       (+ S[B][ldF] with gradients)
+//   group    S2[B][ld2] (ld2 = pad4(ng M)) | P[ng][B][ldM] | sigma[ng][Br]
+//            (+ O1[ng][B][ldw] | O2[ng][B][ldw] | WO[F][ng ldw] | GP[B][ng ldw] with gradients)
+struct PathsWork {
+    int ldw, ldM, ldF, ldn, ld2, ng;
+    size_t Br, o_x, o_xn, o_k, o_c, o_vp, o_s, o_s2, o_p, o_sig, o_o1, o_o2, o_wo, o_gp, total;
+};
+constexpr size_t PP_GROUP_FLOATS = (size_t)1 << 27;      // the group part stays under 512 MiB unless one sample alone needs more
+constexpr long long PP_IDX_MAX = 0x7fffffffLL;           // intermediates are indexed with 32 bits
+
+// 0, or -1 for a shape the composed route refuses (an intermediate would pass 2^31 entries: split the batch)
+inline int paths_work(int M, int d, int F, int n, int B, int want_grad, PathsWork& s) {
+    if (M < 1 || d < 1 || F < 1 || n < 1 || B < 1) return -1;
+    s = PathsWork{};
+    s.ldw = paths_pad4(d); s.ldM = paths_pad4(M); s.ldF = paths_pad4(F); s.ldn = paths_pad4(n);
+    s.Br = paths_pad4z((size_t)B);
+    const size_t per = (size_t)B * M + (size_t)B * s.ldM + s.Br +
+                       (want_grad ? (size_t)3 * B * s.ldw + (size_t)F * s.ldw : 0);
+    size_t ng = PP_GROUP_FLOATS / per;
+    ng = ng < (size_t)n ? ng : (size_t)n;
+    ng = ng < 65535 ? ng : 65535;                         // (a grid dimension)
+    s.ng = ng > 1 ? (int)ng : 1;
+    s.ld2 = paths_pad4(s.ng * M);
+    const long long big[] = {(long long)B * s.ld2, (long long)s.ng * B * s.ldM, (long long)B * s.ldF, (long long)s.ng * B * s.ldw,
+                             (long long)F * s.ng * s.ldw, (long long)B * s.ldn, (long long)B * d};
+    for (long long v : big)
+        if (v > PP_IDX_MAX) return -1;
+    size_t o = 0;
+    s.o_x = o;   o += (size_t)B * s.ldw;
+    s.o_xn = o;  o += s.Br;
+    s.o_k = o;   o += (size_t)B * s.ldM;
+    s.o_c = o;   o += (size_t)B * s.ldF;
+    s.o_vp = o;  o += (size_t)B * s.ldn;
+    s.o_s = o;   o += want_grad ? (size_t)B * s.ldF : 0;
+    s.o_s2 = o;  o += (size_t)B * s.ld2;
+    s.o_p = o;   o += (size_t)s.ng * B * s.ldM;
+    s.o_sig = o; o += (size_t)s.ng * s.Br;
+    s.o_o1 = o;  o += want_grad ? (size_t)s.ng * B * s.ldw : 0;
+    s.o_o2 = o;  o += want_grad ? (size_t)s.ng * B * s.ldw : 0;
+    s.o_wo = o;  o += want_grad ? (size_t)F * s.ng * s.ldw : 0;
+    s.o_gp = o;  o += want_grad ? (size_t)B * s.ng * s.ldw : 0;
+    s.total = o;
+    return 0;
+}

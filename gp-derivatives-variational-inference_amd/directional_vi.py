@@ -697,6 +697,32 @@ def eval_mean(test_dataset, model, num_directions=1, minibatch_size=1, minibatch
     return torch.cat(means) if means else torch.zeros(0)
 
 
+def eval_paths(dataset_or_tensor, paths, minibatch_size, gradients=False):
+    """Posterior function draws (``model.sample_paths(...)``) over a whole dataset (its x) or a tensor [N, d], in minibatches: the values
+    [n, N] concatenated ON THE DEVICE and, with ``gradients=True``, also the gradients [n, N, d].  The same functions in every
+    batch: for d <= 32 the result does not depend on ``minibatch_size``."""
+    if torch.is_tensor(dataset_or_tensor):
+        X = dataset_or_tensor.to(device=paths.device, dtype=torch.float32)
+        if X.dim() == 1:
+            X = X.unsqueeze(-1)
+    else:
+        X, _ = _dataset_tensors(dataset_or_tensor, paths.device, torch.float32)
+    minibatch_size = max(int(minibatch_size), 1)
+    vals, grads = [], []
+    for start in range(0, X.shape[0], minibatch_size):
+        xb = X[start:start + minibatch_size]
+        if gradients:
+            v, g = paths.values_and_gradients(xb)
+            grads.append(g)
+        else:
+            v = paths.values(xb)
+        vals.append(v)
+    if not vals:
+        raise ValueError("eval_paths needs at least one point")
+    values = torch.cat(vals, dim=1)
+    return (values, torch.cat(grads, dim=1)) if gradients else values
+
+
 def eval_values(test_dataset, model, likelihood, minibatch_size=1):
     """``eval_gp(...)`` followed by ``[::p+1]``: predictive means / variances (with likelihood noise) of the FUNCTION VALUES,
     what the reference's callers keep of it (tests/test_dsvgp.py:99-101, the experiments' MSE / NLL reports).  Same batching and

@@ -406,6 +406,20 @@ class ApproximateGP(torch.nn.Module):
         self.__dict__["_mean_cache"] = (key, engine, pred) if not self.training else None
         return pred
 
+    def sample_paths(self, num_samples, num_features=2048, generator=None, base_samples=None):
+        """``num_samples`` draws of the posterior FUNCTION f for the current parameters (``ElboEngine.sample_paths``): a
+        ``SamplePaths`` whose ``values(x)`` [n, B], ``values_and_gradients(x)`` and ``paths(x, derivative_directions)`` evaluate the
+        SAME functions at any number of points in any number of batches -- what a Thompson sampler takes from
+        ``preds.sample(torch.Size([n]))`` without anything of size B' x B'.  Paths are of f: a likelihood's white noise is the
+        caller's to add.  An explicit object: nothing is cached on the model.  Not differentiable."""
+        engine = self.engine            # (ElboEngine64 -- a float64 model -- refuses: NotImplementedError)
+        vs = self.variational_strategy
+        if hasattr(vs, "_strategy_is_updated") and not vs._strategy_is_updated():
+            vs._whiten_legacy_parameters()
+        if self.training and hasattr(vs, "_maybe_init"):
+            vs._maybe_init()
+        return engine.sample_paths(self._param_dict(None), num_samples, num_features, generator, base_samples)
+
     def posterior_mean(self, x, derivative_directions=None):
         """Predictive mean at x [B, d]: [B (pd + 1)] interleaved with pd = len(derivative_directions) // B rows per point
         (``None``: function values only); equals ``likelihood(self(x, derivative_directions=D)).mean`` without assembling

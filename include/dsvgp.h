@@ -742,6 +742,38 @@ int dsvgp_mean_prepare(dsvgp_ctx* ctx, const double* alpha, const float* Z, cons
 int dsvgp_mean_predict(dsvgp_ctx* ctx, const float* weights, int M, int d, const float* x, int B, const float* D, int pd,
                        float* mean_out, float* grad_out, void* workspace);
 
+/* ---- pathwise posterior samples (csrc/paths.hip): draws of the posterior FUNCTION, evaluated with their exact gradient at any number
+ * of points in any number of batches -- what the reference's Thompson samplers take from `preds.sample(torch.Size([n]))`
+ * (experiments/rover/test_turbo.py:138, experiments/GNN_bo/gcn_turbo.py:239,341, turbo1*.py:216-227), without anything of size B' x B'.
+ * Matheron's rule with a random-Fourier-feature prior (K~ = s K_ZZ + j I = L L^T, j the TOTAL diagonal added; u = L (m + L_S eps)):
+ *     f_s(x) = c + sum_j w_js phi_j(x) + K_xZ' nu_s,   nu_s = L^-T [m + L_S eps_s - L^-1 (Phi_Z' w_s + sqrt(j) eta_s)]
+ *     phi_j(x) = sqrt(2 s / F) cos(omega_j . x / ell + b_j),   omega_j ~ N(0, I_d), b_j ~ U[0, 2 pi), w_s, eps_s, eta_s standard normal
+ * The update term K_xZ' nu_s is the posterior mean's closed form above with alpha -> nu_s; the caller forms nu [n, M(p+1)] in fp64 (two
+ * dsvgp_trsm calls per parameter state and sample set).
+ *   dsvgp_paths_prepare   nu[n, M(p+1)], w[n, F], omega[F, d], phase[F] (double), Z, V (raw directions, normalised here; NULL when
+ *                         p = 0; p <= 95), hyp, constant, center[d] (NULL = 0) -> weights: dsvgp_paths_weights_bytes(M, d, F, n) bytes,
+ *                         16-byte aligned, fp32 from fp64 sums: {ell, s, c, ..}, center, |z~|^2, Z~, the feature table in REVOLUTIONS
+ *                         (omega_j / 2 pi against x~ = (x - center) / ell; b_j plus the centre's contribution reduced mod 1 in fp64), and
+ *                         per sample a, a - z~.g/ell, sqrt(2 / (s F)) w, G/ell.  Rows padded to multiples of 4 floats.  Three launches.
+ *   dsvgp_paths_eval      x[B, d] -> values[n, B], grads (NULL or [n, B, d]) = grad f_s (without the constant).  No host read, no
+ *                         synchronisation, no allocation, queued on the context's stream.  d <= 32: ONE fused kernel (a workgroup owns 64
+ *                         points and a group of samples, inducing points and features in LDS chunks, accumulators in registers;
+ *                         workspace may be NULL): the result of (sample, point) is a function of that sample and that point alone, so a
+ *                         path evaluated in batches, or prepared with other samples, returns the same bits.  Any other d: the same sums
+ *                         in GEMM shape through `workspace` (dsvgp_paths_workspace_bytes(M, d, F, n, B, want_grad) bytes, 16-byte aligned;
+ *                         0 for d <= 32) on the fp32 MFMA GEMM, unsplit, with pointwise kernels between the products; samples go through
+ *                         in groups sized by the helper.  Sines and cosines: the hardware instructions after a fract.
+ * No floating-point atomics on either route: two identical calls return bitwise identical results.  DSVGP_EINVAL for M, d, F, n or
+ * B < 1, a null required pointer, a misaligned `weights` (dsvgp_paths_eval) or an intermediate that would pass 2^31 entries (split the
+ * batch).  The two size helpers are pure host functions (0 for arguments the entries refuse).                                        */
+size_t dsvgp_paths_weights_bytes(int M, int d, int F, int n);
+size_t dsvgp_paths_workspace_bytes(int M, int d, int F, int n, int B, int want_grad);
+int dsvgp_paths_prepare(dsvgp_ctx* ctx, const double* nu, const double* w, const double* omega, const double* phase, const float* Z,
+                        const float* V, int M, int d, int p, int F, int n, const float* hyp, const float* constant, const float* center,
+                        float* weights);
+int dsvgp_paths_eval(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, const float* x, int B, float* values,
+                     float* grads, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
