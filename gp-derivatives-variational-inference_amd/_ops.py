@@ -1032,6 +1032,34 @@ def paths_eval(ctx, weights, M, d, F, n, x, values=None, grads=None, workspace=N
     return values
 
 
+def paths_hvp_workspace_bytes(M, d, F, n, B):
+    return int(lib.dsvgp_paths_hvp_workspace_bytes(int(M), int(d), int(F), int(n), int(B)))
+
+
+def paths_hvp(ctx, weights, M, d, F, n, x, v, hv=None, workspace=None):
+    """hv [n, B, d] = grad^2 f_s(x_b) v_b: the Hessian-vector products of n posterior paths at x [B, d] with one vector per point
+    v [B, d], shared by the samples and used as given (dsvgp_paths_hvp).  ``workspace``: uint8 tensor of
+    dsvgp_paths_hvp_workspace_bytes(M, d, F, n, B) bytes (None when that is 0)."""
+    _req(x, f32, "x", 2)
+    _req(v, f32, "v", 2)
+    _req(weights, f32, "weights", 1)
+    B = x.shape[0]
+    if x.shape[1] != d or not x.is_contiguous():
+        raise ValueError("x must be a contiguous [B, %d] tensor, got %s" % (d, tuple(x.shape)))
+    if v.shape != (B, d) or not v.is_contiguous():
+        raise ValueError("v must be a contiguous [B, d] = [%d, %d] tensor, got %s" % (B, d, tuple(v.shape)))
+    if hv is None:
+        hv = torch.empty(n, B, d, dtype=f32, device=x.device)
+    if not hv.is_cuda or hv.dtype != f32 or hv.shape != (n, B, d) or not hv.is_contiguous():
+        raise ValueError("hv must be a contiguous float32 [%d, %d, %d] tensor on the GPU" % (n, B, d))
+    need = paths_hvp_workspace_bytes(M, d, F, n, B)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        raise ValueError("paths_hvp workspace too small: %d bytes needed" % need)
+    check(lib.dsvgp_paths_hvp(ctx.h, _ptr(weights), M, d, F, n, _ptr(x), _ptr(v), B, _ptr(hv), _ptr(workspace if need else None)),
+          "dsvgp_paths_hvp")
+    return hv
+
+
 def likelihood_terms(ctx, mu, var, y, p, hyp, mll_type, global_rows, mu_bar, var_bar, varn, scalars):
     check(lib.dsvgp_likelihood_terms(ctx.h, _ptr(mu), _ptr(var), _ptr(_req(y, f32, "y", 1)), mu.shape[0], p, _ptr(hyp),
                                      int(mll_type), float(global_rows), _ptr(mu_bar), _ptr(var_bar), _ptr(varn),

@@ -54,11 +54,16 @@ class MeanPredictor:
     Holds its own buffers (the weights and, for d > 32, the [B, 2M] workspace): the engine's evaluation cache and training
     workspaces are not used after construction.  Valid for the parameter values it was built from."""
 
-    def __init__(self, device, weights, M, d, values_only=False):
+    def __init__(self, device, weights, M, d, values_only=False, hvp_source=None):
         self.device = torch.device(device)
         self.weights, self.M, self.d = weights, int(M), int(d)
         self.values_only = bool(values_only)        # engine.data_outputs == "values": derivative-free data, value rows only
         self._ws = None
+        # second order (``hvp`` / ``hessian``): the mean is the path with nu = alpha, one feature and a zero prior weight.
+        # ``hvp_source`` = (alpha fp64 [M(p+1)], Z, V or None, p, hyp, constant, center): what dsvgp_paths_prepare needs; its
+        # one-sample weights are packed on the first ``hvp`` call
+        self._hvp_source = hvp_source
+        self._hvp_paths = None
 
     def _workspace(self, B, pd):
         need = _ops.mean_workspace_bytes(self.M, self.d, B, pd)
@@ -100,6 +105,29 @@ class MeanPredictor:
         """(mu_f [B], grad mu_f [B, d]); the gradient carries no constant"""
         return self._run(x, None, 0, True)
 
+    def _paths(self):
+        if self._hvp_paths is None:
+            if self._hvp_source is None:
+                raise ValueError("this MeanPredictor was built without the inducing set (hvp_source): use ElboEngine.mean_predictor")
+            alpha, Z, V, p, hyp, constant, center = self._hvp_source
+            ctx = _ops.Context.get(self.device)
+            zero = lambda *shape: torch.zeros(*shape, dtype=f64, device=self.device)
+            weights = _ops.paths_prepare(ctx, alpha.reshape(1, -1).contiguous(), zero(1, 1), zero(1, self.d), zero(1), Z, V, p, hyp,
+                                         constant, center)
+            self._hvp_paths = SamplePaths(self.device, weights, self.M, self.d, 1, 1, constant.detach().reshape(()).to(f32).clone())
+        return self._hvp_paths
+
+    @torch.no_grad()
+    def hvp(self, x, v):
+        """grad^2 mu_f(x_b) v_b [B, d] for one vector per point v [B, d] (used as given): ``SamplePaths.hvp`` on the path with
+        nu = alpha and no prior draw (dsvgp_paths_hvp)"""
+        return self._paths().hvp(x, v)[0]
+
+    @torch.no_grad()
+    def hessian(self, x):
+        """grad^2 mu_f(x) [B, d, d], symmetrised, from d ``hvp`` calls with the unit vectors"""
+        return self._paths().hessians(x)[0]
+
 
 class SamplePaths:
     """n draws of the posterior FUNCTION of a frozen model (``ElboEngine.sample_paths``; csrc/paths.hip): each can be evaluated, with
@@ -116,10 +144,9 @@ class SamplePaths:
         self.workspace_budget = int(workspace_budget)
         self._ws = None
 
-    def _rows(self, B, want_grad):
-        """rows per call of the C entry: all of them when the workspace fits the budget (d <= 32: it is empty), else the largest
-        block that does (sample groups are cut inside the entry)"""
-        need = lambda r: _ops.paths_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, r, want_grad)
+    def _fit_rows(self, B, need):
+        """rows per call of a C entry whose workspace on r rows is ``need(r)`` bytes: all of them when that fits the budget (d <= 32:
+        it is empty), else the largest block that does (sample groups are cut inside the entry)"""
         if self.d <= 32 or 0 < need(B) <= self.workspace_budget:
             return B
         lo, hi = 1, B                               # need(r) grows with r; 0 = refused (an intermediate past 2^31 entries)
@@ -131,14 +158,19 @@ class SamplePaths:
                 hi = mid - 1
         return lo
 
-    def _workspace(self, rows, want_grad):
-        need = _ops.paths_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, rows, want_grad)
+    def _buffer(self, need):
         if need == 0:
             return None
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _rows(self, B, want_grad):
+        return self._fit_rows(B, lambda r: _ops.paths_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, r, want_grad))
+
+    def _workspace(self, rows, want_grad):
+        return self._buffer(_ops.paths_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, rows, want_grad))
 
     def _run(self, x, want_grad):
         if x.dim() == 1:
@@ -175,6 +207,62 @@ class SamplePaths:
     def values_and_gradients(self, x):
         """(f_s(x) [n, B], grad f_s(x) [n, B, d]); the gradient carries no constant"""
         return self._run(x, True)
+
+    def _hvp_rows(self, B):
+        return self._fit_rows(B, lambda r: _ops.paths_hvp_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, r))
+
+    def _hvp_workspace(self, rows):
+        return self._buffer(_ops.paths_hvp_workspace_bytes(self.M, self.d, self.num_features, self.num_samples, rows))
+
+    @torch.no_grad()
+    def hvp(self, x, v):
+        """grad^2 f_s(x_b) v_b [n, B, d]: the Hessian-vector products of every path at x [B, d] with one vector per point v [B, d],
+        shared by the samples and used as given, not normalised (dsvgp_paths_hvp: 4 d FMAs per (point, inducing point, sample) where
+        the gradient takes 3 d; nothing of size d x d).  d <= 32: the result of (sample, point) does not depend on the batch."""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        if not x.is_cuda or not v.is_cuda:
+            raise _lib.DsvgpError("x and v must live on the GPU: the DSVGP hot path has no CPU fallback")
+        if tuple(v.shape) != (x.shape[0], self.d) or x.shape[1] != self.d:
+            raise ValueError("v must be [B, d] = [%d, %d] next to x [B, d], got v %s and x %s"
+                             % (x.shape[0], self.d, tuple(v.shape), tuple(x.shape)))
+        ctx = _ops.Context.get(self.device)
+        x, v = x.contiguous(), v.to(f32).contiguous()
+        B, n, d = x.shape[0], self.num_samples, self.d
+        hv = torch.empty(n, B, d, dtype=f32, device=self.device)
+        if B == 0:
+            return hv
+        rows = self._hvp_rows(B)
+        if rows >= B:
+            _ops.paths_hvp(ctx, self.weights, self.M, d, self.num_features, n, x, v, hv, self._hvp_workspace(B))
+            return hv
+        for r0 in range(0, B, rows):                # row blocks: the entry writes [n, rows, d] contiguous
+            r1 = min(B, r0 + rows)
+            h = torch.empty(n, r1 - r0, d, dtype=f32, device=self.device)
+            _ops.paths_hvp(ctx, self.weights, self.M, d, self.num_features, n, x[r0:r1], v[r0:r1], h, self._hvp_workspace(r1 - r0))
+            hv[:, r0:r1] = h
+        return hv
+
+    @torch.no_grad()
+    def hessians(self, x):
+        """grad^2 f_s(x) [n, B, d, d] from d ``hvp`` calls with the unit vectors, returned as (H + H^T) / 2 (exactly symmetric).
+        For small d: the result is n B d^2 floats and has to fit ``workspace_budget``."""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        if not x.is_cuda:
+            raise _lib.DsvgpError("x must live on the GPU: the DSVGP hot path has no CPU fallback")
+        B, n, d = x.shape[0], self.num_samples, self.d
+        size = 4 * n * B * d * d
+        if size > self.workspace_budget:
+            raise ValueError("hessians: n B d^2 = %d x %d x %d^2 floats (%d bytes) exceed the workspace budget of %d bytes; "
+                             "use hvp, or fewer points per call" % (n, B, d, size, self.workspace_budget))
+        H = torch.empty(n, B, d, d, dtype=f32, device=self.device)
+        e = torch.zeros(B, d, dtype=f32, device=self.device)
+        for k in range(d):
+            e.zero_()
+            e[:, k] = 1.0
+            H[:, :, :, k] = self.hvp(x, e)          # column k = H e_k
+        return 0.5 * (H + H.transpose(2, 3))
 
     @torch.no_grad()
     def __call__(self, x, derivative_directions=None):
@@ -767,7 +855,11 @@ class ElboEngine:
         weights = _ops.mean_prepare(ctx, alpha.reshape(Mp), params["inducing_points"].contiguous(),
                                     params["inducing_directions"].contiguous() if p > 0 else None, p, hyp,
                                     params["constant"], self.center)
-        return MeanPredictor(self.device, weights, M, d, values_only=self.data_outputs == "values")
+        # (copies: the predictor stays valid for THESE parameter values after the engine or an optimiser moves on; M' d floats)
+        keep = lambda t: t.detach().clone().contiguous()
+        source = (alpha.reshape(Mp), keep(params["inducing_points"]), keep(params["inducing_directions"]) if p > 0 else None, p,
+                  keep(hyp), keep(params["constant"]), keep(self.center))
+        return MeanPredictor(self.device, weights, M, d, values_only=self.data_outputs == "values", hvp_source=source)
 
     @torch.no_grad()
     def sample_paths(self, params, num_samples, num_features=2048, generator=None, base_samples=None):

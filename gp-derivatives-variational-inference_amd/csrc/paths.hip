@@ -400,6 +400,265 @@ int unsplit_gemm(dsvgp_ctx* ctx, int flags, int M, int N, int K, const float* A,
     return launch_gemm(ctx->stream, 0, g);
 }
 
+// ---- Hessian-vector products: hv[s][b][:] = grad^2 f_s(x_b) v_b ---------------------------------------------------------------------
+//     grad^2 f_s(x) v = (s / ell^2) [ sum_i ((k_i beta_is (r_i.v) + k_i (G'_is.v)) r_i + k_i (r_i.v) G'_is)
+//                                     + sum_j wq_js (-4 pi^2 cos_j)(Om_j.v) Om_j - (sum_i k_i beta_is) v ]
+// (the gradient's terms differentiated once more: d r / d x~ = -I, grad k = k r, grad beta = G').  r_i.v and Om_j.v do not depend on the
+// sample.  Fused route (d <= 32): the structure of paths_fused_kernel<D> with v[D] next to x~[D] and r[D] in the lane's registers and
+// NS = paths_hvp_ns(D) samples per group; no sine.  The order of every sum is fixed by M, F and d.
+constexpr float PP_M4PI2 = -39.4784176043574344753f;     // -4 pi^2
+
+template <int D>
+__global__ __launch_bounds__(PP_NW * 64) void paths_hvp_fused_kernel(const float* __restrict__ w, PathsWeights L, int M, int d, int F, int n,
+                                                                     const float* __restrict__ x, const float* __restrict__ vin, int64_t B,
+                                                                     float* __restrict__ hv) {
+    constexpr int NS = paths_hvp_ns(D);
+    constexpr PathsLds LD = paths_hvp_lds(D);
+    constexpr int NT = PP_NW * 64;
+    __shared__ __align__(16) float lds[LD.floats];
+    const int tid = threadIdx.x, lane = tid & 63, slice = tid >> 6;
+    const int64_t b0 = (int64_t)blockIdx.x * PP_TP;
+    const int64_t b = b0 + lane;
+    const int s0 = blockIdx.y * NS;
+    const float ell = w[0];
+    float xt[D], r[D], v[D], acc[NS][D], sig[NS];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const bool in = k < d && b < B;
+        xt[k] = in ? (x[b * d + k] - w[L.o_center + k]) / ell : 0.f;
+        v[k] = in ? vin[b * d + k] : 0.f;
+    }
+#pragma unroll
+    for (int g = 0; g < NS; ++g) {
+        sig[g] = 0.f;
+#pragma unroll
+        for (int k = 0; k < D; ++k) acc[g][k] = 0.f;
+    }
+    // ---- update term: the inducing points in chunks of PP_CH ----
+    for (int c0 = 0; c0 < M; c0 += PP_CH) {
+        const int nc = M - c0 < PP_CH ? M - c0 : PP_CH;
+        __syncthreads();                                  // the previous chunk has been consumed
+        const float4* srcZ = reinterpret_cast<const float4*>(w + L.o_z + (size_t)c0 * D);
+        for (int t = tid; t < nc * (D / 4); t += NT) reinterpret_cast<float4*>(lds + LD.o_z)[t] = srcZ[t];
+#pragma unroll
+        for (int g = 0; g < NS; ++g) {
+            const bool live = s0 + g < n;                 // (samples past n: zeros in, nothing out)
+            const int sg = live ? s0 + g : 0;
+            const float4* srcG = reinterpret_cast<const float4*>(w + L.o_g + ((size_t)sg * M + c0) * D);
+            float4* dstG = reinterpret_cast<float4*>(lds + LD.o_g + g * PP_CH * D);
+            for (int t = tid; t < nc * (D / 4); t += NT) {
+                float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (live) q = srcG[t];
+                dstG[t] = q;
+            }
+            if (tid < nc) lds[LD.o_a + g * PP_CH + tid] = live ? w[L.o_a + (size_t)sg * L.Mr + c0 + tid] : 0.f;
+        }
+        __syncthreads();
+        for (int i = slice; i < nc; i += PP_NW) {         // every LDS read below is one address per wave (broadcast)
+            const float* z = lds + LD.o_z + i * D;
+            float r2 = 0.f, rv = 0.f;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                r[k] = z[k] - xt[k];
+                r2 = __builtin_fmaf(r[k], r[k], r2);
+                rv = __builtin_fmaf(r[k], v[k], rv);
+            }
+            const float kk = __expf(-0.5f * r2);
+            const float krv = kk * rv;
+#pragma unroll
+            for (int g = 0; g < NS; ++g) {
+                const float* gp = lds + LD.o_g + (g * PP_CH + i) * D;
+                float rg = 0.f, gv = 0.f;
+#pragma unroll
+                for (int k = 0; k < D; ++k) {
+                    rg = __builtin_fmaf(r[k], gp[k], rg);
+                    gv = __builtin_fmaf(v[k], gp[k], gv);
+                }
+                const float P = kk * (lds[LD.o_a + g * PP_CH + i] - rg);      // k_i beta_is
+                sig[g] += P;
+                const float c1 = __builtin_fmaf(P, rv, kk * gv);
+#pragma unroll
+                for (int k = 0; k < D; ++k) acc[g][k] = __builtin_fmaf(c1, r[k], __builtin_fmaf(krv, gp[k], acc[g][k]));
+            }
+        }
+    }
+    // ---- prior term: the features in chunks of PP_CH ----
+    for (int j0 = 0; j0 < F; j0 += PP_CH) {
+        const int nf = F - j0 < PP_CH ? F - j0 : PP_CH;
+        __syncthreads();
+        const float4* srcO = reinterpret_cast<const float4*>(w + L.o_om + (size_t)j0 * D);
+        for (int t = tid; t < nf * (D / 4); t += NT) reinterpret_cast<float4*>(lds + LD.o_om)[t] = srcO[t];
+        if (tid < nf) lds[LD.o_ph + tid] = w[L.o_ph + j0 + tid];
+#pragma unroll
+        for (int g = 0; g < NS; ++g) {
+            const bool live = s0 + g < n;
+            const int sg = live ? s0 + g : 0;
+            if (tid < nf) lds[LD.o_w + g * PP_CH + tid] = live ? w[L.o_wq + (size_t)sg * L.Fr + j0 + tid] : 0.f;
+        }
+        __syncthreads();
+        for (int j = slice; j < nf; j += PP_NW) {
+            const float* om = lds + LD.o_om + j * D;
+            float th = lds[LD.o_ph + j], ov = 0.f;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                th = __builtin_fmaf(om[k], xt[k], th);
+                ov = __builtin_fmaf(om[k], v[k], ov);
+            }
+            th = __builtin_amdgcn_fractf(th);
+            const float tc = (PP_M4PI2 * __builtin_amdgcn_cosf(th)) * ov;
+#pragma unroll
+            for (int g = 0; g < NS; ++g) {
+                const float t = lds[LD.o_w + g * PP_CH + j] * tc;
+#pragma unroll
+                for (int k = 0; k < D; ++k) acc[g][k] = __builtin_fmaf(t, om[k], acc[g][k]);
+            }
+        }
+    }
+    // ---- the waves' partial sums, added in the fixed order 0 + 1 + .. + 7 ----
+    float* red = lds + LD.o_red;
+    for (int s = 1; s < PP_NW; ++s) {
+        __syncthreads();
+        if (slice == s) {
+#pragma unroll
+            for (int g = 0; g < NS; ++g) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) red[(g * PP_TP + lane) * (D + 1) + k] = acc[g][k];
+                red[(g * PP_TP + lane) * (D + 1) + D] = sig[g];
+            }
+        }
+        __syncthreads();
+        if (slice == 0) {
+#pragma unroll
+            for (int g = 0; g < NS; ++g) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) acc[g][k] += red[(g * PP_TP + lane) * (D + 1) + k];
+                sig[g] += red[(g * PP_TP + lane) * (D + 1) + D];
+            }
+        }
+    }
+    __syncthreads();
+    const float s_ell2 = w[4] * w[3];                    // s / ell^2
+    if (slice == 0) {
+#pragma unroll
+        for (int g = 0; g < NS; ++g) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) red[(g * PP_TP + lane) * (D + 1) + k] = s_ell2 * (acc[g][k] - sig[g] * v[k]);
+        }
+    }
+    __syncthreads();
+    const int npts = (int)(B - b0 < PP_TP ? B - b0 : PP_TP);
+    for (int g = 0; g < NS; ++g) {
+        if (s0 + g >= n) break;
+        const size_t so = (size_t)(s0 + g) * (size_t)B + (size_t)b0;
+        for (int t = tid; t < npts * d; t += NT) {
+            const int pt = t / d, k = t - pt * d;
+            hv[so * d + t] = red[(g * PP_TP + pt) * (D + 1) + k];
+        }
+    }
+}
+
+// composed route: V zero padded to ldw and xv = x~ . v: one wave per test point
+__global__ __launch_bounds__(256) void paths_hvp_pack_v_kernel(const float* __restrict__ v, int B, int d, int ldw, const float* __restrict__ Xt,
+                                                              float* __restrict__ Vp, float* __restrict__ xv) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= B) return;
+    float acc = 0.f;
+    for (int k = lane; k < ldw; k += 64) {
+        const float q = k < d ? v[(size_t)row * d + k] : 0.f;
+        Vp[(size_t)row * ldw + k] = q;
+        acc = __builtin_fmaf(q, Xt[(size_t)row * ldw + k], acc);
+    }
+    acc = wave_sum(acc);
+    if (lane == 0) xv[row] = acc;
+}
+
+// V Z~^T -> RV = r . v in place, C2 = k o RV; zero from M up to ldM
+__global__ __launch_bounds__(256) void paths_hvp_rv_kernel(int M, int B, const float* __restrict__ K, float* __restrict__ RV,
+                                                          float* __restrict__ C2, int ldM, const float* __restrict__ xv) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)B * ldM) return;
+    const int b = (int)(t / ldM), i = (int)(t - (int64_t)b * ldM);
+    float rv = 0.f;
+    if (i < M) rv = RV[t] - xv[b];
+    RV[t] = rv;
+    C2[t] = K[t] * rv;
+}
+
+// T = -4 pi^2 cos o OV in place of the cosines; zero from F up to ldF
+__global__ __launch_bounds__(256) void paths_hvp_t_kernel(int F, int B, float* __restrict__ T, const float* __restrict__ OV, int ldF) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (int64_t)B * ldF) return;
+    const int j = (int)(t % ldF);
+    T[t] = j < F ? (PP_M4PI2 * T[t]) * OV[t] : 0.f;
+}
+
+// P = k (a'_s + S2), C1[g][b][i] = P RV + k GV, sigma[g][b] = sum_i P, sigma1[g][b] = sum_i C1: one workgroup per (test point,
+// sample), fixed-order sums
+__global__ __launch_bounds__(256) void paths_hvp_pointwise_kernel(const float* __restrict__ w, PathsWeights L, int M, int B, int s0,
+                                                                 const float* __restrict__ K, const float* __restrict__ RV, int ldM,
+                                                                 const float* __restrict__ S2, const float* __restrict__ GV, int ld2,
+                                                                 float* __restrict__ C1, float* __restrict__ sigma,
+                                                                 float* __restrict__ sigma1, size_t Br) {
+    __shared__ float part[8];
+    const int b = blockIdx.x, g = blockIdx.y, tid = threadIdx.x;
+    const float* ap = w + L.o_ap + (size_t)(s0 + g) * L.Mr;
+    const float* Kr = K + (size_t)b * ldM;
+    const float* Rr = RV + (size_t)b * ldM;
+    const float* Sr = S2 + (size_t)b * ld2 + (size_t)g * M;
+    const float* Gr = GV + (size_t)b * ld2 + (size_t)g * M;
+    float* Cr = C1 + ((size_t)g * B + b) * ldM;
+    float acc = 0.f, acc1 = 0.f;
+    for (int i = tid; i < ldM; i += 256) {
+        float P = 0.f, c1 = 0.f;
+        if (i < M) {
+            P = Kr[i] * (ap[i] + Sr[i]);
+            c1 = __builtin_fmaf(P, Rr[i], Kr[i] * Gr[i]);
+        }
+        Cr[i] = c1;
+        acc += P;
+        acc1 += c1;
+    }
+    acc = wave_sum(acc);
+    acc1 = wave_sum(acc1);
+    if ((tid & 63) == 0) {
+        part[tid >> 6] = acc;
+        part[4 + (tid >> 6)] = acc1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        sigma[(size_t)g * Br + b] = ((part[0] + part[1]) + part[2]) + part[3];
+        sigma1[(size_t)g * Br + b] = ((part[4] + part[5]) + part[6]) + part[7];
+    }
+}
+
+// hv[s][b][:] = (s / ell^2)(O1 + O2 - sigma1 x~ + GP - sigma v): one wave per (test point, sample)
+__global__ __launch_bounds__(256) void paths_hvp_epilogue_kernel(const float* __restrict__ w, PathsWeights L, int B, int d, int s0, int ng,
+                                                                const float* __restrict__ Xt, const float* __restrict__ Vp,
+                                                                const float* __restrict__ sigma, const float* __restrict__ sigma1,
+                                                                size_t Br, const float* __restrict__ O1, const float* __restrict__ O2,
+                                                                const float* __restrict__ GP, float* __restrict__ hv) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, g = blockIdx.y;
+    if (row >= B) return;
+    const float s_ell2 = w[4] * w[3];
+    const float sg = sigma[(size_t)g * Br + row], sg1 = sigma1[(size_t)g * Br + row];
+    const size_t so = (size_t)(s0 + g) * (size_t)B + (size_t)row;
+    const float* o1 = O1 + ((size_t)g * B + row) * L.ldw;
+    const float* o2 = O2 + ((size_t)g * B + row) * L.ldw;
+    const float* gp = GP + (size_t)row * ((size_t)ng * L.ldw) + (size_t)g * L.ldw;
+    const float* xr = Xt + (size_t)row * L.ldw;
+    const float* vr = Vp + (size_t)row * L.ldw;
+    for (int k = lane; k < d; k += 64) hv[so * d + k] = s_ell2 * ((((o1[k] + o2[k]) - sg1 * xr[k]) + gp[k]) - sg * vr[k]);
+}
+
+template <int D>
+int launch_hvp_fused(hipStream_t st, const float* w, const PathsWeights& L, int M, int d, int F, int n, const float* x, const float* v, int B,
+                     float* hv) {
+    hipLaunchKernelGGL((paths_hvp_fused_kernel<D>), dim3(cdiv(B, PP_TP), cdiv(n, paths_hvp_ns(D))), dim3(PP_NW * 64), 0, st, w, L, M, d, F,
+                       n, x, v, (int64_t)B, hv);
+    DSVGP_LAUNCH_CHECK();
+    return 0;
+}
+
 bool paths_shape_ok(int M, int d, int F, int n) {
     return M >= 1 && d >= 1 && F >= 1 && n >= 1 && (long long)n * M * paths_pad4(d) <= PP_IDX_MAX * 4 &&
            (long long)F * paths_pad4(d) <= PP_IDX_MAX && (long long)n * paths_pad4(F) <= PP_IDX_MAX;
@@ -497,6 +756,86 @@ extern "C" int dsvgp_paths_eval(dsvgp_ctx* ctx, const float* weights, int M, int
         }
         hipLaunchKernelGGL(paths_epilogue_kernel, dim3(cdiv(B, 4), ng), dim3(256), 0, st, weights, L, B, d, s0, ng, Xt, sig, S.Br, VP,
                            S.ldn, O1, O2, GP, values, grads);
+        DSVGP_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" size_t dsvgp_paths_hvp_workspace_bytes(int M, int d, int F, int n, int B) {
+    if (!paths_shape_ok(M, d, F, n) || B < 1) return 0;
+    if (d <= PP_FUSED_MAX_D) return 0;                    // the fused kernel keeps everything in registers and LDS
+    PathsHvpWork S;
+    if (paths_hvp_work(M, d, F, n, B, S)) return 0;
+    return S.total * sizeof(float);
+}
+
+extern "C" int dsvgp_paths_hvp(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, const float* x, const float* v, int B,
+                               float* hv, void* workspace) {
+    if (!ctx || !weights || !x || !v || !hv || !paths_shape_ok(M, d, F, n) || B < 1) return DSVGP_EINVAL;
+    if ((int64_t)B * d > PP_IDX_MAX) return DSVGP_EINVAL;
+    if ((uintptr_t)weights % 16) return DSVGP_EINVAL;
+    const PathsWeights L = paths_weights(M, d, F, n);
+    hipStream_t st = ctx->stream;
+    if (d <= PP_FUSED_MAX_D) {
+        if (cdiv(n, paths_hvp_ns(L.ldw)) > 65535) return DSVGP_EINVAL;
+        switch (L.ldw) {
+            case 4: return launch_hvp_fused<4>(st, weights, L, M, d, F, n, x, v, B, hv);
+            case 8: return launch_hvp_fused<8>(st, weights, L, M, d, F, n, x, v, B, hv);
+            case 12: return launch_hvp_fused<12>(st, weights, L, M, d, F, n, x, v, B, hv);
+            case 16: return launch_hvp_fused<16>(st, weights, L, M, d, F, n, x, v, B, hv);
+            case 20: return launch_hvp_fused<20>(st, weights, L, M, d, F, n, x, v, B, hv);
+            case 24: return launch_hvp_fused<24>(st, weights, L, M, d, F, n, x, v, B, hv);
+            case 28: return launch_hvp_fused<28>(st, weights, L, M, d, F, n, x, v, B, hv);
+            default: return launch_hvp_fused<32>(st, weights, L, M, d, F, n, x, v, B, hv);
+        }
+    }
+    if (!workspace || (uintptr_t)workspace % 16) return DSVGP_EINVAL;
+    PathsHvpWork S;
+    if (paths_hvp_work(M, d, F, n, B, S)) return DSVGP_EINVAL;                       // (an intermediate past 2^31 entries: split the batch)
+    float* ws = (float*)workspace;
+    float *Xt = ws + S.o_x, *Vp = ws + S.o_v, *xn = ws + S.o_xn, *xv = ws + S.o_xv, *K = ws + S.o_k, *RV = ws + S.o_rv, *C2 = ws + S.o_c2;
+    float *T = ws + S.o_t, *OV = ws + S.o_ov, *S2 = ws + S.o_s2, *GV = ws + S.o_gv, *C1 = ws + S.o_c1, *sig = ws + S.o_sig;
+    float *sig1 = ws + S.o_sig1, *O1 = ws + S.o_o1, *O2 = ws + S.o_o2, *WO = ws + S.o_wo, *GP = ws + S.o_gp;
+    const float *Zt = weights + L.o_z, *Om = weights + L.o_om, *G = weights + L.o_g;
+    const int KP = DSVGP_GEMM_TRANS_B | DSVGP_GEMM_K_PADDED;
+    hipLaunchKernelGGL(paths_pack_x_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, weights, L, x, B, d, Xt, xn);
+    DSVGP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(paths_hvp_pack_v_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, v, B, d, S.ldw, Xt, Vp, xv);
+    DSVGP_LAUNCH_CHECK();
+    // S1 = X~ Z~^T -> k;  V Z~^T -> RV = r . v, C2 = k o RV (once for all samples)
+    if (int rc = unsplit_gemm(ctx, KP, B, M, d, Xt, S.ldw, Zt, L.ldw, K, S.ldM)) return rc;
+    hipLaunchKernelGGL(paths_k_kernel, dim3(cdiv((int64_t)B * S.ldM, 256)), dim3(256), 0, st, weights, L, M, B, K, S.ldM, xn);
+    DSVGP_LAUNCH_CHECK();
+    if (int rc = unsplit_gemm(ctx, KP, B, M, d, Vp, S.ldw, Zt, L.ldw, RV, S.ldM)) return rc;
+    hipLaunchKernelGGL(paths_hvp_rv_kernel, dim3(cdiv((int64_t)B * S.ldM, 256)), dim3(256), 0, st, M, B, K, RV, C2, S.ldM, xv);
+    DSVGP_LAUNCH_CHECK();
+    // Theta = X~ Om^T -> cos;  OV = V Om^T;  T = -4 pi^2 cos o OV (once for all samples)
+    if (int rc = unsplit_gemm(ctx, KP, B, F, d, Xt, S.ldw, Om, L.ldw, T, S.ldF)) return rc;
+    hipLaunchKernelGGL(paths_feature_kernel, dim3(cdiv((int64_t)B * S.ldF, 256)), dim3(256), 0, st, weights, L, F, B, T, (float*)nullptr,
+                       S.ldF);
+    DSVGP_LAUNCH_CHECK();
+    if (int rc = unsplit_gemm(ctx, KP, B, F, d, Vp, S.ldw, Om, L.ldw, OV, S.ldF)) return rc;
+    hipLaunchKernelGGL(paths_hvp_t_kernel, dim3(cdiv((int64_t)B * S.ldF, 256)), dim3(256), 0, st, F, B, T, OV, S.ldF);
+    DSVGP_LAUNCH_CHECK();
+    for (int s0 = 0; s0 < n; s0 += S.ng) {
+        const int ng = n - s0 < S.ng ? n - s0 : S.ng;
+        const float* Gg = G + (size_t)s0 * M * L.ldw;
+        // S2 = X~ G'_group^T, GV = V G'_group^T
+        if (int rc = unsplit_gemm(ctx, KP, B, ng * M, d, Xt, S.ldw, Gg, L.ldw, S2, S.ld2)) return rc;
+        if (int rc = unsplit_gemm(ctx, KP, B, ng * M, d, Vp, S.ldw, Gg, L.ldw, GV, S.ld2)) return rc;
+        hipLaunchKernelGGL(paths_hvp_pointwise_kernel, dim3(B, ng), dim3(256), 0, st, weights, L, M, B, s0, K, RV, S.ldM, S2, GV, S.ld2, C1,
+                           sig, sig1, S.Br);
+        DSVGP_LAUNCH_CHECK();
+        // O1 = C1 Z~ for the whole group, O2_s = C2 G'_s per sample, GP = T WO with WO = wq_s o Om
+        if (int rc = unsplit_gemm(ctx, 0, ng * B, d, M, C1, S.ldM, Zt, L.ldw, O1, S.ldw)) return rc;
+        for (int g = 0; g < ng; ++g)
+            if (int rc = unsplit_gemm(ctx, 0, B, d, M, C2, S.ldM, G + (size_t)(s0 + g) * M * L.ldw, L.ldw, O2 + (size_t)g * B * S.ldw, S.ldw))
+                return rc;
+        hipLaunchKernelGGL(paths_wo_kernel, dim3(cdiv((int64_t)F * ng * L.ldw, 256)), dim3(256), 0, st, weights, L, F, s0, ng, WO);
+        DSVGP_LAUNCH_CHECK();
+        if (int rc = unsplit_gemm(ctx, 0, B, ng * L.ldw, F, T, S.ldF, WO, (int64_t)ng * L.ldw, GP, (int64_t)ng * L.ldw)) return rc;
+        hipLaunchKernelGGL(paths_hvp_epilogue_kernel, dim3(cdiv(B, 4), ng), dim3(256), 0, st, weights, L, B, d, s0, ng, Xt, Vp, sig, sig1,
+                           S.Br, O1, O2, GP, hv);
         DSVGP_LAUNCH_CHECK();
     }
     return 0;

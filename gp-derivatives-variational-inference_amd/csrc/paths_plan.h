@@ -35,8 +35,7 @@ constexpr int paths_ns(int D) {
 
 // LDS float offsets of the three images (template parameter D)
 struct PathsLds { int o_z, o_g, o_a, o_om, o_ph, o_w, o_red, floats; };
-constexpr PathsLds paths_lds(int D) {
-    const int NS = paths_ns(D);
+constexpr PathsLds paths_lds_ns(int D, int NS) {
     PathsLds l{};
     l.o_z = 0; l.o_g = PP_CH * D; l.o_a = l.o_g + NS * PP_CH * D;
     l.o_om = 0; l.o_ph = PP_CH * D; l.o_w = l.o_ph + PP_CH;
@@ -44,6 +43,19 @@ constexpr PathsLds paths_lds(int D) {
     l.floats = l.o_a + NS * PP_CH;                        // >= PP_CH (D + 1 + NS) and >= NS PP_TP (D + 1)
     return l;
 }
+constexpr PathsLds paths_lds(int D) { return paths_lds_ns(D, paths_ns(D)); }
+
+// Hessian-vector products (paths_hvp_fused_kernel<D>): the lane also holds v[D], so the group is narrower at the large D.  The rule
+// is the one above with 3 D registers of x~, r, v; where the compiler's own temporaries (a row of G' or Om held across the inner
+// loops) still pushed an instance past 256 registers the width is one less: the table is the widest at which no instance spills.
+// The three LDS images are those above at this NS.
+constexpr int paths_hvp_ns(int D) {
+    int ns = (176 - 3 * D) / (D + 1);
+    if (D == 24 || D == 32) ns -= 1;
+    ns = ns < PP_NS_MAX ? ns : PP_NS_MAX;
+    return ns > 1 ? ns : 1;
+}
+constexpr PathsLds paths_hvp_lds(int D) { return paths_lds_ns(D, paths_hvp_ns(D)); }
 
 // packed weights (floats): hdr[8] = {ell, s, c, 1/ell, s/ell, 0, 0, 0} | center[ldw] | nz[Mr] = |z~|^2 | Z~[M][ldw] |
 // Om[F][ldw] = omega / 2 pi | phase[Fr] (revolutions, in [0, 1]) | a[n][Mr] | a'[n][Mr] = a - z~.G' | wq[n][Fr] = sqrt(2 / (s F)) w |
@@ -107,6 +119,55 @@ inline int paths_work(int M, int d, int F, int n, int B, int want_grad, PathsWor
     s.o_o2 = o;  o += want_grad ? (size_t)s.ng * B * s.ldw : 0;
     s.o_wo = o;  o += want_grad ? (size_t)F * s.ng * s.ldw : 0;
     s.o_gp = o;  o += want_grad ? (size_t)B * s.ng * s.ldw : 0;
+    s.total = o;
+    return 0;
+}
+
+// composed route of the Hessian-vector product: workspace (floats) of one call on B rows; samples go through in groups of ng.
+//   shared   X~[B][ldw] | V[B][ldw] | xn[Br] | xv[Br] = x~.v | K[B][ldM] | RV[B][ldM] = V Z~^T - xv | C2[B][ldM] = k o RV |
+//            T[B][ldF] = -4 pi^2 cos o OV | OV[B][ldF] = V Om^T
+//   group    S2[B][ld2] | GV[B][ld2] (ld2 = pad4(ng M)) | C1[ng][B][ldM] | sigma[ng][Br] | sigma1[ng][Br] |
+//            O1[ng][B][ldw] | O2[ng][B][ldw] | WO[F][ng ldw] | GP[B][ng ldw]
+struct PathsHvpWork {
+    int ldw, ldM, ldF, ld2, ng;
+    size_t Br, o_x, o_v, o_xn, o_xv, o_k, o_rv, o_c2, o_t, o_ov, o_s2, o_gv, o_c1, o_sig, o_sig1, o_o1, o_o2, o_wo, o_gp, total;
+};
+
+// 0, or -1 for a shape the composed route refuses (an intermediate would pass 2^31 entries: split the batch)
+inline int paths_hvp_work(int M, int d, int F, int n, int B, PathsHvpWork& s) {
+    if (M < 1 || d < 1 || F < 1 || n < 1 || B < 1) return -1;
+    s = PathsHvpWork{};
+    s.ldw = paths_pad4(d); s.ldM = paths_pad4(M); s.ldF = paths_pad4(F);
+    s.Br = paths_pad4z((size_t)B);
+    const size_t per = (size_t)2 * B * M + (size_t)B * s.ldM + 2 * s.Br + (size_t)3 * B * s.ldw + (size_t)F * s.ldw;
+    size_t ng = PP_GROUP_FLOATS / per;
+    ng = ng < (size_t)n ? ng : (size_t)n;
+    ng = ng < 65535 ? ng : 65535;                         // (a grid dimension)
+    s.ng = ng > 1 ? (int)ng : 1;
+    s.ld2 = paths_pad4(s.ng * M);
+    const long long big[] = {(long long)B * s.ld2, (long long)s.ng * B * s.ldM, (long long)B * s.ldF, (long long)s.ng * B * s.ldw,
+                             (long long)F * s.ng * s.ldw, (long long)B * d};
+    for (long long v : big)
+        if (v > PP_IDX_MAX) return -1;
+    size_t o = 0;
+    s.o_x = o;    o += (size_t)B * s.ldw;
+    s.o_v = o;    o += (size_t)B * s.ldw;
+    s.o_xn = o;   o += s.Br;
+    s.o_xv = o;   o += s.Br;
+    s.o_k = o;    o += (size_t)B * s.ldM;
+    s.o_rv = o;   o += (size_t)B * s.ldM;
+    s.o_c2 = o;   o += (size_t)B * s.ldM;
+    s.o_t = o;    o += (size_t)B * s.ldF;
+    s.o_ov = o;   o += (size_t)B * s.ldF;
+    s.o_s2 = o;   o += (size_t)B * s.ld2;
+    s.o_gv = o;   o += (size_t)B * s.ld2;
+    s.o_c1 = o;   o += (size_t)s.ng * B * s.ldM;
+    s.o_sig = o;  o += (size_t)s.ng * s.Br;
+    s.o_sig1 = o; o += (size_t)s.ng * s.Br;
+    s.o_o1 = o;   o += (size_t)s.ng * B * s.ldw;
+    s.o_o2 = o;   o += (size_t)s.ng * B * s.ldw;
+    s.o_wo = o;   o += (size_t)F * s.ng * s.ldw;
+    s.o_gp = o;   o += (size_t)B * s.ng * s.ldw;
     s.total = o;
     return 0;
 }

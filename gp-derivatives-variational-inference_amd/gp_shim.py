@@ -435,6 +435,19 @@ class ApproximateGP(torch.nn.Module):
             x = x.unsqueeze(-1)
         return self._mean_predictor().value_and_gradient(x)[1]
 
+    def posterior_mean_hvp(self, x, v):
+        """Hessian of the predictive mean of f times one vector per point: grad^2 mu_f(x_b) v_b, x and v [B, d] -> [B, d]
+        (``MeanPredictor.hvp``; v is used as given)"""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        return self._mean_predictor().hvp(x, v)
+
+    def posterior_mean_hessian(self, x):
+        """Hessian of the predictive mean of f at x [B, d] -> [B, d, d], symmetric (``MeanPredictor.hessian``: d products)"""
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        return self._mean_predictor().hessian(x)
+
     def posterior_gradient(self, x, likelihood=None):
         """The distribution of (f(x), grad f(x)) at every point of x [B, d], whatever number of directions the model was trained
         with: a named tuple of value_mean [B], value_variance [B], gradient_mean [B, d], gradient_covariance [B, d, d] and

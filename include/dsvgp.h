@@ -774,6 +774,28 @@ int dsvgp_paths_prepare(dsvgp_ctx* ctx, const double* nu, const double* w, const
 int dsvgp_paths_eval(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, const float* x, int B, float* values,
                      float* grads, void* workspace);
 
+/* ---- Hessian-vector products of the paths (csrc/paths.hip): second-order information for a Newton or trust-region refinement of a
+ * candidate on its own sampled function, or the curvature of a fitted implicit surface.  With x~ = (x - center) / ell, r_i = z~_i - x~,
+ * k_i = exp(-|r_i|^2 / 2), G'_is = g_is / ell, beta_is = a_is - r_i . G'_is, theta_j = Om_j . x~ + ph_j (revolutions) and wq_js as above
+ *     grad^2 f_s(x) v = (s / ell^2) [ sum_i ((k_i beta_is (r_i.v) + k_i (G'_is.v)) r_i + k_i (r_i.v) G'_is)
+ *                                     + sum_j wq_js (-4 pi^2 cos 2 pi theta_j)(Om_j.v) Om_j - (sum_i k_i beta_is) v ]
+ * -- the terms the gradient already uses; r_i.v and Om_j.v do not depend on the sample, no sine is needed, and nothing of size d x d is
+ * formed (d accumulators per sample, as for the gradient; 4 d FMAs per (point, i, sample) where the gradient takes 3 d).
+ *   dsvgp_paths_hvp       `weights` as dsvgp_paths_prepare wrote them (unchanged); x[B, d]; v[B, d]: ONE vector per point, shared by
+ *                         all samples, used as given (not normalised) -> hv[n, B, d] = grad^2 f_s(x_b) v_b.  The host contract is
+ *                         dsvgp_paths_eval's: no host read, no synchronisation, no allocation, queued on the context's stream.
+ *                         d <= 32: ONE fused kernel of dsvgp_paths_eval's structure with v next to x~ and r in the lane's registers
+ *                         (narrower sample groups at the large d; workspace may be NULL): the result of (sample, point) is a function
+ *                         of that sample, that point and its vector alone.  Any other d: the same sums in GEMM shape through `workspace`
+ *                         (dsvgp_paths_hvp_workspace_bytes(M, d, F, n, B) bytes, 16-byte aligned; 0 for d <= 32) on the unsplit fp32
+ *                         MFMA GEMM, samples in groups sized by the helper.
+ * No floating-point atomics on either route: two identical calls return bitwise identical results.  DSVGP_EINVAL as for
+ * dsvgp_paths_eval: M, d, F, n or B < 1, a null required pointer (v included), a misaligned `weights`, or an intermediate that would
+ * pass 2^31 entries (split the batch).  The size helper is a pure host function (0 for d <= 32 and for arguments the entry refuses). */
+size_t dsvgp_paths_hvp_workspace_bytes(int M, int d, int F, int n, int B);
+int dsvgp_paths_hvp(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, const float* x, const float* v, int B, float* hv,
+                    void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
