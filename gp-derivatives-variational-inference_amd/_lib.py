@@ -202,6 +202,10 @@ SIGNATURES = {
     "dsvgp_paths_eval": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
     "dsvgp_paths_hvp_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "dsvgp_paths_hvp": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "dsvgp_paths_own_workspace_bytes": (_z, [_i, _i, _i, _i, _i, _i]),
+    "dsvgp_paths_eval_own": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "dsvgp_paths_descend_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dsvgp_paths_descend": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _f, _i, _i, _p, _p, _p, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1060,6 +1060,70 @@ def paths_hvp(ctx, weights, M, d, F, n, x, v, hv=None, workspace=None):
     return hv
 
 
+def paths_own_workspace_bytes(M, d, F, n, B, want_grad):
+    return int(lib.dsvgp_paths_own_workspace_bytes(int(M), int(d), int(F), int(n), int(B), 1 if want_grad else 0))
+
+
+def _req_own(t, shape, name, dtype=f32):
+    if not t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s %s tensor on the GPU, got %s %s"
+                         % (name, str(dtype).replace("torch.", ""), list(shape), t.dtype, tuple(t.shape)))
+    return t
+
+
+def paths_eval_own(ctx, weights, M, d, F, n, x, values=None, grads=None, workspace=None):
+    """values [n, B] = f_s(x[s][b]) and, when ``grads`` [n, B, d] is given, the gradients of n posterior paths, each at its OWN points
+    x [n, B, d] (dsvgp_paths_eval_own).  ``workspace``: uint8 tensor of dsvgp_paths_own_workspace_bytes(M, d, F, n, B, grads is not
+    None) bytes (None when that is 0)."""
+    _req(x, f32, "x", 3)
+    _req(weights, f32, "weights", 1)
+    if x.shape[0] != n or x.shape[2] != d or not x.is_contiguous():
+        raise ValueError("x must be a contiguous [%d, B, %d] tensor, got %s" % (n, d, tuple(x.shape)))
+    B = x.shape[1]
+    if values is None:
+        values = torch.empty(n, B, dtype=f32, device=x.device)
+    _req_own(values, (n, B), "values")
+    if grads is not None:
+        _req_own(grads, (n, B, d), "grads")
+    need = paths_own_workspace_bytes(M, d, F, n, B, grads is not None)
+    if need and (workspace is None or workspace.numel() * workspace.element_size() < need):
+        raise ValueError("paths_eval_own workspace too small: %d bytes needed" % need)
+    check(lib.dsvgp_paths_eval_own(ctx.h, _ptr(weights), M, d, F, n, _ptr(x), B, _ptr(values), _ptr(grads),
+                                   _ptr(workspace if need else None)), "dsvgp_paths_eval_own")
+    return values
+
+
+def paths_descend_workspace_bytes(M, d, F, n, B):
+    return int(lib.dsvgp_paths_descend_workspace_bytes(int(M), int(d), int(F), int(n), int(B)))
+
+
+def paths_descend(ctx, weights, M, d, F, n, x, lower, upper, iterations, initial_step, maximize, resume, values, grads, steps, accepted,
+                  workspace):
+    """``iterations`` projected gradient steps of every (sample, start) pair on its own path, in place on x [n, B, d] and the state
+    tensors values [n, B], grads [n, B, d], steps [n, B] (float32) and accepted [n, B] (int32) (dsvgp_paths_descend).  ``workspace``:
+    uint8 tensor of dsvgp_paths_descend_workspace_bytes(M, d, F, n, B) bytes."""
+    _req(x, f32, "x", 3)
+    _req(weights, f32, "weights", 1)
+    if x.shape[0] != n or x.shape[2] != d or not x.is_contiguous():
+        raise ValueError("x must be a contiguous [%d, B, %d] tensor, got %s" % (n, d, tuple(x.shape)))
+    B = x.shape[1]
+    _req_own(lower, (d,), "lower")
+    _req_own(upper, (d,), "upper")
+    _req_own(values, (n, B), "values")
+    _req_own(grads, (n, B, d), "grads")
+    _req_own(steps, (n, B), "steps")
+    _req_own(accepted, (n, B), "accepted", torch.int32)
+    need = paths_descend_workspace_bytes(M, d, F, n, B)
+    if need == 0:
+        raise ValueError("paths_descend: M, d, F, n, B = %d, %d, %d, %d, %d is not a shape the entry takes" % (M, d, F, n, B))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        raise ValueError("paths_descend workspace too small: %d bytes needed" % need)
+    check(lib.dsvgp_paths_descend(ctx.h, _ptr(weights), M, d, F, n, _ptr(x), B, _ptr(lower), _ptr(upper), int(iterations),
+                                  float(initial_step), 1 if maximize else 0, 1 if resume else 0, _ptr(values), _ptr(grads), _ptr(steps),
+                                  _ptr(accepted), _ptr(workspace)), "dsvgp_paths_descend")
+    return x
+
+
 def likelihood_terms(ctx, mu, var, y, p, hyp, mll_type, global_rows, mu_bar, var_bar, varn, scalars):
     check(lib.dsvgp_likelihood_terms(ctx.h, _ptr(mu), _ptr(var), _ptr(_req(y, f32, "y", 1)), mu.shape[0], p, _ptr(hyp),
                                      int(mll_type), float(global_rows), _ptr(mu_bar), _ptr(var_bar), _ptr(varn),

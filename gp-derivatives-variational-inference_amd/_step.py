@@ -15,6 +15,7 @@ K_XZ is not assembled (it is K_ZX^T) and the second triangular solve of the refe
 repeated (A_t == A); everything else keeps the reference's arithmetic precision: fp32 model, fp64
 Cholesky / triangular solves.
 """
+import collections
 import math
 import os
 import time
@@ -127,6 +128,11 @@ class MeanPredictor:
     def hessian(self, x):
         """grad^2 mu_f(x) [B, d, d], symmetrised, from d ``hvp`` calls with the unit vectors"""
         return self._paths().hessians(x)[0]
+
+
+PathDescent = collections.namedtuple("PathDescent", ["x", "values", "gradients", "steps", "accepted"])
+PathDescent.__doc__ = ("The state of ``SamplePaths.descend``: iterates x [n, B, d], their values [n, B] and gradients [n, B, d] on their own "
+                       "paths, the step length [n, B] and the number of accepted steps [n, B] (int32) of every (sample, start) pair")
 
 
 class SamplePaths:
@@ -242,6 +248,109 @@ class SamplePaths:
             _ops.paths_hvp(ctx, self.weights, self.M, d, self.num_features, n, x[r0:r1], v[r0:r1], h, self._hvp_workspace(r1 - r0))
             hv[:, r0:r1] = h
         return hv
+
+    # ---- every path at its OWN points (dsvgp_paths_eval_own) and the descent built on it (dsvgp_paths_descend) ----
+    def _own_check(self, x, what="x"):
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise _lib.DsvgpError("%s must live on the GPU: the DSVGP hot path has no CPU fallback" % what)
+        if x.dim() != 3 or x.shape[0] != self.num_samples or x.shape[2] != self.d:
+            raise ValueError("%s must be [n, B, d] = [%d, B, %d] (the points of every sample), got %s"
+                             % (what, self.num_samples, self.d, tuple(x.shape)))
+        return x.to(f32).contiguous()
+
+    def _run_own(self, x, want_grad):
+        x = self._own_check(x)
+        ctx = _ops.Context.get(self.device)
+        n, B, d = x.shape
+        values = torch.empty(n, B, dtype=f32, device=self.device)
+        grads = torch.empty(n, B, d, dtype=f32, device=self.device) if want_grad else None
+        if B == 0:
+            return values, grads
+        need = lambda r: _ops.paths_own_workspace_bytes(self.M, d, self.num_features, n, r, want_grad)
+        rows = self._fit_rows(B, need)
+        if rows >= B:
+            _ops.paths_eval_own(ctx, self.weights, self.M, d, self.num_features, n, x, values, grads, self._buffer(need(B)))
+            return values, grads
+        for r0 in range(0, B, rows):                # point blocks: the entry reads and writes [n, rows] contiguous
+            r1 = min(B, r0 + rows)
+            v = torch.empty(n, r1 - r0, dtype=f32, device=self.device)
+            g = torch.empty(n, r1 - r0, d, dtype=f32, device=self.device) if want_grad else None
+            _ops.paths_eval_own(ctx, self.weights, self.M, d, self.num_features, n, x[:, r0:r1].contiguous(), v, g,
+                                self._buffer(need(r1 - r0)))
+            values[:, r0:r1] = v
+            if want_grad:
+                grads[:, r0:r1] = g
+        return values, grads
+
+    @torch.no_grad()
+    def values_at(self, x):
+        """f_s(x[s][b]) [n, B] for x [n, B, d]: every path at its OWN points (dsvgp_paths_eval_own; ``values`` shares one point set)"""
+        return self._run_own(x, False)[0]
+
+    @torch.no_grad()
+    def values_and_gradients_at(self, x):
+        """(f_s(x[s][b]) [n, B], grad f_s(x[s][b]) [n, B, d]) for x [n, B, d]; the gradient carries no constant.  d <= 32: the result of
+        (sample, point) does not depend on the batch it is evaluated in, and ``values_at`` returns the same values bits."""
+        return self._run_own(x, True)
+
+    @torch.no_grad()
+    def descend(self, x0, lower, upper, iterations=20, initial_step=None, maximize=False, state=None):
+        """``iterations`` projected gradient steps of every (sample, start) pair x0 [n, B, d] on its OWN path inside the box
+        [lower, upper] ([d] each), one C call with no host read (dsvgp_paths_descend): one trial per iteration, accepted when it
+        passes the Armijo test with c1 = 1e-4, the pair's step length doubled after an accepted trial and halved after a rejected
+        one; ``initial_step`` (a length in x; None: a quarter lengthscale) divided by |grad| is the first step length.  Returns a
+        ``PathDescent``; the values never get worse.  ``state``: a previous ``PathDescent`` to continue from (``x0`` is then not
+        read and may be None).  ``x0`` is not modified."""
+        resume = state is not None
+        iterations = int(iterations)
+        if iterations < 0:
+            raise ValueError("descend needs iterations >= 0, got %d" % iterations)
+        src = state.x if resume else x0
+        x = self._own_check(src, "state.x" if resume else "x0")
+        n, B, d = x.shape
+        box = []
+        for name, t in (("lower", lower), ("upper", upper)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise _lib.DsvgpError("%s must live on the GPU: the DSVGP hot path has no CPU fallback" % name)
+            if tuple(t.shape) != (d,):
+                raise ValueError("%s must be [d] = [%d], got %s" % (name, d, tuple(t.shape)))
+            box.append(t.to(f32).contiguous())
+        if x.data_ptr() == src.data_ptr():
+            x = x.clone()                           # the entry works in place
+        if resume:
+            for name, t, shape in (("values", state.values, (n, B)), ("gradients", state.gradients, (n, B, d)),
+                                   ("steps", state.steps, (n, B)), ("accepted", state.accepted, (n, B))):
+                if not torch.is_tensor(t) or not t.is_cuda:
+                    raise _lib.DsvgpError("state.%s must live on the GPU" % name)
+                if tuple(t.shape) != shape:
+                    raise ValueError("state.%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
+            values, grads = state.values.to(f32).clone(), state.gradients.to(f32).clone()
+            steps, accepted = state.steps.to(f32).clone(), state.accepted.to(torch.int32).clone()
+        else:
+            values = torch.empty(n, B, dtype=f32, device=self.device)
+            grads = torch.empty(n, B, d, dtype=f32, device=self.device)
+            steps = torch.empty(n, B, dtype=f32, device=self.device)
+            accepted = torch.empty(n, B, dtype=torch.int32, device=self.device)
+        out = PathDescent(x, values, grads, steps, accepted)
+        if B == 0:
+            return out
+        ctx = _ops.Context.get(self.device)
+        step0 = -1.0 if initial_step is None else float(initial_step)
+        need = lambda r: _ops.paths_descend_workspace_bytes(self.M, d, self.num_features, n, r)
+        rows = self._fit_rows(B, need)
+        args = (self.M, d, self.num_features, n)
+        if rows >= B:
+            _ops.paths_descend(ctx, self.weights, *args, x, box[0], box[1], iterations, step0, maximize, resume, values, grads, steps,
+                               accepted, self._buffer(need(B)))
+            return out
+        for r0 in range(0, B, rows):                # the pairs are independent: blocks of starts, one call each
+            r1 = min(B, r0 + rows)
+            part = [t[:, r0:r1].contiguous() for t in out]
+            _ops.paths_descend(ctx, self.weights, *args, part[0], box[0], box[1], iterations, step0, maximize, resume, part[1], part[2],
+                               part[3], part[4], self._buffer(need(r1 - r0)))
+            for t, q in zip(out, part):
+                t[:, r0:r1] = q
+        return out
 
     @torch.no_grad()
     def hessians(self, x):

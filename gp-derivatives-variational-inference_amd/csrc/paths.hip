@@ -18,6 +18,9 @@
 //             point alone: no atomics, no dependence on B, n, the neighbours or the card.
 //   d > 32    the same sums in GEMM shape through the caller's workspace on the fp32 MFMA GEMM (unsplit: no floating-point atomics),
 //             with pointwise kernels between the products.
+// dsvgp_paths_eval_own evaluates sample s at its OWN points x[s] on the same two routes (one sample per workgroup; the n B points as rows
+// of one stacked problem with one product per sample), and dsvgp_paths_descend builds a device-resident projected gradient descent of
+// every (sample, start) pair on it.
 #include "common.h"
 #include "paths_plan.h"
 
@@ -659,6 +662,267 @@ int launch_hvp_fused(hipStream_t st, const float* w, const PathsWeights& L, int 
     return 0;
 }
 
+// ---- own-point evaluation: sample s at its own points x[s][B][d] (dsvgp_paths_eval_own) --------------------------------------------
+// Fused route (d <= 32): paths_fused_kernel<D> at ONE sample per workgroup -- grid [point tiles, samples], lane = point, the lane holds
+// x~[D], r[D], acc[D] and sig.  The expression sequence of a (sample, point) is the shared-point kernel's; contraction is off so that
+// the instance without gradients forms the value from the same operations as the one with them.
+template <int D, bool WANT_GRAD>
+__global__ __launch_bounds__(PP_NW * 64) void paths_own_fused_kernel(const float* __restrict__ w, PathsWeights L, int M, int d, int F,
+                                                                     const float* __restrict__ x, int64_t B, float* __restrict__ values,
+                                                                     float* __restrict__ grads) {
+#pragma clang fp contract(off)
+    constexpr PathsLds LD = paths_own_lds(D);
+    constexpr int NT = PP_NW * 64;
+    __shared__ __align__(16) float lds[LD.floats];
+    const int tid = threadIdx.x, lane = tid & 63, slice = tid >> 6;
+    const int64_t b0 = (int64_t)blockIdx.x * PP_TP;
+    const int64_t b = b0 + lane;
+    const int s = blockIdx.y;
+    const size_t so = paths_own_row(s, B, b0);             // first (sample, point) pair of this workgroup
+    const float ell = w[0];
+    float xt[D], r[D], acc[D], sig = 0.f;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        xt[k] = (k < d && b < B) ? (x[(so + lane) * d + k] - w[L.o_center + k]) / ell : 0.f;
+        acc[k] = 0.f;
+    }
+    // ---- update term: the inducing points in chunks of PP_CH ----
+    for (int c0 = 0; c0 < M; c0 += PP_CH) {
+        const int nc = M - c0 < PP_CH ? M - c0 : PP_CH;
+        __syncthreads();                                  // the previous chunk has been consumed
+        const float4* srcZ = reinterpret_cast<const float4*>(w + L.o_z + (size_t)c0 * D);
+        const float4* srcG = reinterpret_cast<const float4*>(w + L.o_g + ((size_t)s * M + c0) * D);
+        for (int t = tid; t < nc * (D / 4); t += NT) {
+            reinterpret_cast<float4*>(lds + LD.o_z)[t] = srcZ[t];
+            reinterpret_cast<float4*>(lds + LD.o_g)[t] = srcG[t];
+        }
+        if (tid < nc) lds[LD.o_a + tid] = w[L.o_a + (size_t)s * L.Mr + c0 + tid];
+        __syncthreads();
+        for (int i = paths_own_first(slice); i < nc; i += PP_NW) {      // every LDS read below is one address per wave (broadcast)
+            const float* z = lds + LD.o_z + i * D;
+            const float* gp = lds + LD.o_g + i * D;
+            float r2 = 0.f, rg = 0.f;
+#pragma unroll
+            for (int k = 0; k < D; ++k) {
+                r[k] = z[k] - xt[k];
+                r2 = __builtin_fmaf(r[k], r[k], r2);
+            }
+            const float kk = __expf(-0.5f * r2);
+#pragma unroll
+            for (int k = 0; k < D; ++k) rg = __builtin_fmaf(r[k], gp[k], rg);
+            const float P = kk * (lds[LD.o_a + i] - rg);                  // k_i beta_is
+            sig += P;
+            if (WANT_GRAD) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) acc[k] = __builtin_fmaf(P, r[k], __builtin_fmaf(kk, gp[k], acc[k]));
+            }
+        }
+    }
+    // ---- prior term: the features in chunks of PP_CH ----
+    for (int j0 = 0; j0 < F; j0 += PP_CH) {
+        const int nf = F - j0 < PP_CH ? F - j0 : PP_CH;
+        __syncthreads();
+        const float4* srcO = reinterpret_cast<const float4*>(w + L.o_om + (size_t)j0 * D);
+        for (int t = tid; t < nf * (D / 4); t += NT) reinterpret_cast<float4*>(lds + LD.o_om)[t] = srcO[t];
+        if (tid < nf) {
+            lds[LD.o_ph + tid] = w[L.o_ph + j0 + tid];
+            lds[LD.o_w + tid] = w[L.o_wq + (size_t)s * L.Fr + j0 + tid];
+        }
+        __syncthreads();
+        for (int j = paths_own_first(slice); j < nf; j += PP_NW) {
+            const float* om = lds + LD.o_om + j * D;
+            float th = lds[LD.o_ph + j];
+#pragma unroll
+            for (int k = 0; k < D; ++k) th = __builtin_fmaf(om[k], xt[k], th);
+            th = __builtin_amdgcn_fractf(th);
+            const float cs = __builtin_amdgcn_cosf(th);
+            const float wj = lds[LD.o_w + j];
+            sig = __builtin_fmaf(wj, cs, sig);
+            if (WANT_GRAD) {
+                const float sn = -PP_TWO_PI * __builtin_amdgcn_sinf(th);
+                const float t = wj * sn;
+#pragma unroll
+                for (int k = 0; k < D; ++k) acc[k] = __builtin_fmaf(t, om[k], acc[k]);
+            }
+        }
+    }
+    // ---- the waves' partial sums, added in the fixed order 0 + 1 + .. + 7 ----
+    float* red = lds + LD.o_red;
+    for (int q = 1; q < PP_NW; ++q) {
+        __syncthreads();
+        if (slice == q) {
+            if (WANT_GRAD) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) red[paths_own_red(lane, k, D)] = acc[k];
+            }
+            red[paths_own_red(lane, D, D)] = sig;
+        }
+        __syncthreads();
+        if (slice == 0) {
+            if (WANT_GRAD) {
+#pragma unroll
+                for (int k = 0; k < D; ++k) acc[k] += red[paths_own_red(lane, k, D)];
+            }
+            sig += red[paths_own_red(lane, D, D)];
+        }
+    }
+    __syncthreads();
+    const float sc = w[1], c = w[2], s_ell = w[4];
+    if (slice == 0) {
+        if (WANT_GRAD) {
+#pragma unroll
+            for (int k = 0; k < D; ++k) red[paths_own_red(lane, k, D)] = s_ell * acc[k];
+        }
+        red[paths_own_red(lane, D, D)] = __builtin_fmaf(sc, sig, c);
+    }
+    __syncthreads();
+    const int npts = (int)(B - b0 < PP_TP ? B - b0 : PP_TP);
+    if (tid < npts) values[so + tid] = red[paths_own_red(tid, D, D)];
+    if (WANT_GRAD) {
+        for (int t = tid; t < npts * d; t += NT) {
+            const int pt = t / d, k = t - pt * d;
+            grads[so * d + t] = red[paths_own_red(pt, k, D)];
+        }
+    }
+}
+
+template <int D>
+int launch_own_fused(hipStream_t st, const float* w, const PathsWeights& L, int M, int d, int F, int n, const float* x, int B,
+                     float* values, float* grads) {
+    const dim3 grid(cdiv(B, PP_TP), n), block(PP_NW * 64);
+    if (grads) hipLaunchKernelGGL((paths_own_fused_kernel<D, true>), grid, block, 0, st, w, L, M, d, F, x, (int64_t)B, values, grads);
+    else hipLaunchKernelGGL((paths_own_fused_kernel<D, false>), grid, block, 0, st, w, L, M, d, F, x, (int64_t)B, values, grads);
+    DSVGP_LAUNCH_CHECK();
+    return 0;
+}
+
+// composed route.  Theta -> the prior's value vp[row] = sum_j cos_j wq_s[j] (fixed order) and, with gradients, T = wq_s o (-2 pi sin)
+// in place (zero from F up to ldF): one workgroup per row, s = row / B
+__global__ __launch_bounds__(256) void paths_own_feature_kernel(const float* __restrict__ w, PathsWeights L, int F, int B,
+                                                               float* __restrict__ T, int ldF, float* __restrict__ vp, int want_grad) {
+    __shared__ float part[4];
+    const int row = blockIdx.x, tid = threadIdx.x, s = row / B;
+    const float* wq = w + L.o_wq + (size_t)s * L.Fr;
+    float* Tr = T + (size_t)row * ldF;
+    float acc = 0.f;
+    for (int j = tid; j < ldF; j += 256) {
+        float sn = 0.f;
+        if (j < F) {
+            const float th = __builtin_amdgcn_fractf(Tr[j] + w[L.o_ph + j]);
+            acc = __builtin_fmaf(wq[j], __builtin_amdgcn_cosf(th), acc);
+            sn = wq[j] * (-PP_TWO_PI * __builtin_amdgcn_sinf(th));
+        }
+        if (want_grad) Tr[j] = sn;
+    }
+    acc = wave_sum(acc);
+    if ((tid & 63) == 0) part[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) vp[row] = ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+// P[row][i] = k[row][i] (a'_s[i] + S2[row][i]) in place of S2, sigma[row] = sum_i P: one workgroup per row, fixed-order sums
+__global__ __launch_bounds__(256) void paths_own_pointwise_kernel(const float* __restrict__ w, PathsWeights L, int M, int B,
+                                                                 const float* __restrict__ K, float* __restrict__ P, int ldM,
+                                                                 float* __restrict__ sigma) {
+    __shared__ float part[4];
+    const int row = blockIdx.x, tid = threadIdx.x, s = row / B;
+    const float* ap = w + L.o_ap + (size_t)s * L.Mr;
+    const float* Kr = K + (size_t)row * ldM;
+    float* Pr = P + (size_t)row * ldM;
+    float acc = 0.f;
+    for (int i = tid; i < ldM; i += 256) {
+        float v = 0.f;
+        if (i < M) v = Kr[i] * (ap[i] + Pr[i]);
+        Pr[i] = v;
+        acc += v;
+    }
+    acc = wave_sum(acc);
+    if ((tid & 63) == 0) part[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) sigma[row] = ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+// values[row] = c + s (sigma + vp), grads[row][:] = (s / ell)(O1 + O2 - sigma x~ + GP): one wave per row
+__global__ __launch_bounds__(256) void paths_own_epilogue_kernel(const float* __restrict__ w, int N, int d, int ldw,
+                                                                const float* __restrict__ Xt, const float* __restrict__ sigma,
+                                                                const float* __restrict__ vp, const float* __restrict__ O1,
+                                                                const float* __restrict__ O2, const float* __restrict__ GP,
+                                                                float* __restrict__ values, float* __restrict__ grads) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= N) return;
+    const float sc = w[1], c = w[2], s_ell = w[4];
+    const float sg = sigma[row];
+    if (lane == 0) values[row] = __builtin_fmaf(sc, sg + vp[row], c);
+    if (!grads) return;
+    const size_t o = (size_t)row * ldw;
+    for (int k = lane; k < d; k += 64) grads[(size_t)row * d + k] = s_ell * (((O1[o + k] + O2[o + k]) - sg * Xt[o + k]) + GP[o + k]);
+}
+
+// ---- device-resident descent (dsvgp_paths_descend; the rule and its constants: paths_plan.h) -------------------------------------------
+// x <- clamp(x, lower, upper), elementwise
+__global__ __launch_bounds__(256) void paths_descend_clamp_kernel(float* __restrict__ x, int64_t total, int d, const float* __restrict__ lower,
+                                                                 const float* __restrict__ upper) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total) return;
+    const int k = (int)(t % d);
+    x[t] = fminf(fmaxf(x[t], lower[k]), upper[k]);
+}
+
+// one wave per (sample, start) pair, lanes over the coordinates; the dot product and the norm are a per-lane sum in the order of k and a
+// butterfly over the wave.  mode 0: first step length from |g|, accepted = 0; mode 1: nothing (the state is a previous call's);
+// mode 2: judge the trial (y, fy, gy) of this iteration and update the pair.  Every mode ends with the proposal of the next iteration
+// y = clamp(x - sigma eta g).
+__global__ __launch_bounds__(256) void paths_descend_step_kernel(const float* __restrict__ w, int mode, int N, int d, float sgn,
+                                                                float initial_step, const float* __restrict__ lower,
+                                                                const float* __restrict__ upper, float* __restrict__ x,
+                                                                float* __restrict__ f, float* __restrict__ g, float* __restrict__ eta,
+                                                                int* __restrict__ accepted, float* __restrict__ y,
+                                                                const float* __restrict__ fy, const float* __restrict__ gy) {
+    const int pair = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (pair >= N) return;
+    const size_t o = (size_t)pair * d;
+    float step;
+    bool take = false;
+    if (mode == 0) {
+        float nn = 0.f;
+        for (int k = lane; k < d; k += 64) nn = __builtin_fmaf(g[o + k], g[o + k], nn);
+        nn = wave_sum(nn);
+        const float step0 = initial_step > 0.f ? initial_step : PP_DESCEND_STEP0 * w[0];
+        step = fminf(step0 / fmaxf(sqrtf(nn), PP_DESCEND_TINY), PP_DESCEND_ETA_MAX);
+        if (lane == 0) {
+            eta[pair] = step;
+            accepted[pair] = 0;
+        }
+    } else if (mode == 1) {
+        step = eta[pair];
+    } else {
+        float dot = 0.f;
+        for (int k = lane; k < d; k += 64) dot = __builtin_fmaf(g[o + k], y[o + k] - x[o + k], dot);
+        dot = wave_sum(dot);
+        const float f0 = f[pair], f1 = fy[pair];
+        take = sgn * f1 <= sgn * f0 + PP_DESCEND_C1 * (sgn * dot);        // (a NaN f1 compares false: rejected)
+        step = eta[pair];
+        step = take ? fminf(PP_DESCEND_GROW * step, PP_DESCEND_ETA_MAX) : PP_DESCEND_SHRINK * step;
+        if (lane == 0) {
+            eta[pair] = step;
+            if (take) {
+                f[pair] = f1;
+                accepted[pair] += 1;
+            }
+        }
+    }
+    for (int k = lane; k < d; k += 64) {
+        float xk = x[o + k], gk = g[o + k];
+        if (take) {
+            xk = y[o + k];
+            gk = gy[o + k];
+            x[o + k] = xk;
+            g[o + k] = gk;
+        }
+        y[o + k] = fminf(fmaxf(xk - sgn * (step * gk), lower[k]), upper[k]);
+    }
+}
+
 bool paths_shape_ok(int M, int d, int F, int n) {
     return M >= 1 && d >= 1 && F >= 1 && n >= 1 && (long long)n * M * paths_pad4(d) <= PP_IDX_MAX * 4 &&
            (long long)F * paths_pad4(d) <= PP_IDX_MAX && (long long)n * paths_pad4(F) <= PP_IDX_MAX;
@@ -836,6 +1100,116 @@ extern "C" int dsvgp_paths_hvp(dsvgp_ctx* ctx, const float* weights, int M, int 
         if (int rc = unsplit_gemm(ctx, 0, B, ng * L.ldw, F, T, S.ldF, WO, (int64_t)ng * L.ldw, GP, (int64_t)ng * L.ldw)) return rc;
         hipLaunchKernelGGL(paths_hvp_epilogue_kernel, dim3(cdiv(B, 4), ng), dim3(256), 0, st, weights, L, B, d, s0, ng, Xt, Vp, sig, sig1,
                            S.Br, O1, O2, GP, hv);
+        DSVGP_LAUNCH_CHECK();
+    }
+    return 0;
+}
+
+extern "C" size_t dsvgp_paths_own_workspace_bytes(int M, int d, int F, int n, int B, int want_grad) {
+    if (!paths_shape_ok(M, d, F, n) || B < 1 || n > 65535) return 0;
+    if (d <= PP_FUSED_MAX_D) return 0;                    // the fused kernel keeps everything in registers and LDS
+    PathsOwnWork S;
+    if (paths_own_work(M, d, F, n, B, want_grad != 0, S)) return 0;
+    return S.total * sizeof(float);
+}
+
+extern "C" int dsvgp_paths_eval_own(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, const float* x, int B, float* values,
+                                    float* grads, void* workspace) {
+    if (!ctx || !weights || !x || !values || !paths_shape_ok(M, d, F, n) || B < 1 || n > 65535) return DSVGP_EINVAL;
+    if ((int64_t)n * B * d > PP_IDX_MAX) return DSVGP_EINVAL;
+    if ((uintptr_t)weights % 16) return DSVGP_EINVAL;
+    const PathsWeights L = paths_weights(M, d, F, n);
+    hipStream_t st = ctx->stream;
+    if (d <= PP_FUSED_MAX_D) {
+        switch (L.ldw) {
+            case 4: return launch_own_fused<4>(st, weights, L, M, d, F, n, x, B, values, grads);
+            case 8: return launch_own_fused<8>(st, weights, L, M, d, F, n, x, B, values, grads);
+            case 12: return launch_own_fused<12>(st, weights, L, M, d, F, n, x, B, values, grads);
+            case 16: return launch_own_fused<16>(st, weights, L, M, d, F, n, x, B, values, grads);
+            case 20: return launch_own_fused<20>(st, weights, L, M, d, F, n, x, B, values, grads);
+            case 24: return launch_own_fused<24>(st, weights, L, M, d, F, n, x, B, values, grads);
+            case 28: return launch_own_fused<28>(st, weights, L, M, d, F, n, x, B, values, grads);
+            default: return launch_own_fused<32>(st, weights, L, M, d, F, n, x, B, values, grads);
+        }
+    }
+    if (!workspace || (uintptr_t)workspace % 16) return DSVGP_EINVAL;
+    PathsOwnWork S;
+    if (paths_own_work(M, d, F, n, B, grads != nullptr, S)) return DSVGP_EINVAL;    // (an intermediate past 2^31 entries: split the points)
+    float* ws = (float*)workspace;
+    float *Xt = ws + S.o_x, *xn = ws + S.o_xn, *K = ws + S.o_k, *T = ws + S.o_t, *vp = ws + S.o_vp, *P = ws + S.o_p, *sig = ws + S.o_sig;
+    float *O1 = ws + S.o_o1, *O2 = ws + S.o_o2, *GP = ws + S.o_gp;
+    const float *Zt = weights + L.o_z, *Om = weights + L.o_om, *G = weights + L.o_g;
+    const int KP = DSVGP_GEMM_TRANS_B | DSVGP_GEMM_K_PADDED;
+    const int N = (int)S.N;
+    // all n B points as the rows of one X~
+    hipLaunchKernelGGL(paths_pack_x_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, weights, L, x, N, d, Xt, xn);
+    DSVGP_LAUNCH_CHECK();
+    // S1 = X~ Z~^T -> k, stacked
+    if (int rc = unsplit_gemm(ctx, KP, N, M, d, Xt, S.ldw, Zt, L.ldw, K, S.ldM)) return rc;
+    hipLaunchKernelGGL(paths_k_kernel, dim3(cdiv((int64_t)N * S.ldM, 256)), dim3(256), 0, st, weights, L, M, N, K, S.ldM, xn);
+    DSVGP_LAUNCH_CHECK();
+    // Theta = X~ Om^T, stacked -> the prior's value (a fixed-order row dot with wq_s) and wq_s o S in place
+    if (int rc = unsplit_gemm(ctx, KP, N, F, d, Xt, S.ldw, Om, L.ldw, T, S.ldF)) return rc;
+    hipLaunchKernelGGL(paths_own_feature_kernel, dim3(N), dim3(256), 0, st, weights, L, F, B, T, S.ldF, vp, grads ? 1 : 0);
+    DSVGP_LAUNCH_CHECK();
+    // S2_s = X~_s G'_s^T: one product per sample on its row block; P = k o (a'_s + S2_s) and its row sums in place
+    for (int s = 0; s < n; ++s)
+        if (int rc = unsplit_gemm(ctx, KP, B, M, d, Xt + (size_t)s * B * S.ldw, S.ldw, G + (size_t)s * M * L.ldw, L.ldw,
+                                  P + (size_t)s * B * S.ldM, S.ldM))
+            return rc;
+    hipLaunchKernelGGL(paths_own_pointwise_kernel, dim3(N), dim3(256), 0, st, weights, L, M, B, K, P, S.ldM, sig);
+    DSVGP_LAUNCH_CHECK();
+    if (grads) {
+        // O1 = P Z~ stacked, O2_s = K_s G'_s per sample, GP = (wq_s o S) Om stacked
+        if (int rc = unsplit_gemm(ctx, 0, N, d, M, P, S.ldM, Zt, L.ldw, O1, S.ldw)) return rc;
+        for (int s = 0; s < n; ++s)
+            if (int rc = unsplit_gemm(ctx, 0, B, d, M, K + (size_t)s * B * S.ldM, S.ldM, G + (size_t)s * M * L.ldw, L.ldw,
+                                      O2 + (size_t)s * B * S.ldw, S.ldw))
+                return rc;
+        if (int rc = unsplit_gemm(ctx, 0, N, d, F, T, S.ldF, Om, L.ldw, GP, S.ldw)) return rc;
+    }
+    hipLaunchKernelGGL(paths_own_epilogue_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, weights, N, d, S.ldw, Xt, sig, vp, O1, O2, GP, values,
+                       grads);
+    DSVGP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t dsvgp_paths_descend_workspace_bytes(int M, int d, int F, int n, int B) {
+    if (!paths_shape_ok(M, d, F, n) || B < 1 || n > 65535) return 0;
+    PathsDescendWork S;
+    if (paths_descend_work(M, d, F, n, B, S)) return 0;
+    return S.total * sizeof(float);
+}
+
+extern "C" int dsvgp_paths_descend(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, float* x, int B, const float* lower,
+                                   const float* upper, int iterations, float initial_step, int maximize, int resume, float* values,
+                                   float* grads, float* steps, int* accepted, void* workspace) {
+    if (!ctx || !weights || !x || !lower || !upper || !values || !grads || !steps || !accepted || !workspace || iterations < 0 ||
+        !paths_shape_ok(M, d, F, n) || B < 1 || n > 65535)
+        return DSVGP_EINVAL;
+    if ((uintptr_t)weights % 16 || (uintptr_t)workspace % 16) return DSVGP_EINVAL;
+    PathsDescendWork S;
+    if (paths_descend_work(M, d, F, n, B, S)) return DSVGP_EINVAL;
+    float* ws = (float*)workspace;
+    float *y = ws + S.o_y, *gy = ws + S.o_gy, *fy = ws + S.o_fy;
+    void* evw = d <= PP_FUSED_MAX_D ? nullptr : (void*)(ws + S.o_eval);
+    const int N = n * B;
+    const float sgn = maximize ? -1.f : 1.f;
+    hipStream_t st = ctx->stream;
+    auto step = [&](int mode) {
+        hipLaunchKernelGGL(paths_descend_step_kernel, dim3(cdiv(N, 4)), dim3(256), 0, st, weights, mode, N, d, sgn, initial_step, lower, upper,
+                           x, values, grads, steps, accepted, y, fy, gy);
+    };
+    if (!resume) {
+        hipLaunchKernelGGL(paths_descend_clamp_kernel, dim3(cdiv((int64_t)N * d, 256)), dim3(256), 0, st, x, (int64_t)N * d, d, lower, upper);
+        DSVGP_LAUNCH_CHECK();
+        if (int rc = dsvgp_paths_eval_own(ctx, weights, M, d, F, n, x, B, values, grads, evw)) return rc;
+    }
+    step(resume ? 1 : 0);
+    DSVGP_LAUNCH_CHECK();
+    for (int t = 0; t < iterations; ++t) {
+        if (int rc = dsvgp_paths_eval_own(ctx, weights, M, d, F, n, y, B, fy, gy, evw)) return rc;
+        step(2);
         DSVGP_LAUNCH_CHECK();
     }
     return 0;

@@ -171,3 +171,81 @@ inline int paths_hvp_work(int M, int d, int F, int n, int B, PathsHvpWork& s) {
     s.total = o;
     return 0;
 }
+
+// ---- own-point evaluation (paths_own_fused_kernel<D, WANT_GRAD>, dsvgp_paths_eval_own): sample s at its OWN points x[s][B][d] ------
+// Fused kernel (d <= 32): a workgroup of PP_NW waves owns PP_TP = 64 points of ONE sample (grid = [point tiles, samples], lane = point);
+// there is no sample group, so the lane holds x~[D], r[D], acc[D] and sig only.  The chunking and the ownership are those above (wave w
+// owns the entries w, w + PP_NW, ... of every chunk of PP_CH); the three LDS images are the ones above at NS = 1:
+//   inducing chunk   Z~[CH][D] | G'_s[CH][D] | a_s[CH]
+//   feature chunk    Om[CH][D] | phase[CH] | wq_s[CH]
+//   reduction        red[TP][D + 1]
+constexpr PathsLds paths_own_lds(int D) { return paths_lds_ns(D, 1); }
+constexpr int paths_own_first(int wave) { return wave; }                 // first entry of a chunk a wave owns; the stride is PP_NW
+constexpr int paths_own_red(int point, int k, int D) { return point * (D + 1) + k; }      // k = D: the value
+// global float offsets of (sample, point tile): the first point of the tile in x / grads ([n][B][d]) and in values ([n][B])
+constexpr size_t paths_own_row(int s, long long B, long long b0) { return (size_t)s * (size_t)B + (size_t)b0; }
+
+// Composed route (any other d): all N = n B (sample, point) pairs are rows of ONE stacked problem; the per-sample operands G'_s enter
+// through one product per sample on the sample's row block.  Workspace (floats):
+//   X~[N][ldw] | xn[Nr] | K[N][ldM] | T[N][ldF] (Theta, then wq_s o S in place) | vp[Nr] | P[N][ldM] (S2, then P in place) | sigma[Nr]
+//   (+ O1[N][ldw] | O2[N][ldw] | GP[N][ldw] with gradients)
+struct PathsOwnWork {
+    int ldw, ldM, ldF;
+    long long N;
+    size_t Nr, o_x, o_xn, o_k, o_t, o_vp, o_p, o_sig, o_o1, o_o2, o_gp, total;
+};
+
+// 0, or -1 for a shape the composed route refuses (an intermediate would pass 2^31 entries: split the points)
+inline int paths_own_work(int M, int d, int F, int n, int B, int want_grad, PathsOwnWork& s) {
+    if (M < 1 || d < 1 || F < 1 || n < 1 || B < 1) return -1;
+    s = PathsOwnWork{};
+    s.ldw = paths_pad4(d); s.ldM = paths_pad4(M); s.ldF = paths_pad4(F);
+    s.N = (long long)n * B;
+    if (s.N > PP_IDX_MAX) return -1;
+    s.Nr = paths_pad4z((size_t)s.N);
+    const long long big[] = {s.N * s.ldw, s.N * s.ldM, s.N * s.ldF};
+    for (long long v : big)
+        if (v > PP_IDX_MAX) return -1;
+    const size_t N = (size_t)s.N;
+    size_t o = 0;
+    s.o_x = o;   o += N * s.ldw;
+    s.o_xn = o;  o += s.Nr;
+    s.o_k = o;   o += N * s.ldM;
+    s.o_t = o;   o += N * s.ldF;
+    s.o_vp = o;  o += s.Nr;
+    s.o_p = o;   o += N * s.ldM;
+    s.o_sig = o; o += s.Nr;
+    s.o_o1 = o;  o += want_grad ? N * s.ldw : 0;
+    s.o_o2 = o;  o += want_grad ? N * s.ldw : 0;
+    s.o_gp = o;  o += want_grad ? N * s.ldw : 0;
+    s.total = o;
+    return 0;
+}
+
+// ---- device-resident descent (dsvgp_paths_descend): projected gradient steps of every (sample, start) pair on its own path ----------
+// One trial per iteration, a step length per pair: accept iff  sigma f_y <= sigma f + c1 sigma g.(y - x)  (sigma = +1 to minimise, -1 to
+// maximise), then eta <- min(GROW eta, ETA_MAX), else eta <- SHRINK eta.  Workspace (floats): y[N d'] | gy[N d'] | fy[Nr] and behind them
+// the evaluation's own (d' = N d padded to 4 floats; N = n B).
+constexpr float PP_DESCEND_C1 = 1e-4f;
+constexpr float PP_DESCEND_GROW = 2.f;
+constexpr float PP_DESCEND_SHRINK = 0.5f;
+constexpr float PP_DESCEND_ETA_MAX = 1e30f;              // the finite ceiling of a step length
+constexpr float PP_DESCEND_TINY = 1e-30f;                // floor of |g| in the first step length
+constexpr float PP_DESCEND_STEP0 = 0.25f;                // initial_step <= 0: this many lengthscales
+struct PathsDescendWork { size_t o_y, o_gy, o_fy, o_eval, total; };
+inline int paths_descend_work(int M, int d, int F, int n, int B, PathsDescendWork& s) {
+    if (M < 1 || d < 1 || F < 1 || n < 1 || B < 1) return -1;
+    s = PathsDescendWork{};
+    const long long N = (long long)n * B;
+    if (N > PP_IDX_MAX || N * d > PP_IDX_MAX) return -1;
+    size_t ev = 0;
+    if (d > PP_FUSED_MAX_D) {
+        PathsOwnWork w;
+        if (paths_own_work(M, d, F, n, B, 1, w)) return -1;
+        ev = w.total;
+    }
+    const size_t nd = paths_pad4z((size_t)N * d), nr = paths_pad4z((size_t)N);
+    s.o_y = 0; s.o_gy = nd; s.o_fy = 2 * nd; s.o_eval = 2 * nd + nr;
+    s.total = s.o_eval + ev;
+    return 0;
+}

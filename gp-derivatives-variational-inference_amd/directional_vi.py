@@ -723,6 +723,27 @@ def eval_paths(dataset_or_tensor, paths, minibatch_size, gradients=False):
     return (values, torch.cat(grads, dim=1)) if gradients else values
 
 
+def thompson_candidates(paths, candidates, lower, upper, num_starts=8, iterations=20, maximize=False):
+    """One Thompson step with refinement: every path (``model.sample_paths(...)``) is evaluated at the shared ``candidates`` [N, d]
+    (``paths.values``), its ``num_starts`` best candidates become its own starts [n, num_starts, d], ``paths.descend`` refines each
+    start ON ITS OWN PATH inside the box [lower, upper] ([d] each) and the best refined start per path is returned:
+    (x_next [n, d], f_next [n], f_candidates_best [n]) with f_next never worse than f_candidates_best, the path's best value over
+    the candidates (what the reference's TuRBO loops stop at: the arg-min of each joint draw)."""
+    X = candidates.to(device=paths.device, dtype=torch.float32)
+    if X.dim() == 1:
+        X = X.unsqueeze(-1)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] != paths.d:
+        raise ValueError("candidates must be [N, d] = [N >= 1, %d], got %s" % (paths.d, tuple(X.shape)))
+    k = max(1, min(int(num_starts), X.shape[0]))
+    vals = paths.values(X)                                              # [n, N]: the shared-point kernel
+    top = torch.topk(vals, k, dim=1, largest=bool(maximize))
+    starts = X[top.indices]                                             # [n, k, d]
+    res = paths.descend(starts, lower.to(paths.device), upper.to(paths.device), iterations=iterations, maximize=maximize)
+    best = res.values.argmax(dim=1) if maximize else res.values.argmin(dim=1)
+    rows = torch.arange(res.x.shape[0], device=paths.device)
+    return res.x[rows, best], res.values[rows, best], top.values[:, 0]
+
+
 def eval_values(test_dataset, model, likelihood, minibatch_size=1):
     """``eval_gp(...)`` followed by ``[::p+1]``: predictive means / variances (with likelihood noise) of the FUNCTION VALUES,
     what the reference's callers keep of it (tests/test_dsvgp.py:99-101, the experiments' MSE / NLL reports).  Same batching and

@@ -420,6 +420,15 @@ class ApproximateGP(torch.nn.Module):
             vs._maybe_init()
         return engine.sample_paths(self._param_dict(None), num_samples, num_features, generator, base_samples)
 
+    def thompson_step(self, candidates, lower, upper, num_samples, num_starts=8, iterations=20, num_features=2048, maximize=False,
+                      generator=None):
+        """``sample_paths(num_samples, num_features, generator)`` followed by ``directional_vi.thompson_candidates``: per draw the
+        best of ``num_starts`` candidates refined on that draw inside the box -> (x_next [n, d], f_next [n], f_candidates_best [n]).
+        Refuses where ``sample_paths`` refuses (CIQ whitening, float64 models)."""
+        from .directional_vi import thompson_candidates
+        paths = self.sample_paths(num_samples, num_features, generator)
+        return thompson_candidates(paths, candidates, lower, upper, num_starts, iterations, maximize)
+
     def posterior_mean(self, x, derivative_directions=None):
         """Predictive mean at x [B, d]: [B (pd + 1)] interleaved with pd = len(derivative_directions) // B rows per point
         (``None``: function values only); equals ``likelihood(self(x, derivative_directions=D)).mean`` without assembling

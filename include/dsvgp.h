@@ -796,6 +796,45 @@ size_t dsvgp_paths_hvp_workspace_bytes(int M, int d, int F, int n, int B);
 int dsvgp_paths_hvp(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, const float* x, const float* v, int B, float* hv,
                     void* workspace);
 
+/* ---- paths at their OWN points (csrc/paths.hip): sample s evaluated at x[s], and a device-resident projected-gradient descent of every
+ * (sample, start) pair on its own path -- the refinement of a Thompson candidate on its own sampled function.  dsvgp_paths_eval shares
+ * one point set among the n samples; after one step of a per-path refinement the n point sets differ.
+ *   dsvgp_paths_eval_own  `weights` as dsvgp_paths_prepare wrote them (unchanged); x[n, B, d] -> values[n, B] = f_s(x[s][b]), grads (NULL
+ *                         or [n, B, d]) = grad f_s (without the constant).  The host contract is dsvgp_paths_eval's: no host read, no
+ *                         synchronisation, no allocation, queued on the context's stream.  d <= 32: ONE fused kernel; a workgroup of 8
+ *                         waves owns 64 points of ONE sample (grid [ceil(B / 64), n], lane = point; x~, r, the d accumulators and the
+ *                         value in registers; inducing points, then features through LDS in chunks of 64; the waves' partial sums added
+ *                         in the order 0..7); the arithmetic of a (sample, point) is dsvgp_paths_eval's and its result depends on that
+ *                         sample and that point alone (not on B, n, the neighbours or the card); workspace may be NULL.  Any other d:
+ *                         the n B points as rows of one stacked problem on the unsplit fp32 MFMA GEMM through `workspace`
+ *                         (dsvgp_paths_own_workspace_bytes(M, d, F, n, B, want_grad) bytes, 16-byte aligned; 0 for d <= 32): X~ Z~^T,
+ *                         X~ Om^T, P Z~ and S Om stacked, X~_s G'_s^T and K_s G'_s one product per sample, pointwise kernels and
+ *                         fixed-order row sums between them: 10 + 2 n launches with gradients (the per-sample products are small at the
+ *                         B a refinement uses).  grads = NULL returns the same values bits.
+ *   dsvgp_paths_descend   x[n, B, d] (in: starts, out: iterates), lower[d], upper[d]; sigma = +1 to minimise, -1 with `maximize`.
+ *                         resume = 0: x <- clamp(x); (f, g) by dsvgp_paths_eval_own; eta = step0 / max(|g|, 1e-30) with
+ *                         step0 = initial_step, or 0.25 ell read from the weights on the device when initial_step <= 0; accepted = 0.
+ *                         resume = 1: x, values, grads, steps, accepted are the state a previous call left (no first evaluation).
+ *                         Then `iterations` times, per pair: y = clamp(x - sigma eta g); (f_y, g_y) by the own-point evaluation of all
+ *                         pairs; accept iff sigma f_y <= sigma f + 1e-4 sigma g.(y - x) (a NaN f_y rejects): x, f, g <- y, f_y, g_y,
+ *                         eta <- min(2 eta, 1e30), accepted += 1; else eta <- eta / 2.  One step kernel (one wave per pair, fixed-order
+ *                         wave sums) judges iteration t and proposes iteration t + 1: a call is a clamp, 1 + iterations evaluations
+ *                         (`iterations` when resuming) and 1 + iterations step launches, no host read.  sigma values never increases;
+ *                         iterates stay in the box; iterations = 0 gives the start state.  values[n, B], grads[n, B, d], steps[n, B],
+ *                         accepted[n, B] (int) are outputs (and inputs when resuming).  `workspace`:
+ *                         dsvgp_paths_descend_workspace_bytes(M, d, F, n, B) bytes, 16-byte aligned, never 0 for a shape the entry takes
+ *                         (the trial point, its value and gradient live there on both routes).
+ * No floating-point atomics.  DSVGP_EINVAL as for dsvgp_paths_eval (M, d, F, n or B < 1, a null required pointer, a misaligned `weights`
+ * or workspace, an intermediate that would pass 2^31 entries), for n > 65535, and in dsvgp_paths_descend for iterations < 0.  The size
+ * helpers are pure host functions (0 for arguments the entries refuse).                                                              */
+size_t dsvgp_paths_own_workspace_bytes(int M, int d, int F, int n, int B, int want_grad);
+int dsvgp_paths_eval_own(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, const float* x, int B, float* values,
+                         float* grads, void* workspace);
+size_t dsvgp_paths_descend_workspace_bytes(int M, int d, int F, int n, int B);
+int dsvgp_paths_descend(dsvgp_ctx* ctx, const float* weights, int M, int d, int F, int n, float* x, int B, const float* lower,
+                        const float* upper, int iterations, float initial_step, int maximize, int resume, float* values, float* grads,
+                        float* steps, int* accepted, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
