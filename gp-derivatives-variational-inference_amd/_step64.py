@@ -67,7 +67,7 @@ class ElboEngine64(ElboEngine):
 
     def _refuse_rect(self, params, x, D):
         """float64 models predict with the model's own number of directions per data point: the rectangular assembly
-        (csrc/assemble_rect.hip, ElboEngine.predict) is a float32 kernel"""
+        (csrc/assemble_wide.hip, ElboEngine.predict) is a float32 kernel"""
         p, pd = self._direction_counts(params, x, D, self.shared_directions)
         if pd != p:
             raise ValueError("float64 model mode predicts with the model's own number of directions per data point (%d), got %d: "

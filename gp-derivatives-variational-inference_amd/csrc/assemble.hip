@@ -3112,7 +3112,7 @@ extern "C" int dsvgp_kernel_fwd(dsvgp_ctx* ctx, const float* P1, const float* se
     if (n1 == 0 || n2 == 0) return 0;
     const int n1q = n1 * g.q, n2q = n2 * g.q;
     if (ld < n2q) return DSVGP_EINVAL;
-    if (geom_wide(g)) return launch_kernel_fwd_wide(ctx->stream, P1, self1, n1q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
+    if (geom_wide(g)) return launch_kernel_fwd_tiled(ctx->stream, P1, self1, n1q, g.q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
     if (g.q == 11 && g.K4 <= 12) {      // full-gradient SVGP at d <= 12 (BASELINE config 3): the split-row kernel
         const int T = 44;
         const int rt = cdiv(n1q, T), ctiles = cdiv(n2q, T);
@@ -3194,7 +3194,7 @@ extern "C" int dsvgp_kernel_fwd_wide(dsvgp_ctx* ctx, const float* P1, const floa
     if (n1 == 0 || n2 == 0) return 0;
     const int n1q = n1 * g.q, n2q = n2 * g.q;
     if (ld < n2q) return DSVGP_EINVAL;
-    return launch_kernel_fwd_wide(ctx->stream, P1, self1, n1q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
+    return launch_kernel_fwd_tiled(ctx->stream, P1, self1, n1q, g.q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
 }
 
 extern "C" size_t dsvgp_kernel_bwd_wide_workspace_bytes(int n1, int n2, int d, int p) {

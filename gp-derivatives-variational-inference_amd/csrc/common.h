@@ -134,20 +134,15 @@ int kernel_bwd_points_flush(dsvgp_ctx* ctx, const float* P1, const float* vnorm1
                             const float* rs, const float* rn, float* drl, float* drs, float* drn, float* dconst, float* loss);
 int launch_column_mean_hyp(hipStream_t st, const float* x, int n, int d, float* center, const float* rl, const float* rs,
                            const float* rn, float* hyp);                                       // assemble.hip
-// wide-input assembly (assemble_wide.hip; packed width > 96, any d through the dsvgp_kernel_*_wide entries): the forward into `out`, and
-// the backward's tile and contraction launches -- slab[ns][n1q][NP] and partials[nparts][2] inside `workspace` (kernel_bwd_wide_workspace
-// bytes), for kernel_bwd_points_kernel's contract (assemble.hip)
-int launch_kernel_fwd_wide(hipStream_t st, const float* P1, const float* self1, int n1q, const float* P2, const float* self2, int n2q,
-                           int q, int K4, int DP, const float* hyp, float jitter, void* out, int64_t ld, int out_is_double);
+// K-looped tiled assembly (assemble_wide.hip): the forward into `out` with a row period q1 and a column period q2 (packed width > 96 and
+// the dsvgp_kernel_fwd_wide entry pass the same q twice), and the wide-input backward's tile and contraction launches -- slab[ns][n1q][NP]
+// and partials[nparts][2] inside `workspace` (kernel_bwd_wide_workspace bytes), for kernel_bwd_points_kernel's contract (assemble.hip)
+int launch_kernel_fwd_tiled(hipStream_t st, const float* P1, const float* self1, int n1q, int q1, const float* P2, const float* self2,
+                            int n2q, int q2, int K4, int DP, const float* hyp, float jitter, void* out, int64_t ld, int out_is_double);
 size_t kernel_bwd_wide_workspace(int n1q, int n2q, int q, int NP);
 int launch_kernel_bwd_wide(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1q,
                            const float* P2, const float* self2, int n2q, int q, int K4, int DP, int NP, const float* hyp, void* workspace,
                            float** slab, int* ns, float** partials, int* nparts);
-// the contraction launch alone, for a Tbar[n1q, n2q] made elsewhere (assemble_rect.hip: its two sides have different micro-block periods,
-// which the contraction never sees): slab[*ns][n1q][NP], kernel_bwd_wide_slab_floats floats (a multiple of 64)
-size_t kernel_bwd_wide_slab_floats(int n1q, int n2q, int NP);
-int launch_kernel_bwd_wide_contract(hipStream_t st, const float* TB, int n1q, int n2q, const float* P2, int DP, int NP, float* slab,
-                                    int* ns);
 // the points launch of the kernel backwards (assemble.hip: finish_points) for side 1's geometry (d, p): d_x1 / d_v1 / d_hyp[0..1] +=
 int kernel_bwd_finish_points(dsvgp_ctx* ctx, int d, int p, const float* slab, int ns, const float* P1, const float* vnorm1, int n1,
                              const float* hyp, float sym, float* d_x1, float* d_v1, const float* partials, int nparts, float* d_hyp);

@@ -18,7 +18,7 @@
 #define PRED_BLOCKS_FN inline
 #endif
 
-constexpr int PB_TMAX = 96;         // strip columns at most (the tile rule of assemble_rect.hip)
+constexpr int PB_TMAX = 96;         // strip columns at most (the tile rule of assemble_wide.hip)
 constexpr int PB_KC = 32;           // rows per staged chunk
 constexpr int PB_MAXPAIRS = 6;      // live tile pairs per wave at most: ceil(21 / 4)
 constexpr int PB_NT = 256;          // threads per workgroup (4 waves)

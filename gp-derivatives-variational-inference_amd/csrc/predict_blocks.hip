@@ -5,7 +5,7 @@
 // predict_joint pays B q x B q floats for.
 //
 // Launch 1 (pred_blocks_gram_kernel), one workgroup (256 threads) per (group, slice) of pred_blocks_plan.h: a group is a strip of
-// G = max(1, 96 / q) whole points (Tc = G q <= 96 columns, the tile rule of assemble_rect.hip), a slice `rps` of the Mp rows.  The
+// G = max(1, 96 / q) whole points (Tc = G q <= 96 columns, the tile rule of assemble_wide.hip), a slice `rps` of the Mp rows.  The
 // workgroup walks its rows in chunks of 32: [32][Tc] of W and of A go through registers (coalesced along the columns; the next chunk
 // is in flight while the current one is multiplied) into two LDS images of row stride ld = 16 mod 32, and the strip's Gram
 // accumulates on v_mfma_f32_16x16x4_f32.  For C += X^T X both operands of a tile pair are fragments of the same [k][column] image: the

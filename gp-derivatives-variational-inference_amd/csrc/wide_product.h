@@ -1,4 +1,4 @@
-// The K-looped operand product of the wide-input assembly kernels (assemble_wide.hip, assemble_rect.hip): T = P1 P2^T per
+// The K-looped operand product of the wide-input assembly kernels (assemble_wide.hip): T = P1 P2^T per
 // workgroup tile on v_mfma_f32_16x16x4_f32, over fixed 32-column chunks staged through LDS.
 #pragma once
 #include "common.h"

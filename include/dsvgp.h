@@ -132,7 +132,7 @@ int dsvgp_kernel_bwd_wide(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_d
                           const float* self1, const float* vnorm1, int n1, const float* P2,
                           const float* self2, int n2, int d, int p, const float* hyp, int symmetric,
                           float* d_x1, float* d_v1, float* d_hyp, void* workspace);
-/* Rectangular assembly (csrc/assemble_rect.hip): the two sides carry DIFFERENT numbers of directions.
+/* Rectangular assembly (csrc/assemble_wide.hip): the two sides carry DIFFERENT numbers of directions.
  *   out[n1*(p1+1), n2*(p2+1)] (float, leading dimension ld >= n2*(p2+1)) = hyp.outputscale * K(x1, x2; v1, v2), interleaved as
  *   dsvgp_kernel_fwd: micro-block (i, j) is k [[1, w_b/ell], [-u_a/ell, (G_ab - u_a w_b)/ell^2]] for a = 1..p1, b = 1..p2, with
  *   r = (x1_i - x2_j)/ell, k = exp(-|r|^2/2), u_a = r.v1_ia, w_b = r.v2_jb, G_ab = v1_ia.v2_jb (unit directions).

@@ -1,4 +1,4 @@
-"""CPU: the surface of the rectangular kernel assembly (``dsvgp_kernel_fwd_rect``, csrc/assemble_rect.hip) and of what is built on it
+"""CPU: the surface of the rectangular kernel assembly (``dsvgp_kernel_fwd_rect``, csrc/assemble_wide.hip) and of what is built on it
 -- the export, its declaration and binding, ``ApproximateGP.posterior``, ``eval_values`` and the float64 engine's refusal.  Nothing here
 touches a GPU."""
 import inspect

@@ -1,4 +1,4 @@
-"""CPU: the surface of the rectangular kernel backward (``dsvgp_kernel_bwd_rect``, csrc/assemble_rect.hip) and of the training step
+"""CPU: the surface of the rectangular kernel backward (``dsvgp_kernel_bwd_rect``, csrc/assemble_wide.hip) and of the training step
 built on it -- the exports, their declarations and bindings, the workspace arithmetic, the engines' refusals (raised on the shapes
 alone, before any device work), the harness signatures and the model attribute.  Nothing here touches a GPU."""
 import inspect

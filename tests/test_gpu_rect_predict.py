@@ -1,5 +1,5 @@
 """Predictions with any number of data directions: the rectangular kernel assembly (``dsvgp_kernel_fwd_rect``,
-csrc/assemble_rect.hip) and ``ElboEngine.predict`` / ``predict_joint`` / ``ApproximateGP.posterior`` / ``eval_values`` on top of it.
+csrc/assemble_wide.hip) and ``ElboEngine.predict`` / ``predict_joint`` / ``ApproximateGP.posterior`` / ``eval_values`` on top of it.
 
 The yardstick is built here in float64 from the oracle (``rect_kernel``, ``rect_predictive``); the CPU test pins it to
 ``O.predictive`` / ``O.predictive_joint`` where those are defined (pd = 0 through the derivative-free variant, pd = p).  The GPU

@@ -1,4 +1,4 @@
-"""Training with any number of data directions: the rectangular kernel backward (``dsvgp_kernel_bwd_rect``, csrc/assemble_rect.hip),
+"""Training with any number of data directions: the rectangular kernel backward (``dsvgp_kernel_bwd_rect``, csrc/assemble_wide.hip),
 ``ElboEngine.loss_and_grads`` with pd != p on top of it, and the ``data_directions`` keyword of the model / harness.
 
 The yardstick is built here in float64: ``rect_kernel`` of tests/test_gpu_rect_predict.py (differentiable torch), the oracle's Cholesky
@@ -218,7 +218,8 @@ def test_kernel_bwd_rect_accumulates_takes_a_strided_upstream_and_is_reproducibl
 @gpu
 @pytest.mark.parametrize("n1,p,n2,d", [(20, 5, 45, 20), (11, 2, 23, 200)])
 def test_kernel_bwd_rect_at_equal_counts_is_kernel_bwd_wide(dsvgp, gpu_device, n1, p, n2, d):
-    """p1 == p2 > 0: the column-tile cap does not bite, tiles and arithmetic are kernel_bwd_wide_tbar_kernel's -- bitwise equal"""
+    """p1 == p2 > 0: the column-tile cap does not bite, so the two entries plan the same tiles for the one kernel_bwd_tbar_kernel --
+    bitwise equal"""
     dev = gpu_device
     x1, v1, x2, v2, ell, s, G, _ = _op_case(n1, p, n2, p, d)
     ops, ctx, hyp, pk1, pk2 = _op_packs(dsvgp, dev, x1, v1, p, x2, v2, p, ell, s)
@@ -228,6 +229,21 @@ def test_kernel_bwd_rect_at_equal_counts_is_kernel_bwd_wide(dsvgp, gpu_device, n
         ops.kernel_bwd_wide(ctx, Gd, pk1, n1, pk2, n2, d, p, hyp, False, *wide)
         _report("equal counts d=%d p=%d %dx%d" % (d, p, n1, n2), {k: relmax(u, v) for k, u, v in zip(("d_x1", "d_v1", "d_hyp"), rect, wide)})
         assert all(torch.equal(u, v) for u, v in zip(rect, wide))
+
+
+@gpu
+@pytest.mark.parametrize("n1,p,n2,d", [(20, 5, 45, 20), (11, 2, 23, 200), (9, 0, 30, 200)])
+def test_kernel_fwd_rect_at_equal_counts_is_kernel_fwd_wide(dsvgp, gpu_device, n1, p, n2, d):
+    """p1 == p2 (the forward has no column cap, so p = 0 too): the same tiles of the one kernel_fwd_tiled_kernel, ragged on both sides, one K
+    chunk and several with a ragged last one, 1 x 1 micro-blocks -- equal values (not told apart: a -0 that meets the wide entry's
+    zero jitter on the global diagonal)"""
+    dev = gpu_device
+    x1, v1, x2, v2, ell, s, _, _ = _op_case(n1, p, n2, p, d)
+    ops, ctx, hyp, pk1, pk2 = _op_packs(dsvgp, dev, x1, v1, p, x2, v2, p, ell, s)
+    rect = ops.kernel_fwd_rect(ctx, pk1, n1, p, pk2, n2, p, d, hyp)
+    wide = ops.kernel_fwd_wide(ctx, pk1, n1, pk2, n2, d, p, hyp, jitter=0.0, dtype=torch.float32)
+    assert rect.shape == wide.shape == (n1 * (p + 1), n2 * (p + 1)) and rect.abs().max().item() > 0
+    assert torch.equal(rect, wide)
 
 
 # ------------------------------------------------------------------ GPU 2: the step against the yardstick

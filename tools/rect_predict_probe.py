@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Predictions of the function values only (pd = 0, K_ZX from csrc/assemble_rect.hip) against predictions with the model's own
+"""Predictions of the function values only (pd = 0, K_ZX from csrc/assemble_wide.hip) against predictions with the model's own
 direction count (pd = p), ALTERNATING in one process on the same model (one engine per path), on a hit of the evaluation cache:
 
     full     ElboEngine.predict(params, x, D_p, cache=True)     B (p + 1) columns: assembly, fp64 solve, W = L_S^T A, statistics

@@ -2,7 +2,7 @@
 """Training on function values only (pd = 0) two ways, ALTERNATING in one process on the same parameters and batch:
 
   kernel backward of K_ZX-bar [M', B]
-    rect     _ops.kernel_bwd_rect on the [M', B] upstream as it is                                  (csrc/assemble_rect.hip)
+    rect     _ops.kernel_bwd_rect on the [M', B] upstream as it is                                  (csrc/assemble_wide.hip)
     full     the upstream scattered into a zero-filled [M', B (p + 1)] matrix, then _ops.kernel_bwd  (what _kernel_bwd_zx does for the
              derivative-free engine)
   kernel forward of K_ZX [M', B]
