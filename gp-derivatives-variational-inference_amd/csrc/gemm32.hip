@@ -15,6 +15,7 @@
 // Staging stores: 8-byte stores for the k-contiguous image (rows are 8-byte aligned), 16-byte for the other.
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "gram_walk.h"
@@ -338,6 +339,8 @@ __device__ __forceinline__ void lds_dma16(const float* gsrc, unsigned lds_byte_a
 // the two workgroups of a CU alternate MFMA and DMA-issue phases in lockstep, a shorter MFMA phase of one does not shorten the
 // period of the pair); diagonal tiles: Gram 2.077 -> 2.124 ms at C4 and 0.633 -> 0.774 ms at C3 (slower); the mere presence of
 // the extra loop copies costs 1-2 % (2.077 -> 2.114 with the patterns switched off at run time).
+// This does not carry over to gemm32_gram_kernel below, which runs ONE workgroup per CU and one wave per SIMD: there a stage takes as long as
+// its MFMAs, the same dealing pays (C4 Gram alone 1.82 -> 1.66 ms) and the extra loop copies cost nothing (profiles/gram_live_ab.txt).
 // MF = 32: 2 x 2 tiles of v_mfma_f32_32x32x2_f32 per wave;  MF = 16: 4 x 4 tiles of v_mfma_f32_16x16x4_f32 (same 64 x 64 wave tile,
 // same LDS images and DMA; twice the fragment reads per flop, but the smaller shape holds a higher clock under load).
 // Lane l = TS h + r (TS = 32 / 16 rows per tile, h = k slot 0..1 / 0..3) reads chunk (64 / MF) j + h of its row per read.
@@ -688,11 +691,25 @@ __global__ __launch_bounds__(256, 1) void gemm32_wide_kernel(const G32 g) {
 // its share leaves a tile and at its end.  A share may start and end mid-tile and, when K is short, span several tiles.
 // Epilogue: 256 atomic instructions per wave, each 2 x 128 contiguous bytes; at most 32 of a wave are in flight (a counted vmcnt
 // after every MFMA tile's 16), which is where the issue of float atomics stalls anyway.
+// Patterns (gram_walk.h; DSVGP_G32_GRAM_LIVE=0 at a launch turns them off): the above is the stage of a FULL tile.  A diagonal tile has 36
+// live MFMA tiles of 64 and a ragged last tile row fewer live MFMA rows than 8, and a wave that issues MFMAs for dead tiles sets the pace
+// of the stage for nothing.  DIAG deals the 36 tiles 9 per wave, ROWS3 (5 or 6 live MFMA rows) 12 per wave; every live MFMA tile keeps ONE
+// owner over a unit's whole stage range, so an output still receives one partial sum per unit.  A pattern's stage is the same layout with
+// fewer MFMAs (144 / 192 for 256) and only the fragments its tiles need; DIAG's four lists differ, so each wave runs its own copy of the
+// stage loop -- all waves still meet at one vmcnt(0) and one barrier per stage.  The walk deals equal COST (16 / 12 / 9 per stage), not
+// equal stage counts.  C4: 1120 x 768 MFMA tiles per wave instead of 1248 x 768 (-10.3 %); no scratch (profiles/gram_live_resource_usage.txt).
 // -------------------------------------------------------------------------------------------------
 constexpr int GT = 256, GBK = 32;
 constexpr int G_OPWORDS = GT * GBK, G_STAGE = 2 * G_OPWORDS;                                   // 2 x 8192 words = 64 KB
 constexpr int G_NP = G_OPWORDS / 1024;                                                         // 1 KB pieces per operand, wave and stage: 8
 constexpr int G_LDS_BYTES = 2 * G_STAGE * 4;
+
+template <int PAT, int WV>
+struct GramPat { static constexpr GramPatWave v = gram_pattern(PAT, WV); };     // the table of gram_walk.h, used in constant expressions only
+template <class F, int... I>
+__device__ __forceinline__ void g32_static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F>
+__device__ __forceinline__ void g32_static_for(F&& f) { g32_static_for_impl(f, std::make_integer_sequence<int, N>{}); }
 
 struct G32Gram {
     const float* A; const float* B; float* C;
@@ -722,6 +739,7 @@ __global__ __launch_bounds__(256, 1) void gemm32_gram_kernel(const G32Gram g) {
         aoff[j] = (wr * 128 + r) * GBK + 4 * ((2 * j) ^ q7);
         boff[j] = (wc * 128 + r) * GBK + 4 * ((2 * j) ^ q7);
     }
+    const int frag0 = r * GBK;                             // (the patterns add their own MFMA rows: aoff[j] = frag0 + wr * 128 * GBK + 4 ((2 j) ^ q7))
     // DMA: piece i of wave w is the 1 KB block 8 w + i of either image -- rows 8 (8 w + i) .. + 7, lane -> (row, swizzled chunk)
     int drow[G_NP], dkk[G_NP];
 #pragma unroll
@@ -741,13 +759,15 @@ __global__ __launch_bounds__(256, 1) void gemm32_gram_kernel(const G32Gram g) {
             asrc[i] = g.A + (int64_t)min(m0 + drow[i], g.M - 1) * g.lda + kbeg + dkk[i];
             bsrc[i] = g.B + (int64_t)min(n0 + drow[i], g.N - 1) * g.ldb + kbeg + dkk[i];
         }
-        acc16 acc[4][4];
+        acc16 acc[4][4];                                   // (zeroed below, where the unit's pattern is known: NT sets)
+        auto zero_acc = [&](int nt) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i)
+            for (int t = 0; t < 16; ++t)
+                if (t < nt) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int c = 0; c < 16; ++c) acc[i][j][c] = 0.f;
+                    for (int c = 0; c < 16; ++c) acc[t / 4][t % 4][c] = 0.f;
+                }
+        };
 
         // one stage: the MFMAs on buffer buf with, between them, the DMA of the stage at knext into the other buffer.
         // MODE 0: no DMA (the last stage of the unit); 1: a whole stage; 2: the stage that may cross K (chunks past it come from the zero chunk)
@@ -810,6 +830,79 @@ __global__ __launch_bounds__(256, 1) void gemm32_gram_kernel(const G32Gram g) {
             }
         };
 
+        // the same stage for a pattern of gram_walk.h: wave WV's NT tiles (accumulator set t = tile t of its list), fragments of its
+        // NR MFMA rows and NC MFMA columns only, the same 16 DMA instructions in the same k-groups, one other item after every second
+        // MFMA.  rbase / cbase: words of the wave's first MFMA row / column (row0, col0 of the table) inside an image
+        auto live_body = [&](auto pat_, auto wv_, auto mode_, int buf, int knext, int rbase, int cbase) {
+            constexpr int MODE = decltype(mode_)::value;
+            using P = GramPat<decltype(pat_)::value, decltype(wv_)::value>;
+            constexpr int NR = P::v.nr, NC = P::v.nc, NT = P::v.nt;
+            static_assert(6 + NR + NC <= 2 * NT, "a k-group's slots hold its DMA instructions and the next k-group's fragment reads");
+            const float* As = glds + buf * G_STAGE + rbase + frag0;
+            const float* Bs = glds + buf * G_STAGE + G_OPWORDS + cbase + frag0;
+            const unsigned dst = lds_base + (unsigned)(buf ^ 1) * (G_STAGE * 4);
+            float fa[2][NR][4], fb[2][NC][4];
+            auto rd = [&](auto j_, auto q_) {                 // fragment read q of k-group j: rows first, then columns
+                constexpr int j = decltype(j_)::value, q = decltype(q_)::value;
+                if constexpr (q < NR) {
+                    constexpr int ro = P::v.rows[q] * 32 * GBK;
+                    const float4 v = *reinterpret_cast<const float4*>(As + ro + 4 * ((2 * j) ^ q7));
+                    fa[j & 1][q][0] = v.x; fa[j & 1][q][1] = v.y; fa[j & 1][q][2] = v.z; fa[j & 1][q][3] = v.w;
+                } else if constexpr (q < NR + NC) {
+                    constexpr int co = P::v.cols[q - NR] * 32 * GBK;
+                    const float4 v = *reinterpret_cast<const float4*>(Bs + co + 4 * ((2 * j) ^ q7));
+                    fb[j & 1][q - NR][0] = v.x; fb[j & 1][q - NR][1] = v.y; fb[j & 1][q - NR][2] = v.z; fb[j & 1][q - NR][3] = v.w;
+                }
+            };
+            auto dma1 = [&](int d) {                          // as in the stage above
+                if (d < G_NP) {
+                    const float* s = asrc[d];
+                    if (MODE == 2) s = (knext + dkk[d] >= K4) ? g32_zero_chunk : s;
+                    lds_dma16(s, dst + (wave_u * G_NP + d) * 1024);
+                    asrc[d] += GBK;
+                } else {
+                    const int i = d - G_NP;
+                    const float* s = bsrc[i];
+                    if (MODE == 2) s = (knext + dkk[i] >= K4) ? g32_zero_chunk : s;
+                    lds_dma16(s, dst + G_OPWORDS * 4 + (wave_u * G_NP + i) * 1024);
+                    bsrc[i] += GBK;
+                }
+            };
+            g32_static_for<NR + NC>([&](auto q_) { rd(std::integral_constant<int, 0>{}, q_); });
+            g32_static_for<4>([&](auto j_) {
+                constexpr int j = decltype(j_)::value;
+                constexpr int nd = MODE == 0 ? 0 : (j == 0 ? 6 : (j < 3 ? 5 : 0)), d0 = j == 0 ? 0 : (j == 1 ? 6 : 11);
+                g32_static_for<4 * NT>([&](auto n_) {
+                    constexpr int n = decltype(n_)::value, e = n / NT, t = n % NT, ia = P::v.tr[t], ib = P::v.tc[t];
+                    acc[t / 4][t % 4] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[j & 1][ia][e], fb[j & 1][ib][e], acc[t / 4][t % 4], 0, 0, 0);
+                    if constexpr (n & 1) {
+                        constexpr int sl = n >> 1;
+                        __builtin_amdgcn_sched_barrier(0);
+                        if constexpr (sl < nd) dma1(d0 + sl);
+                        else if constexpr (j < 3) rd(std::integral_constant<int, j + 1>{}, std::integral_constant<int, sl - nd>{});
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                });
+            });
+        };
+        // a pattern's partial sums into C: the wave's own tiles, the predicates and the in-flight count of the FULL epilogue below
+        auto live_store = [&](auto pat_, auto wv_, int mrow0, int ncol0) {
+            using P = GramPat<decltype(pat_)::value, decltype(wv_)::value>;
+            g32_static_for<P::v.nt>([&](auto t_) {
+                constexpr int t = decltype(t_)::value, ro = P::v.rows[P::v.tr[t]] * 32, co = P::v.cols[P::v.tc[t]] * 32;
+                const int mt = m0 + mrow0 + ro, nt = n0 + ncol0 + co;
+                if (mt >= g.M || nt >= g.N || nt > mt + 31) return;
+                const int n = nt + r;
+                float* dst = g.C + (int64_t)(mt + 4 * h) * g.ldc + n;
+#pragma unroll
+                for (int c = 0; c < 16; ++c) {
+                    const int mo = (c & 3) + 8 * (c >> 2), m = mt + 4 * h + mo;
+                    if (m < g.M && n < g.N && n <= m) atomicAdd(dst + (int64_t)mo * g.ldc, g.alpha * acc[t / 4][t % 4][c]);
+                }
+                if (G32_GRAM_INFLIGHT < 63) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G32_GRAM_INFLIGHT) : "memory");
+            });
+        };
+
         __syncthreads();                                   // every wave has left the buffers of the previous unit
         {   // stage 0 of the unit (tail-checked: it may be the last stage of K)
 #pragma unroll
@@ -824,6 +917,39 @@ __global__ __launch_bounds__(256, 1) void gemm32_gram_kernel(const G32Gram g) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                   // stage 0 has landed for every wave
         int buf = 0, k0 = kbeg + GBK;                      // k0: the stage whose DMA the next call issues
+        // The pattern is wave-uniform per unit.  DIAG's four lists differ, so each wave runs the unit in its own copy of the stage loop
+        // (a scalar branch per unit, none inside a stage); every copy has the same vmcnt(0) and barrier after every stage but the last
+        auto run_unit = [&](auto pat_, auto wv_, int row0, int col0) {      // row0 / col0: the wave's first MFMA row / column
+            zero_acc(GramPat<decltype(pat_)::value, decltype(wv_)::value>::v.nt);
+            const int rbase = row0 * 32 * GBK, cbase = col0 * 32 * GBK;
+            auto st = [&](auto mode_, int b, int kn) {
+                live_body(pat_, wv_, mode_, b, kn, rbase, cbase);
+                if (decltype(mode_)::value != 0) {
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    __syncthreads();
+                }
+            };
+            for (int s = 0; s + 2 < nst; ++s, buf ^= 1, k0 += GBK) st(std::integral_constant<int, 1>{}, buf, k0);
+            if (nst >= 2) { st(std::integral_constant<int, 2>{}, buf, k0); buf ^= 1; }
+            st(std::integral_constant<int, 0>{}, buf, 0);
+            live_store(pat_, wv_, row0 * 32, col0 * 32);
+        };
+        const int pat = gram_walk_pattern(g.walk, u.tm, u.tn);
+        if (pat != GRAM_PAT_FULL) {
+            using std::integral_constant;
+            if (pat == GRAM_PAT_ROWS3) {
+                run_unit(integral_constant<int, GRAM_PAT_ROWS3>{}, integral_constant<int, 0>{}, gram_pat_row0(GRAM_PAT_ROWS3, wave_u), gram_pat_col0(GRAM_PAT_ROWS3, wave_u));
+            } else {
+                switch (wave_u) {
+                    case 0: run_unit(integral_constant<int, GRAM_PAT_DIAG>{}, integral_constant<int, 0>{}, 0, 0); break;
+                    case 1: run_unit(integral_constant<int, GRAM_PAT_DIAG>{}, integral_constant<int, 1>{}, 0, 0); break;
+                    case 2: run_unit(integral_constant<int, GRAM_PAT_DIAG>{}, integral_constant<int, 2>{}, 0, 0); break;
+                    default: run_unit(integral_constant<int, GRAM_PAT_DIAG>{}, integral_constant<int, 3>{}, 0, 0); break;
+                }
+            }
+            continue;
+        }
+        zero_acc(16);
         for (int s = 0; s + 2 < nst; ++s, buf ^= 1, k0 += GBK) stage(std::integral_constant<int, 1>{}, buf, k0);
         if (nst >= 2) { stage(std::integral_constant<int, 2>{}, buf, k0); buf ^= 1; }
         stage(std::integral_constant<int, 0>{}, buf, 0);
@@ -964,8 +1090,11 @@ int launch_gemm32(hipStream_t st, const GemmArgs& g) {
         }
         const char* cenv = getenv("DSVGP_G32_GRAM_KCHUNKS");
         const int kchunks = cenv ? atoi(cenv) : G32_GRAM_KCHUNKS;
+        // DSVGP_G32_GRAM_LIVE=0: every tile runs FULL and the workgroups get equal stage counts (the kernel before the patterns)
+        const char* lenv = getenv("DSVGP_G32_GRAM_LIVE");
+        const int live = lenv ? (atoi(lenv) != 0) : 1;
         G32Gram w{};
-        w.walk = gram_walk_make(g.M, g.N, g.K, GT, GBK, kchunks);
+        w.walk = gram_walk_make(g.M, g.N, g.K, GT, GBK, kchunks, live);
         if (gmode != 3 || w.walk.G >= (long long)G32_GRAM_STAGES * ncu) {
             w.A = a.A; w.B = a.B; w.C = a.C; w.lda = g.lda; w.ldb = g.ldb; w.ldc = g.ldc;
             w.M = g.M; w.N = g.N; w.K = g.K; w.nwg = ncu; w.alpha = a.alpha;
