@@ -131,6 +131,14 @@ SIGNATURES = {
     "dsvgp_kernel_fwd_rect": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _l]),
     "dsvgp_kernel_bwd_rect_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "dsvgp_kernel_bwd_rect": (_i, [_p, _p, _l, _i, _p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "dsvgp_hyp_forward_ard": (_i, [_p, _p, _i, _p, _p, _p, _p]),
+    "dsvgp_hyp_backward_ard": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "dsvgp_pack_points_ard": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "dsvgp_kernel_diag_ard": (_i, [_p, _p, _i, _i, _i, _p, _p]),
+    "dsvgp_kernel_diag_ard_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "dsvgp_kernel_bwd_ard_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dsvgp_kernel_bwd_ard_slabs": (_i, [_i, _i, _i, _i, _i]),
+    "dsvgp_kernel_bwd_ard": (_i, [_p, _p, _l, _i, _p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p]),
     "dsvgp_kernel_canon_supported": (_i, [_i, _i]),
     "dsvgp_kernel_canon2_supported": (_i, [_i, _i]),
     "dsvgp_kernel_fwd_canon2": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i, _p, _f, _p, _l, _i]),

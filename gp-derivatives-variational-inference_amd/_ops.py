@@ -608,6 +608,130 @@ def kernel_bwd_rect(ctx, G, pack1, n1, p1, pack2, n2, p2, d, hyp, d_x1, d_v1, d_
     return workspace
 
 
+def _req_ell(ell, d):
+    _req(ell, f32, "ell", 1)
+    if ell.shape != (d,):
+        raise ValueError("ell must have shape [%d], got %s" % (d, tuple(ell.shape)))
+    return ell
+
+
+def hyp_forward_ard(ctx, raw_l, raw_s, raw_n):
+    """-> (ell[d], hyp[4]): the softplus-constrained lengthscale vector, and ``hyp_forward``'s hyp with hyp[0] = 1 (the ARD packs carry
+    the lengthscales; csrc/assemble_ard.hip)"""
+    rl = _req(raw_l.reshape(-1), f32, "raw_lengthscale")
+    d = rl.numel()
+    ell = torch.empty(d, dtype=f32, device=rl.device)
+    hyp = torch.empty(4, dtype=f32, device=rl.device)
+    check(lib.dsvgp_hyp_forward_ard(ctx.h, _ptr(rl), d, _ptr(_req(raw_s.reshape(-1), f32, "raw_outputscale")),
+                                    _ptr(_req(raw_n.reshape(-1), f32, "raw_noise")), _ptr(ell), _ptr(hyp)), "dsvgp_hyp_forward_ard")
+    return ell, hyp
+
+
+def hyp_backward_ard(ctx, raw_l, raw_s, raw_n, d_ell, d_hyp, d_raw_l, d_raw_s, d_raw_n):
+    """d_raw_l[k] += d_ell[k] sigmoid(raw_l[k]); d_raw_s / d_raw_n += as ``hyp_backward`` (d_hyp[0] is not read)"""
+    d = raw_l.numel()
+    for t, name in ((raw_l, "raw_lengthscale"), (d_raw_l, "d_raw_lengthscale"), (d_ell, "d_ell")):
+        if not t.is_contiguous() or t.numel() != d or t.dtype != f32:
+            raise ValueError("%s must be %d contiguous float32 values" % (name, d))
+    check(lib.dsvgp_hyp_backward_ard(ctx.h, _ptr(raw_l), d, _ptr(raw_s), _ptr(raw_n), _ptr(d_ell), _ptr(d_hyp), _ptr(d_raw_l),
+                                     _ptr(d_raw_s), _ptr(d_raw_n)), "dsvgp_hyp_backward_ard")
+
+
+def pack_points_ard(ctx, x, v, p, ell, center=None):
+    """``pack_points`` with a lengthscale per dimension, ell[d]: rows (x - c) / ell and (v / |v|) / ell -> (P, self, vnorm)"""
+    _req(x, f32, "x", 2)
+    n, d = x.shape
+    _req_ell(ell, d)
+    if center is not None:
+        _req(center, f32, "center", 1)
+        if center.shape != (d,):
+            raise ValueError("center must have shape [%d]" % d)
+    if p > 0:
+        _req(v, f32, "v", 2)
+        if v.shape != (n * p, d):
+            raise ValueError("directions must be [n*p, d] = [%d, %d], got %s" % (n * p, d, tuple(v.shape)))
+    if not x.is_contiguous() or (p > 0 and not v.is_contiguous()):
+        raise ValueError("x and v must be contiguous")
+    DP = packed_width(d)
+    P = torch.empty(n * (p + 1), DP, dtype=f32, device=x.device)
+    sf = torch.empty(n * (p + 1), dtype=f32, device=x.device)
+    vn = torch.empty(max(n * p, 1), dtype=f32, device=x.device)
+    check(lib.dsvgp_pack_points_ard(ctx.h, _ptr(x), _ptr(v if p > 0 else None), n, d, p, _ptr(ell), _ptr(center), _ptr(P), _ptr(sf),
+                                    _ptr(vn)), "dsvgp_pack_points_ard")
+    return P, sf, vn
+
+
+def _req_pack(pack, n, p, d, name):
+    P, sf = pack[0], pack[1]
+    _req(P, f32, name, 2)
+    _req(sf, f32, name + " self terms", 1)
+    if P.shape != (n * (p + 1), packed_width(d)) or sf.shape[0] != n * (p + 1) or not P.is_contiguous():
+        raise ValueError("%s is not the contiguous pack of %d points with %d directions at d = %d" % (name, n, p, d))
+    return P, sf
+
+
+def kernel_diag_ard(ctx, pack, n, p, d, hyp):
+    """out[n (p + 1)] = s [1, |v~_1|^2, ..., |v~_p|^2] per point: the prior diagonal of the ARD kernel from a ``pack_points_ard`` pack"""
+    P, _ = _req_pack(pack, n, p, d, "pack")
+    out = torch.empty(n * (p + 1), dtype=f32, device=P.device)
+    check(lib.dsvgp_kernel_diag_ard(ctx.h, _ptr(P), n, p, d, _ptr(hyp), _ptr(out)), "dsvgp_kernel_diag_ard")
+    return out
+
+
+def kernel_diag_ard_bwd(ctx, pack, n, p, d, ell, hyp, out, gbar, d_ell, d_hyp):
+    """backward of ``kernel_diag_ard`` given gbar[n (p + 1)] and the forward's ``out``: accumulates (+=) into d_ell[d] and d_hyp[1]"""
+    P, _ = _req_pack(pack, n, p, d, "pack")
+    _req_ell(ell, d)
+    _req_ell(d_ell, d)
+    for t, name in ((out, "out"), (gbar, "gbar")):
+        _req(t, f32, name, 1)
+        if t.shape[0] != n * (p + 1):
+            raise ValueError("%s must have %d entries" % (name, n * (p + 1)))
+    check(lib.dsvgp_kernel_diag_ard_bwd(ctx.h, _ptr(P), n, p, d, _ptr(ell), _ptr(hyp), _ptr(out), _ptr(gbar), _ptr(d_ell), _ptr(d_hyp)),
+          "dsvgp_kernel_diag_ard_bwd")
+
+
+def kernel_bwd_ard_workspace_bytes(n1, p1, n2, p2, d):
+    """bytes of the workspace of ``kernel_bwd_ard`` (pure host arithmetic); 0 for a shape it does not take"""
+    return int(lib.dsvgp_kernel_bwd_ard_workspace_bytes(int(n1), int(p1), int(n2), int(p2), int(d)))
+
+
+def kernel_bwd_ard_slabs(n1, p1, n2, p2, d):
+    """how many split slabs the contraction of ``kernel_bwd_ard`` writes for these shapes (pure host arithmetic); 0: refused"""
+    return int(lib.dsvgp_kernel_bwd_ard_slabs(int(n1), int(p1), int(n2), int(p2), int(d)))
+
+
+def kernel_bwd_ard(ctx, G, pack1, n1, p1, pack2, n2, p2, d, ell, hyp, symmetric, d_x1, d_v1, d_ell, d_hyp, workspace=None):
+    """backward of the ARD kernel (``pack_points_ard`` packs, ``hyp_forward_ard``'s hyp) with respect to side 1 (x1, v1), the
+    lengthscale vector (through both sides) and the outputscale, given G = dLoss/dOut [n1 (p1 + 1), n2 (p2 + 1)] (float32 or float64,
+    unit inner stride); accumulates (+=) into d_x1, d_v1, d_ell and d_hyp[1].  d_ell and d_v1 may be None (csrc/assemble_ard.hip)"""
+    P1, s1 = _req_pack(pack1, n1, p1, d, "pack1")
+    P2, s2 = _req_pack(pack2, n2, p2, d, "pack2")
+    vn1 = pack1[2] if len(pack1) > 2 else None
+    isd = G.dtype == f64
+    _req(G, f64 if isd else f32, "G", 2)
+    if G.shape != (n1 * (p1 + 1), n2 * (p2 + 1)):
+        raise ValueError("G has shape %s, expected %s" % (tuple(G.shape), (n1 * (p1 + 1), n2 * (p2 + 1))))
+    _req_ell(ell, d)
+    if d_ell is not None:
+        _req_ell(d_ell, d)
+    _req(d_x1, f32, "d_x1", 2)
+    if d_x1.shape != (n1, d) or not d_x1.is_contiguous():
+        raise ValueError("d_x1 must be contiguous [%d, %d]" % (n1, d))
+    want_v = p1 > 0 and d_v1 is not None
+    if want_v:
+        _req(d_v1, f32, "d_v1", 2)
+        if d_v1.shape != (n1 * p1, d) or not d_v1.is_contiguous() or vn1 is None:
+            raise ValueError("d_v1 must be contiguous [%d, %d] and pack1 must carry its direction norms" % (n1 * p1, d))
+    nbytes = kernel_bwd_ard_workspace_bytes(n1, p1, n2, p2, d)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
+    check(lib.dsvgp_kernel_bwd_ard(ctx.h, _ptr(G), _ld(G), 1 if isd else 0, _ptr(P1), _ptr(s1), _ptr(vn1 if want_v else None), n1, p1,
+                                   _ptr(P2), _ptr(s2), n2, p2, d, _ptr(ell), _ptr(hyp), 1 if symmetric else 0, _ptr(d_x1),
+                                   _ptr(d_v1 if want_v else None), _ptr(d_ell), _ptr(d_hyp), _ptr(workspace)), "dsvgp_kernel_bwd_ard")
+    return workspace
+
+
 def kernel_bwd_wide(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp, workspace=None):
     """kernel_bwd on the wide-input kernels whatever d (see kernel_fwd_wide)"""
     P1, s1, vn1 = pack1

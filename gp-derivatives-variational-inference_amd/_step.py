@@ -518,6 +518,15 @@ class ElboEngine:
         # the rectangular TRAINING step (loss_and_grads with pd != p directions per data point, csrc/assemble_rect.hip): pd while such a
         # step is being queued, None otherwise -- the data side's direction count wherever the piecewise path reads ``_pd``
         self._train_pd = None
+        # ARD lengthscales (raw_lengthscale [1, d], csrc/assemble_ard.hip): set by the entries built for them (predict, predict_joint,
+        # loss_and_grads) while such a call is being queued.  The packs then carry the per-dimension scaling, hyp[0] = 1, K_ZZ comes
+        # from the wide forward, K_ZX from the rectangular one, both backwards from dsvgp_kernel_bwd_ard; ``_ard_ell`` is the
+        # constrained lengthscale vector of the factor in use and ``_ard_diag`` the prior diagonal s [1, |v~|^2] of the data in flight
+        self._ard = False
+        self._ard_ell = None
+        self._ard_diag = None
+        self._ard_d_ell = None
+        self._eval_cache_ell = None
         self._zx_dirs = None                    # (idx, base) of the batch in flight when its directions were stated one-hot (_ops.state_directions)
         self.c_step_used = False        # whether the last step ran through the one-call path
         self.c_step_timed = []          # plans of the steps queued with record_events on, in order
@@ -574,10 +583,19 @@ class ElboEngine:
         p = V.shape[0] // M if M else 0
         Mp = M * (p + 1)
         self._problem_size(Mp)
-        hyp = _ops.hyp_forward(ctx, params["raw_lengthscale"], params["raw_outputscale"], params["raw_noise"])
+        if self._is_ard(params) and not self._ard:
+            raise ValueError("this entry is not built for ARD lengthscales (raw_lengthscale with %d entries): predict, predict_joint "
+                             "and loss_and_grads are" % params["raw_lengthscale"].numel())
+        if self._ard:
+            self._ard_ell, hyp = _ops.hyp_forward_ard(ctx, params["raw_lengthscale"], params["raw_outputscale"], params["raw_noise"])
+        else:
+            hyp = _ops.hyp_forward(ctx, params["raw_lengthscale"], params["raw_outputscale"], params["raw_noise"])
         # common shift of Z and x (gpytorch covar_dist centres on x1.mean): keeps the fp32 quadratic expansion accurate
         self.center = _ops.column_mean(ctx, Z.contiguous())
-        packZ = _ops.pack_points(ctx, Z.contiguous(), V.contiguous(), p, hyp, self.center)
+        if self._ard:
+            packZ = _ops.pack_points_ard(ctx, Z.contiguous(), V.contiguous() if p > 0 else None, p, self._ard_ell, self.center)
+        else:
+            packZ = _ops.pack_points(ctx, Z.contiguous(), V.contiguous(), p, hyp, self.center)
         self._pending_packZ = packZ
         if side_job is not None:
             main = torch.cuda.current_stream(self.device)
@@ -594,7 +612,7 @@ class ElboEngine:
             ctx.bind()                                  # back on the caller's stream
         L = self._get("L", (Mp, Mp), f64)
         info = self._get("info", (1,), torch.int32)
-        _ops.kernel_fwd(ctx, packZ, M, packZ, M, d, p, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
+        self._kzz_fwd(ctx, packZ, M, d, p, hyp, L)
         nrhs = max(int(nrhs), Mp + 1)
         ws = self._bytes("trsm_ws", _lib.lib.dsvgp_trsm_workspace_bytes(Mp, nrhs, self.trsm_nb))
         self._potrf_ws = self._potrf_and_inverse(ctx, L, info, ws, nrhs, "kzz")   # L and the inverted blocks of L
@@ -612,6 +630,49 @@ class ElboEngine:
         if sync:
             self._finish_factor(ctx, ladder=True)
         return hyp, packZ, L, (M, d, p, Mp)
+
+    def _kzz_fwd(self, ctx, packZ, M, d, p, hyp, L):
+        """L <- s K_ZZ + jitter I (float64 storage).  ARD: the wide forward whatever d -- the narrow specialised kernels behind
+        ``kernel_fwd`` are not used on ARD packs"""
+        fwd = _ops.kernel_fwd_wide if self._ard else _ops.kernel_fwd
+        fwd(ctx, packZ, M, packZ, M, d, p, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
+
+    @staticmethod
+    def _is_ard(params):
+        rl = params.get("raw_lengthscale")
+        return rl is not None and rl.numel() > 1
+
+    def _no_ard(self, params, what):
+        if self._is_ard(params):
+            raise ValueError("%s is not built for ARD lengthscales (a follow-up; the scalar-lengthscale model has it)" % what)
+
+    def _ard_refusals(self, params, x, fast=None, training=False):
+        """what the ARD entries are not built for, refused on the parameters and switches alone, before any device work"""
+        d = params["inducing_points"].shape[1]
+        if params["raw_lengthscale"].numel() != d:
+            raise ValueError("ARD lengthscales: raw_lengthscale must have one entry per input dimension (%d), got %d"
+                             % (d, params["raw_lengthscale"].numel()))
+        no = lambda what: ValueError("%s is not built for ARD lengthscales (a follow-up; the scalar-lengthscale model has it)" % what)
+        if params["inducing_points"].dtype != f32 or x.dtype != f32:
+            raise no("a float64 engine")
+        if self.whitening == "ciq":
+            raise no("CIQ whitening")
+        if "natural_vec" in params:
+            raise no("the natural parameterisation")
+        if self.shared_directions:
+            raise no("the shared-directions strategy")
+        if self.data_outputs == "values":
+            raise no("the derivative-free strategy")
+        coll = self.collective
+        if coll is not None and coll.world > 1:
+            raise no("a collective with world = %d" % coll.world)
+        if self.capture_mode:
+            raise no("graph capture (capture_mode)")
+        if training:
+            if self.deterministic:
+                raise no("the deterministic mode")
+            if fast:
+                raise no("the Gram fast path (fast=True)")
 
     def _potrf_scratch(self, name, n):
         """Cholesky scratch of ONE factor of THIS engine (``name``: kzz / ngd_P / ngd_LS / root).  It keeps the inverted
@@ -645,7 +706,7 @@ class ElboEngine:
         if not ladder:
             raise _Refactored()
         for t in range(CHOL_TRIES):                     # rare path: psd_safe_cholesky jitter ladder
-            _ops.kernel_fwd(ctx, packZ, M, packZ, M, d, p, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
+            self._kzz_fwd(ctx, packZ, M, d, p, hyp, L)
             _ops.add_diag_(ctx, L, self.chol_jitter * (10 ** t))
             self._potrf_ws = self._potrf_and_inverse(ctx, L, info, self._inverse_ws, Mp + 1, "kzz")
             if int(info.item()) == 0:
@@ -765,6 +826,8 @@ class ElboEngine:
 
     def _kernel_bwd_zx_bytes(self, M, B, d, p):
         """workspace bytes of ``_kernel_bwd_zx``"""
+        if self._ard:
+            return _ops.kernel_bwd_ard_workspace_bytes(M, p, B, self._train_pd, d)
         if self._train_pd is not None:
             return _ops.kernel_bwd_rect_workspace_bytes(M, p, B, self._train_pd, d)
         return _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, B, d, p)
@@ -772,7 +835,11 @@ class ElboEngine:
     def _kernel_bwd_zx(self, ctx, Kb32, packZ, M, packX, B, d, p, hyp, dZ, dV, d_hyp, kws):
         if self._train_pd is not None:                   # rectangular training step: the upstream [M', B(pd+1)] as it is
             ev = self._event_pair()
-            _ops.kernel_bwd_rect(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, hyp, dZ, dV, d_hyp, kws)
+            if self._ard:                                # d_ell through both sides' packed rows; the data side gets no point gradient
+                _ops.kernel_bwd_ard(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, self._ard_ell, hyp, False, dZ,
+                                    dV if p > 0 else None, self._ard_d_ell, d_hyp, kws)
+            else:
+                _ops.kernel_bwd_rect(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, hyp, dZ, dV, d_hyp, kws)
             self._event_done("assemble_bwd", ev)
             return
         if self.data_outputs == "values" and p > 0:
@@ -800,7 +867,10 @@ class ElboEngine:
             self._zx_dirs = _ops.stated_directions(D, d, p) if p > 0 else None
             Kzx = self._assemble_kzx(ctx, packZ, M, packX, B, d, p, hyp, Mp)
         else:
-            packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, hyp, self.center)
+            if self._ard:
+                packX = _ops.pack_points_ard(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, self._ard_ell, self.center)
+            else:
+                packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, hyp, self.center)
             self._zx_dirs = None
             Kzx = _ops.kernel_fwd_rect(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, Bp), f32))
         A64 = self._get("A64", (Mp, Bp), f64)
@@ -827,6 +897,12 @@ class ElboEngine:
         sws = self._bytes("stats_ws", _lib.lib.dsvgp_stats_workspace_bytes(Mp, Bp))
         _ops.predictive_stats(ctx, A32, W, pd, params["variational_mean"], params["constant"].reshape(-1), hyp, mu, var,
                               sws)
+        if self._ard:
+            # predictive_stats priced the prior diagonal as s [1, 1 / ell^2] with ell = hyp[0] = 1: s on every column.  The ARD
+            # kernel's is s [1, |v~_jb|^2] (dsvgp_kernel_diag_ard): add s (|v~_jb|^2 - 1) on the derivative columns (exactly 0 on the
+            # value columns, where the diagonal is s itself)
+            self._ard_diag = _ops.kernel_diag_ard(ctx, packX, B, pd, d, hyp)
+            var.add_(self._ard_diag - hyp[1])
         return packX, A64, A32, W, mu, var
 
     # ---- public API -----------------------------------------------------------------------------
@@ -835,6 +911,8 @@ class ElboEngine:
         """q(f) mean / variance plus likelihood noise: what ``likelihood(model(x)).mean/.variance`` returns.
         ``cache=True`` (eval mode) keeps the Cholesky factor and its inverted blocks across calls while the
         parameters are unchanged, like the reference's ``@cached`` ``_cholesky_factor`` (DGVS.py:72)."""
+        if self._is_ard(params):
+            return self._predict_ard(params, x, D, cache, False)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
             self._rect_pd(params, x, D)                 # (refuses a direction count other than the model's)
@@ -891,6 +969,8 @@ class ElboEngine:
         MultivariateNormal behind ``likelihood(model(x, derivative_directions=D))`` (reference DGVS.py:199-208), which the
         BO drivers sample jointly (experiments/GNN_bo/gcn_turbo.py:238-239).
         Sigma = s K_XX + 1e-4 I + W^T W - A^T A + noise I: one symmetric kernel assembly and two MFMA Gram products."""
+        if self._is_ard(params):
+            return self._predict_ard(params, x, D, cache, True)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
             # NGD-CIQ: the reference's q(f) carries a DIAGONAL covariance, DiagLazyTensor(predictive_var) (CiqDGVS.py:264-267);
@@ -918,6 +998,7 @@ class ElboEngine:
         point -- the diagonal blocks of ``predict_joint``'s Sigma without K_XX, the two Gram products or anything of size B' x B'
         (csrc/predict_blocks.hip).  Everything up to A = L^-1 K_ZX and W = L_S^T A is ``predict``'s, evaluation cache included, so any
         direction count per data point goes (``D`` None: [B, 1, 1], the variances)."""
+        self._no_ard(params, "predict_blocks (and the block roots built on it)")
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
             # NGD-CIQ: q(f) carries a diagonal covariance (``predict_joint``): the blocks are diagonal too
@@ -943,6 +1024,7 @@ class ElboEngine:
         ``_factor`` (jitter ladder included), packed with the inducing set by dsvgp_mean_prepare.  Natural parameters, shared
         directions, p = 0 (plain SVGP) and p = d (full-gradient SVGP) are the same code.  The factorisation runs in the engine's
         factor buffers, so the evaluation cache of ``predict`` is dropped (it refactors on its next call)."""
+        self._no_ard(params, "mean_predictor")
         if self.whitening == "ciq":
             raise NotImplementedError("posterior-mean predictor with CIQ whitening: alpha there is K^{-1/2} m by msMINRES "
                                       "(contour-integral quadrature), which is not built; use predict()")
@@ -979,6 +1061,7 @@ class ElboEngine:
         absent: drawn on the device with ``generator``.  The factor is ``_factor``'s (jitter ladder included); Phi_Z' and the two
         solves run in float64 once per call, dsvgp_paths_prepare packs the fp32 weights.  Natural parameters, shared directions, p = 0
         and p = d are the same code; the evaluation cache of ``predict`` is dropped (it refactors on its next call)."""
+        self._no_ard(params, "sample_paths (and hvp / descend on the paths)")
         if self.whitening == "ciq":
             raise NotImplementedError("pathwise posterior samples with CIQ whitening: nu there needs K^{-1/2} by msMINRES "
                                       "(contour-integral quadrature), which is not built; use predict_joint() and its samples")
@@ -1048,6 +1131,7 @@ class ElboEngine:
         (fp64 throughout, like the reference's ``.double()`` solves).  The reference evaluates the prior p(u) through
         ``self(inducing_points, prior=True)`` WITHOUT direction kwargs, which its directional kernel cannot take: the
         model's own inducing directions are used here, the evident intent.  Returns (m_w fp32, L_w fp32 lower)."""
+        self._no_ard(params, "whiten_legacy")
         ctx = _ops.Context.get(self.device)
         self._eval_cache = None
         m_u, L_u = params["variational_mean"], params["chol_variational_covar"]
@@ -1070,6 +1154,7 @@ class ElboEngine:
     @torch.no_grad()
     def prior_moments(self, params):
         """p(u) = N(c 1, s K(Z, Z; V, V)) at the inducing points, un-jittered, fp32: ``strategy(Z, prior=True)``"""
+        self._no_ard(params, "prior_moments")
         ctx = _ops.Context.get(self.device)
         Z, V = params["inducing_points"], params["inducing_directions"]
         M, d = Z.shape
@@ -1136,10 +1221,22 @@ class ElboEngine:
         of y[b] under N(mu[b], roots[b] roots[b]^T) at every point."""
         return _ops.blocks_logpdf(_ops.Context.get(self.device) if roots.is_cuda else None, roots, logdet, mu, y)
 
+    def _predict_ard(self, params, x, D, cache, joint):
+        """predict / predict_joint of a model with ARD lengthscales: the per-output path on ARD packs (csrc/assemble_ard.hip)"""
+        self._ard_refusals(params, x)
+        ctx = _ops.Context.get(self.device)
+        self._ard = True
+        try:
+            return self._predict_chol(ctx, params, x, D, cache, joint=joint)
+        finally:
+            self._ard = False
+
     def _predict_chol(self, ctx, params, x, D, cache, joint=False, blocks=False):
         # (the parameters arrive expanded; the evaluation cache below is keyed on them alone: calls with different direction
         #  counts on an unchanged model share the factor)
         rect_pd = self._rect_pd(params, x, D)
+        if self._ard and rect_pd is None:               # ARD: always the rectangular assembly, equal counts included
+            rect_pd = self._direction_counts(params, x, D)[1]
         key = tuple((t.data_ptr(), t._version) for t in params.values()) if cache else None
         hit = cache and self._eval_cache is not None and self._eval_cache[0] == key
         if "natural_vec" in params:
@@ -1151,11 +1248,13 @@ class ElboEngine:
                 params["variational_mean"], params["chol_variational_covar"] = m32, LS32
         if hit:
             _, hyp, packZ, L, dims, _ = self._eval_cache
+            self._ard_ell = self._eval_cache_ell
         else:
             Mz = params["inducing_points"].shape[0]
             pz = params["inducing_directions"].shape[0] // Mz if Mz else 0
             hyp, packZ, L, dims = self._factor(ctx, params, nrhs=x.shape[0] * ((self._pd(pz) if rect_pd is None else rect_pd) + 1))
             self._eval_cache = (key, hyp, packZ, L, dims, params) if cache else None
+            self._eval_cache_ell = self._ard_ell if self._ard else None
         packX, _, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=hit, rect_pd=rect_pd)
         if blocks:                                                                 # (predict_blocks: no K_XX, nothing B' x B')
             pd = self._pd(dims[2]) if rect_pd is None else rect_pd
@@ -1165,7 +1264,10 @@ class ElboEngine:
             B = x.shape[0]
             if rect_pd is not None:
                 p = rect_pd                                                        # (the data pack was made with it)
-            Sigma = _ops.kernel_fwd(ctx, packX, B, packX, B, d, p, hyp)            # s K(X, X; D, D), all (p+1)^2 blocks
+            if self._ard:                                                          # (its diagonal is s [1, |v~|^2] by itself)
+                Sigma = _ops.kernel_fwd_wide(ctx, packX, B, packX, B, d, p, hyp)
+            else:
+                Sigma = _ops.kernel_fwd(ctx, packX, B, packX, B, d, p, hyp)        # s K(X, X; D, D), all (p+1)^2 blocks
             if rect_pd is None and self.data_outputs == "values" and p > 0:
                 Sigma = Sigma[::p + 1, ::p + 1].contiguous()
             if not self._no_middle:
@@ -1183,6 +1285,8 @@ class ElboEngine:
         ``include_kl=False`` leaves the (replicated) KL term out so exactly one rank adds it.
         ``fast`` (default ``self.elbo_fast``): in ELBO mode use the Gram-matrix formulation, which does not
         produce per-output variances (``varn`` is then an empty tensor; ``predict`` gives them on demand)."""
+        if self._is_ard(params):
+            return self._loss_and_grads_ard(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
         train_pd = self._train_rect_pd(params, x, D)       # (refusals first: shapes only, no device work)
         if train_pd is None:
             return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
@@ -1194,6 +1298,26 @@ class ElboEngine:
             return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
         finally:
             self._train_pd = None
+
+    def _loss_and_grads_ard(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
+        """The step of a model with ARD lengthscales (raw_lengthscale [1, d]): ELBO or PLL on the piecewise per-output path, any number
+        of data directions, with ARD packs, hyp[0] = 1, the wide / rectangular forward and dsvgp_kernel_bwd_ard for K_ZX-bar and
+        K_ZZ-bar (csrc/assemble_ard.hip).  ``fast=None`` takes this path; the Gram fast path (``fast=True``) is refused."""
+        self._ard_refusals(params, x, fast=fast, training=True)
+        if mll_type not in ("ELBO", "PLL"):
+            raise ValueError(mll_type)
+        p, pd = self._direction_counts(params, x, D)
+        if pd > 95:
+            raise ValueError("at most 95 derivative directions per data point, got %d" % pd)
+        B = x.shape[0]
+        if y.shape != (B * (pd + 1),):
+            raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % (B * (pd + 1)))
+        self._ard, self._train_pd = True, pd
+        self._ard_d_ell = torch.zeros(x.shape[1], dtype=f32, device=self.device)
+        try:
+            return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, False)
+        finally:
+            self._ard, self._train_pd, self._ard_d_ell, self._ard_diag = False, None, None, None
 
     def _loss_and_grads_checked(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
         ctx = _ops.Context.get(self.device)
@@ -1955,7 +2079,8 @@ class ElboEngine:
 
         dZ, dV = grads["inducing_points"], grads["inducing_directions"]
         kws = self._bytes("kbwd_ws", max(self._kernel_bwd_zx_bytes(M, B, d, p),
-                                         _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, M, d, p)))
+                                         _ops.kernel_bwd_ard_workspace_bytes(M, p, M, p, d) if self._ard
+                                         else _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, M, d, p)))
         # K_ZX-bar's kernel backward (HBM-bound read of 4 M' B' bytes) next to the fp64 products of L-bar and the Cholesky backward
         # (matrix-pipe bound): on the side stream from the moment the dense product is done, joined before the K_ZZ kernel backward
         # (both accumulate into Z-bar, V-bar and the hyper-parameter slots)
@@ -1993,8 +2118,22 @@ class ElboEngine:
             Kzzbar = self._chol_backward(ctx, L, Lbar, self._buf["trsm_ws"], Mp, phi_arg=use_fast)
             if zx_done is not None:
                 torch.cuda.current_stream(self.device).wait_event(zx_done)
-            _ops.kernel_bwd(ctx, Kzzbar, packZ, M, packZ, M, d, p, hyp, True, dZ, dV, d_hyp, kws)
+            if self._ard:
+                _ops.kernel_bwd_ard(ctx, Kzzbar, packZ, M, p, packZ, M, p, d, self._ard_ell, hyp, True, dZ, dV if p > 0 else None,
+                                    self._ard_d_ell, d_hyp, kws)
+            else:
+                _ops.kernel_bwd(ctx, Kzzbar, packZ, M, packZ, M, d, p, hyp, True, dZ, dV, d_hyp, kws)
 
+        if self._ard:
+            # the prior diagonal of the data: likelihood_terms priced it as s [1, 1 / ell^2] at ell = hyp[0] = 1 (scal[3] = sum of
+            # var_bar, scal[4] the scalar lengthscale's share).  Both are replaced by the ARD diagonal's own backward -- d_hyp[1] +=
+            # sum var_bar diag / s, d_ell[k] += -(2 s / ell_k) sum var_bar v~_k^2 -- and the scalar lengthscale slot stays empty
+            _ops.kernel_diag_ard_bwd(ctx, packX, B, pd, d, self._ard_ell, hyp, self._ard_diag, var_bar, self._ard_d_ell, d_hyp)
+            scal[3:5].zero_()
+            _ops.hyp_backward_ard(ctx, params["raw_lengthscale"].reshape(-1), params["raw_outputscale"].reshape(-1),
+                                  params["raw_noise"].reshape(-1), self._ard_d_ell, torch.zeros(4, dtype=f32, device=dev),
+                                  grads["raw_lengthscale"].reshape(-1), grads["raw_outputscale"].reshape(-1),
+                                  grads["raw_noise"].reshape(-1))     # (outputscale and noise: the epilogue below, from d_hyp)
         if self._dev_scale:
             # the kernel gradients above came from the UNSCALED K_ZX-bar / K_ZZ-bar: apply 2 vbar = 1 / (noise rows) now
             _ops.scale_by_vbar_(ctx, [dZ, dV if dV.numel() else None, d_hyp[0:2]], hyp, rows)

@@ -419,6 +419,28 @@ extern "C" size_t dsvgp_kernel_bwd_rect_workspace_bytes(int n1, int p1, int n2, 
     return rect_bwd_plan(n1, p1, n2, p2, d, r) ? 0 : r.w.bytes;
 }
 
+// dsvgp_kernel_bwd_rect's tile and contraction launches on its own plan, for a caller that brings another points reduction
+// (assemble_ard.hip): the same kernels, tiles and arithmetic; TB[n1q][n2q] is handed out as well
+int kernel_bwd_rect_tiles_plan(int n1, int p1, int n2, int p2, int d, size_t* bytes, int* ns) {
+    RectBwdPlan r;
+    if (int rc = rect_bwd_plan(n1, p1, n2, p2, d, r)) return rc;
+    *bytes = r.w.bytes; *ns = r.w.ns;
+    return 0;
+}
+int launch_kernel_bwd_rect_tiles(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1,
+                                 int p1, const float* P2, const float* self2, int n2, int p2, int d, const float* hyp, void* workspace,
+                                 float** slab, int* ns, float** partials, int* nparts, float** TB) {
+    RectBwdPlan r;
+    if (int rc = rect_bwd_plan(n1, p1, n2, p2, d, r)) return rc;
+    if (ldg < r.n2q) return DSVGP_EINVAL;
+    if (int rc = launch_bwd_tiled(st, r.w, G, ldg, g_is_double, P1, self1, r.n1q, r.q1, P2, self2, r.n2q, r.q2, r.K4, r.DP, r.NP, hyp,
+                                  workspace, slab, partials))
+        return rc;
+    *ns = r.w.ns; *nparts = r.w.nparts;
+    *TB = *partials + r.w.part_f;
+    return 0;
+}
+
 extern "C" int dsvgp_kernel_bwd_rect(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
                                      const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
                                      const float* hyp, float* d_x1, float* d_v1, float* d_hyp, void* workspace) {

@@ -143,6 +143,13 @@ size_t kernel_bwd_wide_workspace(int n1q, int n2q, int q, int NP);
 int launch_kernel_bwd_wide(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1q,
                            const float* P2, const float* self2, int n2q, int q, int K4, int DP, int NP, const float* hyp, void* workspace,
                            float** slab, int* ns, float** partials, int* nparts);
+// the tile and contraction launches of dsvgp_kernel_bwd_rect (assemble_wide.hip) for the ARD backward's own points reduction
+// (assemble_ard.hip): plan (workspace bytes, slab count; DSVGP_EINVAL as dsvgp_kernel_bwd_rect_workspace_bytes returns 0) and launch --
+// slab[ns][n1q][NP], partials[nparts][2] and the Tbar matrix TB[n1q][n2q], all inside `workspace`
+int kernel_bwd_rect_tiles_plan(int n1, int p1, int n2, int p2, int d, size_t* bytes, int* ns);
+int launch_kernel_bwd_rect_tiles(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1,
+                                 int p1, const float* P2, const float* self2, int n2, int p2, int d, const float* hyp, void* workspace,
+                                 float** slab, int* ns, float** partials, int* nparts, float** TB);
 // the points launch of the kernel backwards (assemble.hip: finish_points) for side 1's geometry (d, p): d_x1 / d_v1 / d_hyp[0..1] +=
 int kernel_bwd_finish_points(dsvgp_ctx* ctx, int d, int p, const float* slab, int ns, const float* P1, const float* vnorm1, int n1,
                              const float* hyp, float sym, float* d_x1, float* d_v1, const float* partials, int nparts, float* d_hyp);

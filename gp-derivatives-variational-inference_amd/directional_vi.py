@@ -36,7 +36,9 @@ from .parallel import DataParallel
 
 
 class GPModel(ApproximateGP):
-    def __init__(self, inducing_points, inducing_directions, dim, learn_inducing_locations=True, **kwargs):
+    def __init__(self, inducing_points, inducing_directions, dim, learn_inducing_locations=True, ard_num_dims=None, **kwargs):
+        # ``ard_num_dims`` (int, not in the reference; None = one scalar lengthscale): one lengthscale per input dimension,
+        # raw_lengthscale [1, ard_num_dims] under the same state_dict key, as gpytorch's RBFKernel(ard_num_dims=)
         torch.nn.Module.__init__(self)
         self.num_inducing = len(inducing_points)
         self.num_directions = int(len(inducing_directions) / self.num_inducing)  # num directions per point
@@ -60,7 +62,9 @@ class GPModel(ApproximateGP):
         self.data_parallel = None
         self.data_directions = None             # int: the data carry that many directions per point, not num_directions (ApproximateGP)
         self.mean_module = ConstantMean()
-        self.covar_module = ScaleKernel(RBFKernelDirectionalGrad())
+        if ard_num_dims is not None and int(ard_num_dims) != int(dim):
+            raise ValueError("ard_num_dims must equal the input dimension (%d), got %s" % (dim, ard_num_dims))
+        self.covar_module = ScaleKernel(RBFKernelDirectionalGrad(ard_num_dims=ard_num_dims))
         if self._ciq:
             # stable initialization of lengthscale for CIQ (:58-60): lengthscale = 1 / num_inducing through the
             # inverse of the softplus constraint
@@ -470,8 +474,10 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
                    num_epochs=1, learning_rate_hypers=0.01, inducing_data_initialization=True, lr_sched=None,
                    mll_type="ELBO", gamma=0.1, fixed_inducing_locations=None, seed=None, tensors=None,
                    use_ngd=False, learning_rate_ngd=0.1, use_ciq=False, num_contour_quadrature=15, model_class=None,
-                   dfree=False, shared=False, data_directions=None):
+                   dfree=False, shared=False, data_directions=None, ard_num_dims=None):
     """Everything ``train_gp`` does before its loop (directional_vi.py:130-219); returns a TrainLoop.
+    ``ard_num_dims`` (int, default None = one scalar lengthscale): one lengthscale per input dimension (must equal the input
+    dimension) -- the engine's ARD step: Cholesky-whitened per-point model, float32, one rank.
     ``data_directions`` (int, default None = ``num_directions``): derivative columns of y per minibatch point, whatever the number of
     inducing directions (0: function values only; ``dim``: the full gradient) -- the engine's rectangular training step."""
     assert num_directions == minibatch_dim
@@ -483,6 +489,13 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
             raise ValueError("data_directions runs on one rank (dp): the rectangular training step is not built for a collective")
         if torch.get_default_dtype() == torch.float64 or (tensors is not None and tensors[0].dtype == torch.float64):
             raise ValueError("data_directions with a float64 dataset: the rectangular kernel backward is built in float32 only")
+    if ard_num_dims is not None:
+        if dfree or shared or use_ciq or use_ngd:
+            raise ValueError("dfree / shared / CIQ / NGD training is not built for ARD lengthscales (ard_num_dims)")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("a collective with world > 1 is not built for ARD lengthscales (ard_num_dims)")
+        if torch.get_default_dtype() == torch.float64 or (tensors is not None and tensors[0].dtype == torch.float64):
+            raise ValueError("a float64 dataset is not built for ARD lengthscales (ard_num_dims): the ARD kernels are float32")
     if not torch.cuda.is_available():
         raise RuntimeError("train_gp needs an MI355X (HIP) device: the DSVGP hot path has no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
@@ -515,6 +528,9 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
     elif use_ngd:                                                         # :166-167
         model = model_class(inducing_points, inducing_directions, dim, variational_distribution="NGD",
                             learn_inducing_locations=learn_inducing_locations)
+    elif ard_num_dims is not None:
+        model = model_class(inducing_points, inducing_directions, dim, learn_inducing_locations=learn_inducing_locations,
+                            ard_num_dims=int(ard_num_dims))
     else:
         model = model_class(inducing_points, inducing_directions, dim,
                             learn_inducing_locations=learn_inducing_locations)
@@ -605,7 +621,8 @@ def train_gp(train_dataset, num_inducing=128,
     Extra keyword arguments understood through ``**args`` (all optional, ignored by the reference):
       ``seed`` (int): seeds the minibatch permutation and the derivative-column sampling (must be equal
       on all ranks under torch.distributed; broadcast from rank 0 when omitted);
-      ``max_steps`` (int): stop after this many optimisation steps.
+      ``max_steps`` (int): stop after this many optimisation steps;
+      ``ard_num_dims`` (int, the input dimension): one lengthscale per input dimension (``setup_training``).
     """
     assert num_directions == minibatch_dim
     loop = setup_training(train_dataset, num_inducing, num_directions, minibatch_size, minibatch_dim, num_epochs,
@@ -613,7 +630,7 @@ def train_gp(train_dataset, num_inducing=128,
                           fixed_inducing_locations, seed=args.get("seed"), use_ngd=use_ngd,
                           learning_rate_ngd=learning_rate_ngd, use_ciq=use_ciq,
                           num_contour_quadrature=num_contour_quadrature, model_class=args.get("_model_class"),
-                          shared=bool(args.get("_shared")), data_directions=data_directions)
+                          shared=bool(args.get("_shared")), data_directions=data_directions, ard_num_dims=args.get("ard_num_dims"))
     n_samples = loop.X.shape[0]
     stride = (num_directions if loop.data_directions is None else loop.data_directions) + 1      # outputs per minibatch point
     max_steps = args.get("max_steps")

@@ -163,6 +163,56 @@ size_t dsvgp_kernel_bwd_rect_workspace_bytes(int n1, int p1, int n2, int p2, int
 int dsvgp_kernel_bwd_rect(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
                           const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
                           const float* hyp, float* d_x1, float* d_v1, float* d_hyp, void* workspace);
+/* ---- ARD: one lengthscale per input dimension (csrc/assemble_ard.hip) --------------------------------------------------------------
+ * The packed rows carry the per-dimension scaling, x~ = (x - c) ./ ell and v~_a = (v_a / |v_a|) ./ ell with ell[d], and the kernels
+ * run with hyp[0] = 1: micro-block (i, j) of the ARD kernel is k [[1, w~_b], [-u~_a, v~_a.v~_b - u~_a w~_b]], r = x~1 - x~2,
+ * u~_a = r.v~1_a, w~_b = r.v~2_b, k = s exp(-|r|^2/2).  The FORWARD is dsvgp_kernel_fwd_wide (K_ZZ: double output, jitter) or
+ * dsvgp_kernel_fwd_rect on ARD packs with the hyp below; the _canon / _canon2 kernels (unit one-hot data directions) are not for ARD.
+ * All entries: fixed summation orders, no floating-point atomics, two identical calls are bitwise equal.
+ *
+ * dsvgp_hyp_forward_ard: ell[k] = softplus(raw_lengthscale[k]), k < d; hyp[4] as dsvgp_hyp_forward writes it except hyp[0] = 1.
+ * dsvgp_hyp_backward_ard: d_raw_lengthscale[k] += d_ell[k] sigmoid(raw_lengthscale[k]); d_raw_outputscale / d_raw_noise += as
+ *   dsvgp_hyp_backward from d_hyp[1], d_hyp[2] (d_hyp[0] is not read).  DSVGP_EINVAL: a null pointer, d < 1.                         */
+int dsvgp_hyp_forward_ard(dsvgp_ctx* ctx, const float* raw_lengthscale, int d, const float* raw_outputscale, const float* raw_noise,
+                          float* ell, float* hyp);
+int dsvgp_hyp_backward_ard(dsvgp_ctx* ctx, const float* raw_lengthscale, int d, const float* raw_outputscale, const float* raw_noise,
+                           const float* d_ell, const float* d_hyp, float* d_raw_lengthscale, float* d_raw_outputscale,
+                           float* d_raw_noise);
+/* dsvgp_pack_points with ell[d] in place of hyp: the same layout (P[n*(p+1), DP], DP = dsvgp_packed_width(d), zero padding, indicator
+ * column DP - 4 on value rows), rows x~ and v~_a as above, self = |x~|^2 and x~.v~_a by the k-ordered fma chain of the kernels' MFMA
+ * product (r == 0 stays exact on the diagonal micro-blocks of K_ZZ), vnorm = |v|.  One wave per row: any d >= 1.  Both sides of a kernel
+ * call are packed with the same ell and center (center may be null = 0); v and vnorm may be null at p = 0.
+ * DSVGP_EINVAL: a null pointer, n < 0, d < 1, p outside [0, 95], n*(p+1) beyond INT_MAX.  n == 0: returns 0.                          */
+int dsvgp_pack_points_ard(dsvgp_ctx* ctx, const float* x, const float* v, int n, int d, int p, const float* ell, const float* center,
+                          float* P, float* self, float* vnorm);
+/* The prior diagonal of the ARD kernel from a pack: out[i*(p+1)] = s, out[i*(p+1) + a] = s |v~_ia|^2 (in place of s / ell^2), and its
+ * backward given gbar[n*(p+1)] and the forward's out: d_hyp[1] += sum gbar out / s, d_ell[k] += -(2 s / ell_k) sum_{i, a >= 1}
+ * gbar_ia v~_iak^2 (one workgroup per k, fp64 partial sums in a fixed order).  Same refusals as dsvgp_pack_points_ard.                */
+int dsvgp_kernel_diag_ard(dsvgp_ctx* ctx, const float* P, int n, int p, int d, const float* hyp, float* out);
+int dsvgp_kernel_diag_ard_bwd(dsvgp_ctx* ctx, const float* P, int n, int p, int d, const float* ell, const float* hyp, const float* out,
+                              const float* gbar, float* d_ell, float* d_hyp);
+/* Backward of the ARD kernel out[n1*(p1+1), n2*(p2+1)] with respect to side 1 (x1, v1), the lengthscale vector and the outputscale,
+ * given G = dLoss/dOut (leading dimension ldg >= n2*(p2+1); g_is_double selects float / double).  Accumulates (+=) into d_x1[n1, d],
+ * d_v1[n1*p1, d], d_ell[d] (through BOTH sides' packed rows) and d_hyp[1]; d_hyp[0] is not touched.  d_ell may be null (a second call
+ * with the sides swapped, for side 2's point gradients, must not count d_ell and d_hyp twice: pass d_ell = null there and a scratch
+ * d_hyp); d_v1 may be null (vnorm1 is then not read; p1 = 0 needs neither).  The other outputs do not depend on whether d_ell is given.
+ * symmetric != 0: n1 == n2, p1 == p2, side 2 IS side 1 (the same pack) and G is symmetric -- the K_ZZ case: point and direction
+ * gradients doubled, side 2's share of d_ell taken from side 1.
+ * Launches: the Tbar tiles and their contraction with side 2's rows exactly as dsvgp_kernel_bwd_rect runs them (hyp[0] = 1), a points
+ * reduction per point of side 1, for d_ell and symmetric == 0 the column sums of Tbar over side 1's value rows and side 2's self-term
+ * rows, and a fixed-order column reduction (fp64 partial sums).
+ * workspace: dsvgp_kernel_bwd_ard_workspace_bytes bytes, 4-byte aligned (a pure host function; 0 for shapes that
+ * dsvgp_kernel_bwd_rect_workspace_bytes refuses).  dsvgp_kernel_bwd_ard_slabs: how many split slabs the contraction writes for these
+ * shapes (0: refused).  Alignment: P1 and P2 16 bytes, G its element size.
+ * DSVGP_EINVAL: a null pointer other than the optional ones, d < 1, p1 or p2 outside [0, 95], negative n1 / n2, symmetric with n1 != n2
+ * or p1 != p2, n*(p+1) beyond INT_MAX on a side, more than 65535 row tiles or 64-row contraction tiles, ldg too small, P1 or P2
+ * misaligned.  n1 == 0 or n2 == 0: returns 0, nothing is touched.                                                                     */
+size_t dsvgp_kernel_bwd_ard_workspace_bytes(int n1, int p1, int n2, int p2, int d);
+int dsvgp_kernel_bwd_ard_slabs(int n1, int p1, int n2, int p2, int d);
+int dsvgp_kernel_bwd_ard(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
+                         const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
+                         const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell, float* d_hyp,
+                         void* workspace);
 /* 1 when dsvgp_kernel_fwd_canon / _bwd_canon take the geometry (d, p), 0 otherwise */
 int dsvgp_kernel_canon_supported(int d, int p);
 /* backward of dsvgp_kernel_fwd_canon (symmetric = 0 semantics; same workspace size as dsvgp_kernel_bwd) */
