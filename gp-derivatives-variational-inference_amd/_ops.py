@@ -732,6 +732,82 @@ def kernel_bwd_ard(ctx, G, pack1, n1, p1, pack2, n2, p2, d, ell, hyp, symmetric,
     return workspace
 
 
+def kernel_fwd_matern52(ctx, pack1, n1, p1, pack2, n2, p2, d, hyp, jitter=0.0, out=None, dtype=f32):
+    """out[n1 (p1 + 1), n2 (p2 + 1)] = s K(x1, x2; v1, v2) of the Matern-5/2 kernel with directional derivatives, from ``pack_points_ard``
+    packs (same ell and center on both sides) and ``hyp_forward_ard``'s hyp; float32, or float64 storage with ``dtype``; ``jitter`` goes on
+    the global diagonal (K_ZZ: both sides the same pack).  csrc/assemble_matern.hip; backward: ``kernel_bwd_matern52``"""
+    P1, s1 = _req_pack(pack1, n1, p1, d, "pack1")
+    P2, s2 = _req_pack(pack2, n2, p2, d, "pack2")
+    shape = (n1 * (p1 + 1), n2 * (p2 + 1))
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=P1.device)
+    _req(out, dtype, "out", 2)
+    if out.shape != shape:
+        raise ValueError("out has shape %s, expected %s" % (tuple(out.shape), shape))
+    check(lib.dsvgp_kernel_fwd_matern52(ctx.h, _ptr(P1), _ptr(s1), n1, p1, _ptr(P2), _ptr(s2), n2, p2, d, _ptr(hyp), float(jitter),
+                                        _ptr(out), _ld(out), 1 if dtype == f64 else 0), "dsvgp_kernel_fwd_matern52")
+    return out
+
+
+def kernel_diag_matern52(ctx, pack, n, p, d, hyp):
+    """out[n (p + 1)] = s [1, (5/3) |v~_1|^2, ..., (5/3) |v~_p|^2] per point: the prior diagonal of the Matern-5/2 kernel from a
+    ``pack_points_ard`` pack"""
+    P, _ = _req_pack(pack, n, p, d, "pack")
+    out = torch.empty(n * (p + 1), dtype=f32, device=P.device)
+    check(lib.dsvgp_kernel_diag_matern52(ctx.h, _ptr(P), n, p, d, _ptr(hyp), _ptr(out)), "dsvgp_kernel_diag_matern52")
+    return out
+
+
+def kernel_diag_matern52_bwd(ctx, pack, n, p, d, ell, hyp, out, gbar, d_ell, d_hyp):
+    """backward of ``kernel_diag_matern52`` given gbar[n (p + 1)] and the forward's ``out``: accumulates (+=) into d_ell[d] and d_hyp[1]"""
+    P, _ = _req_pack(pack, n, p, d, "pack")
+    _req_ell(ell, d)
+    _req_ell(d_ell, d)
+    for t, name in ((out, "out"), (gbar, "gbar")):
+        _req(t, f32, name, 1)
+        if t.shape[0] != n * (p + 1):
+            raise ValueError("%s must have %d entries" % (name, n * (p + 1)))
+    check(lib.dsvgp_kernel_diag_matern52_bwd(ctx.h, _ptr(P), n, p, d, _ptr(ell), _ptr(hyp), _ptr(out), _ptr(gbar), _ptr(d_ell),
+                                             _ptr(d_hyp)), "dsvgp_kernel_diag_matern52_bwd")
+
+
+def kernel_bwd_matern52_workspace_bytes(n1, p1, n2, p2, d):
+    """bytes of the workspace of ``kernel_bwd_matern52`` (pure host arithmetic; ``kernel_bwd_ard``'s rounded up to a multiple of 16); 0 for
+    a shape it does not take"""
+    return int(lib.dsvgp_kernel_bwd_matern52_workspace_bytes(int(n1), int(p1), int(n2), int(p2), int(d)))
+
+
+def kernel_bwd_matern52(ctx, G, pack1, n1, p1, pack2, n2, p2, d, ell, hyp, symmetric, d_x1, d_v1, d_ell, d_hyp, workspace=None):
+    """backward of ``kernel_fwd_matern52`` with ``kernel_bwd_ard``'s arguments and semantics: accumulates (+=) into d_x1, d_v1, d_ell
+    (through both sides' packed rows) and d_hyp[1]; d_ell and d_v1 may be None (csrc/assemble_matern.hip)"""
+    P1, s1 = _req_pack(pack1, n1, p1, d, "pack1")
+    P2, s2 = _req_pack(pack2, n2, p2, d, "pack2")
+    vn1 = pack1[2] if len(pack1) > 2 else None
+    isd = G.dtype == f64
+    _req(G, f64 if isd else f32, "G", 2)
+    if G.shape != (n1 * (p1 + 1), n2 * (p2 + 1)):
+        raise ValueError("G has shape %s, expected %s" % (tuple(G.shape), (n1 * (p1 + 1), n2 * (p2 + 1))))
+    _req_ell(ell, d)
+    if d_ell is not None:
+        _req_ell(d_ell, d)
+    _req(d_x1, f32, "d_x1", 2)
+    if d_x1.shape != (n1, d) or not d_x1.is_contiguous():
+        raise ValueError("d_x1 must be contiguous [%d, %d]" % (n1, d))
+    want_v = p1 > 0 and d_v1 is not None
+    if want_v:
+        _req(d_v1, f32, "d_v1", 2)
+        if d_v1.shape != (n1 * p1, d) or not d_v1.is_contiguous() or vn1 is None:
+            raise ValueError("d_v1 must be contiguous [%d, %d] and pack1 must carry its direction norms" % (n1 * p1, d))
+    nbytes = kernel_bwd_matern52_workspace_bytes(n1, p1, n2, p2, d)
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=G.device)
+    check(lib.dsvgp_kernel_bwd_matern52(ctx.h, _ptr(G), _ld(G), 1 if isd else 0, _ptr(P1), _ptr(s1), _ptr(vn1 if want_v else None), n1, p1,
+                                        _ptr(P2), _ptr(s2), n2, p2, d, _ptr(ell), _ptr(hyp), 1 if symmetric else 0, _ptr(d_x1),
+                                        _ptr(d_v1 if want_v else None), _ptr(d_ell), _ptr(d_hyp), _ptr(workspace)),
+          "dsvgp_kernel_bwd_matern52")
+    return workspace
+
+
 def kernel_bwd_wide(ctx, G, pack1, n1, pack2, n2, d, p, hyp, symmetric, d_x1, d_v1, d_hyp, workspace=None):
     """kernel_bwd on the wide-input kernels whatever d (see kernel_fwd_wide)"""
     P1, s1, vn1 = pack1

@@ -527,6 +527,13 @@ class ElboEngine:
         self._ard_diag = None
         self._ard_d_ell = None
         self._eval_cache_ell = None
+        # the covariance family: "rbf" (everything above) or "matern52" (csrc/assemble_matern.hip).  Matern-5/2 runs the ARD path --
+        # ARD packs, hyp[0] = 1, piecewise per-output -- with the Matern tile kernels and prior diagonal in place of the RBF ones; a
+        # scalar raw_lengthscale [1, 1] is expanded to d equal entries for the pack and its gradient summed back.  ``_matern`` is set
+        # (with ``_ard``) while such a call is being queued; with kernel == "rbf" nothing below is reached
+        self.kernel = "rbf"
+        self._matern = False
+        self._cache_key_params = None
         self._zx_dirs = None                    # (idx, base) of the batch in flight when its directions were stated one-hot (_ops.state_directions)
         self.c_step_used = False        # whether the last step ran through the one-call path
         self.c_step_timed = []          # plans of the steps queued with record_events on, in order
@@ -634,6 +641,9 @@ class ElboEngine:
     def _kzz_fwd(self, ctx, packZ, M, d, p, hyp, L):
         """L <- s K_ZZ + jitter I (float64 storage).  ARD: the wide forward whatever d -- the narrow specialised kernels behind
         ``kernel_fwd`` are not used on ARD packs"""
+        if self._matern:
+            _ops.kernel_fwd_matern52(ctx, packZ, M, p, packZ, M, p, d, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
+            return
         fwd = _ops.kernel_fwd_wide if self._ard else _ops.kernel_fwd
         fwd(ctx, packZ, M, packZ, M, d, p, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
 
@@ -673,6 +683,50 @@ class ElboEngine:
                 raise no("the deterministic mode")
             if fast:
                 raise no("the Gram fast path (fast=True)")
+
+    def _is_matern(self):
+        """whether the engine's kernel is Matern-5/2; any value but "rbf" / "matern52" is refused"""
+        kernel = getattr(self, "kernel", "rbf")
+        if kernel not in ("rbf", "matern52"):
+            raise ValueError("ElboEngine.kernel must be 'rbf' or 'matern52', got %r" % (kernel,))
+        return kernel == "matern52"
+
+    def _no_matern(self, what):
+        if self._is_matern():
+            raise ValueError("%s is not built for the Matern-5/2 kernel (kernel = 'matern52'): its closed forms are the RBF kernel's; "
+                             "predict, predict_joint and loss_and_grads are" % what)
+
+    def _matern_params(self, params, x, fast=None, training=False):
+        """what the Matern-5/2 entries are not built for, refused on the parameters and switches alone, before any device work; returns
+        the parameters with raw_lengthscale as [1, d] (a scalar lengthscale: d equal entries)"""
+        no = lambda what: ValueError("%s is not built for the Matern-5/2 kernel (kernel = 'matern52')" % what)
+        if "natural_vec" in params:
+            raise no("the natural parameterisation")
+        d = params["inducing_points"].shape[1]
+        rl = params["raw_lengthscale"]
+        if rl.numel() not in (1, d):
+            raise ValueError("Matern-5/2: raw_lengthscale must have 1 entry or one per input dimension (%d), got %d" % (d, rl.numel()))
+        if params["inducing_points"].dtype != f32 or x.dtype != f32 or type(self) is not ElboEngine:
+            raise no("a float64 engine")
+        if self.whitening == "ciq":
+            raise no("CIQ whitening")
+        if self.shared_directions:
+            raise no("the shared-directions strategy")
+        if self.data_outputs == "values":
+            raise no("the derivative-free strategy")
+        coll = self.collective
+        if coll is not None and coll.world > 1:
+            raise no("a collective with world = %d" % coll.world)
+        if self.capture_mode:
+            raise no("graph capture (capture_mode)")
+        if training:
+            if self.deterministic:
+                raise no("the deterministic mode")
+            if fast:
+                raise no("the Gram fast path (fast=True)")
+        if rl.numel() == d and rl.dim() == 2:
+            return params
+        return dict(params, raw_lengthscale=rl.reshape(1, -1).expand(1, d).contiguous())
 
     def _potrf_scratch(self, name, n):
         """Cholesky scratch of ONE factor of THIS engine (``name``: kzz / ngd_P / ngd_LS / root).  It keeps the inverted
@@ -781,7 +835,8 @@ class ElboEngine:
         if self._train_pd is not None:                   # rectangular training step: (p + 1) x (pd + 1) micro-blocks, one launch
             pd = self._train_pd
             ev = self._event_pair()
-            Kzx = _ops.kernel_fwd_rect(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, B * (pd + 1)), f32))
+            fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
+            Kzx = fwd(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, B * (pd + 1)), f32))
             self._event_done("assemble_fwd", ev)
             return Kzx
         if self.data_outputs == "values" and p > 0:
@@ -826,6 +881,8 @@ class ElboEngine:
 
     def _kernel_bwd_zx_bytes(self, M, B, d, p):
         """workspace bytes of ``_kernel_bwd_zx``"""
+        if self._matern:
+            return _ops.kernel_bwd_matern52_workspace_bytes(M, p, B, self._train_pd, d)
         if self._ard:
             return _ops.kernel_bwd_ard_workspace_bytes(M, p, B, self._train_pd, d)
         if self._train_pd is not None:
@@ -836,8 +893,9 @@ class ElboEngine:
         if self._train_pd is not None:                   # rectangular training step: the upstream [M', B(pd+1)] as it is
             ev = self._event_pair()
             if self._ard:                                # d_ell through both sides' packed rows; the data side gets no point gradient
-                _ops.kernel_bwd_ard(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, self._ard_ell, hyp, False, dZ,
-                                    dV if p > 0 else None, self._ard_d_ell, d_hyp, kws)
+                bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
+                bwd(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, self._ard_ell, hyp, False, dZ, dV if p > 0 else None,
+                    self._ard_d_ell, d_hyp, kws)
             else:
                 _ops.kernel_bwd_rect(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, hyp, dZ, dV, d_hyp, kws)
             self._event_done("assemble_bwd", ev)
@@ -872,7 +930,8 @@ class ElboEngine:
             else:
                 packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, hyp, self.center)
             self._zx_dirs = None
-            Kzx = _ops.kernel_fwd_rect(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, Bp), f32))
+            fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
+            Kzx = fwd(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, Bp), f32))
         A64 = self._get("A64", (Mp, Bp), f64)
         A32 = self._get("A32", (Mp, Bp), f32)
         need = _lib.lib.dsvgp_trsm_workspace_bytes(Mp, max(Bp, Mp), self.trsm_nb)
@@ -901,7 +960,8 @@ class ElboEngine:
             # predictive_stats priced the prior diagonal as s [1, 1 / ell^2] with ell = hyp[0] = 1: s on every column.  The ARD
             # kernel's is s [1, |v~_jb|^2] (dsvgp_kernel_diag_ard): add s (|v~_jb|^2 - 1) on the derivative columns (exactly 0 on the
             # value columns, where the diagonal is s itself)
-            self._ard_diag = _ops.kernel_diag_ard(ctx, packX, B, pd, d, hyp)
+            # (Matern-5/2: s [1, (5/3) |v~_jb|^2], dsvgp_kernel_diag_matern52)
+            self._ard_diag = (_ops.kernel_diag_matern52 if self._matern else _ops.kernel_diag_ard)(ctx, packX, B, pd, d, hyp)
             var.add_(self._ard_diag - hyp[1])
         return packX, A64, A32, W, mu, var
 
@@ -911,6 +971,8 @@ class ElboEngine:
         """q(f) mean / variance plus likelihood noise: what ``likelihood(model(x)).mean/.variance`` returns.
         ``cache=True`` (eval mode) keeps the Cholesky factor and its inverted blocks across calls while the
         parameters are unchanged, like the reference's ``@cached`` ``_cholesky_factor`` (DGVS.py:72)."""
+        if self._is_matern():
+            return self._predict_matern(params, x, D, cache, False)
         if self._is_ard(params):
             return self._predict_ard(params, x, D, cache, False)
         ctx = _ops.Context.get(self.device)
@@ -938,6 +1000,7 @@ class ElboEngine:
         directional_vi.py:256-258) -- from the A = L^-1 K_ZX that step left in its workspace: W = L_S^T A[:, ::p+1] is one
         triangular [M', M'] x [M', B] fp32 product (1/(p+1) of the per-output path's W, and none of its U / per-output backward).
         Valid until the parameters change or the next step is queued: the training loop calls it BEFORE the optimizers step."""
+        self._no_matern("value_variances (the ELBO fast path)")
         lf = getattr(self, "_last_fast", None)
         if lf is None or "chol_variational_covar" not in params:
             raise RuntimeError("value_variances needs an ELBO fast-path step of the Cholesky-whitened strategy queued last")
@@ -969,6 +1032,8 @@ class ElboEngine:
         MultivariateNormal behind ``likelihood(model(x, derivative_directions=D))`` (reference DGVS.py:199-208), which the
         BO drivers sample jointly (experiments/GNN_bo/gcn_turbo.py:238-239).
         Sigma = s K_XX + 1e-4 I + W^T W - A^T A + noise I: one symmetric kernel assembly and two MFMA Gram products."""
+        if self._is_matern():
+            return self._predict_matern(params, x, D, cache, True)
         if self._is_ard(params):
             return self._predict_ard(params, x, D, cache, True)
         ctx = _ops.Context.get(self.device)
@@ -998,6 +1063,7 @@ class ElboEngine:
         point -- the diagonal blocks of ``predict_joint``'s Sigma without K_XX, the two Gram products or anything of size B' x B'
         (csrc/predict_blocks.hip).  Everything up to A = L^-1 K_ZX and W = L_S^T A is ``predict``'s, evaluation cache included, so any
         direction count per data point goes (``D`` None: [B, 1, 1], the variances)."""
+        self._no_matern("predict_blocks (and the block roots built on it)")
         self._no_ard(params, "predict_blocks (and the block roots built on it)")
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
@@ -1024,6 +1090,7 @@ class ElboEngine:
         ``_factor`` (jitter ladder included), packed with the inducing set by dsvgp_mean_prepare.  Natural parameters, shared
         directions, p = 0 (plain SVGP) and p = d (full-gradient SVGP) are the same code.  The factorisation runs in the engine's
         factor buffers, so the evaluation cache of ``predict`` is dropped (it refactors on its next call)."""
+        self._no_matern("mean_predictor")
         self._no_ard(params, "mean_predictor")
         if self.whitening == "ciq":
             raise NotImplementedError("posterior-mean predictor with CIQ whitening: alpha there is K^{-1/2} m by msMINRES "
@@ -1061,6 +1128,7 @@ class ElboEngine:
         absent: drawn on the device with ``generator``.  The factor is ``_factor``'s (jitter ladder included); Phi_Z' and the two
         solves run in float64 once per call, dsvgp_paths_prepare packs the fp32 weights.  Natural parameters, shared directions, p = 0
         and p = d are the same code; the evaluation cache of ``predict`` is dropped (it refactors on its next call)."""
+        self._no_matern("sample_paths (and thompson_step, hvp / descend on the paths)")
         self._no_ard(params, "sample_paths (and hvp / descend on the paths)")
         if self.whitening == "ciq":
             raise NotImplementedError("pathwise posterior samples with CIQ whitening: nu there needs K^{-1/2} by msMINRES "
@@ -1131,6 +1199,7 @@ class ElboEngine:
         (fp64 throughout, like the reference's ``.double()`` solves).  The reference evaluates the prior p(u) through
         ``self(inducing_points, prior=True)`` WITHOUT direction kwargs, which its directional kernel cannot take: the
         model's own inducing directions are used here, the evident intent.  Returns (m_w fp32, L_w fp32 lower)."""
+        self._no_matern("whiten_legacy")
         self._no_ard(params, "whiten_legacy")
         ctx = _ops.Context.get(self.device)
         self._eval_cache = None
@@ -1154,6 +1223,7 @@ class ElboEngine:
     @torch.no_grad()
     def prior_moments(self, params):
         """p(u) = N(c 1, s K(Z, Z; V, V)) at the inducing points, un-jittered, fp32: ``strategy(Z, prior=True)``"""
+        self._no_matern("prior_moments")
         self._no_ard(params, "prior_moments")
         ctx = _ops.Context.get(self.device)
         Z, V = params["inducing_points"], params["inducing_directions"]
@@ -1231,6 +1301,19 @@ class ElboEngine:
         finally:
             self._ard = False
 
+    def _predict_matern(self, params, x, D, cache, joint):
+        """predict / predict_joint with kernel = "matern52": ``_predict_ard``'s path on the Matern kernels (csrc/assemble_matern.hip).
+        The evaluation cache is keyed on the caller's parameters (a scalar lengthscale is expanded per call) and on the kernel."""
+        expanded = self._matern_params(params, x)
+        ctx = _ops.Context.get(self.device)
+        self._ard = self._matern = True
+        self._cache_key_params = params
+        try:
+            return self._predict_chol(ctx, expanded, x, D, cache, joint=joint)
+        finally:
+            self._ard = self._matern = False
+            self._cache_key_params = None
+
     def _predict_chol(self, ctx, params, x, D, cache, joint=False, blocks=False):
         # (the parameters arrive expanded; the evaluation cache below is keyed on them alone: calls with different direction
         #  counts on an unchanged model share the factor)
@@ -1238,6 +1321,8 @@ class ElboEngine:
         if self._ard and rect_pd is None:               # ARD: always the rectangular assembly, equal counts included
             rect_pd = self._direction_counts(params, x, D)[1]
         key = tuple((t.data_ptr(), t._version) for t in params.values()) if cache else None
+        if cache and self._matern:
+            key = ("matern52",) + tuple((t.data_ptr(), t._version) for t in self._cache_key_params.values())
         hit = cache and self._eval_cache is not None and self._eval_cache[0] == key
         if "natural_vec" in params:
             if hit:
@@ -1264,7 +1349,9 @@ class ElboEngine:
             B = x.shape[0]
             if rect_pd is not None:
                 p = rect_pd                                                        # (the data pack was made with it)
-            if self._ard:                                                          # (its diagonal is s [1, |v~|^2] by itself)
+            if self._matern:
+                Sigma = _ops.kernel_fwd_matern52(ctx, packX, B, p, packX, B, p, d, hyp)
+            elif self._ard:                                                        # (its diagonal is s [1, |v~|^2] by itself)
                 Sigma = _ops.kernel_fwd_wide(ctx, packX, B, packX, B, d, p, hyp)
             else:
                 Sigma = _ops.kernel_fwd(ctx, packX, B, packX, B, d, p, hyp)        # s K(X, X; D, D), all (p+1)^2 blocks
@@ -1285,6 +1372,8 @@ class ElboEngine:
         ``include_kl=False`` leaves the (replicated) KL term out so exactly one rank adds it.
         ``fast`` (default ``self.elbo_fast``): in ELBO mode use the Gram-matrix formulation, which does not
         produce per-output variances (``varn`` is then an empty tensor; ``predict`` gives them on demand)."""
+        if self._is_matern():
+            return self._loss_and_grads_matern(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
         if self._is_ard(params):
             return self._loss_and_grads_ard(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
         train_pd = self._train_rect_pd(params, x, D)       # (refusals first: shapes only, no device work)
@@ -1318,6 +1407,31 @@ class ElboEngine:
             return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, False)
         finally:
             self._ard, self._train_pd, self._ard_d_ell, self._ard_diag = False, None, None, None
+
+    def _loss_and_grads_matern(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
+        """The step with kernel = "matern52": ``_loss_and_grads_ard``'s path (ELBO or PLL, piecewise per-output, any number of data
+        directions) with the Matern forward for K_ZZ / K_ZX, dsvgp_kernel_bwd_matern52 for K_ZX-bar / K_ZZ-bar and the Matern prior
+        diagonal.  A scalar raw_lengthscale [1, 1]: its gradient is the sum of the [1, d] gradient (one fixed-shape reduction)."""
+        expanded = self._matern_params(params, x, fast=fast, training=True)
+        if mll_type not in ("ELBO", "PLL"):
+            raise ValueError(mll_type)
+        p, pd = self._direction_counts(expanded, x, D)
+        if pd > 95:
+            raise ValueError("at most 95 derivative directions per data point, got %d" % pd)
+        B = x.shape[0]
+        if y.shape != (B * (pd + 1),):
+            raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % (B * (pd + 1)))
+        self._ard, self._matern, self._train_pd = True, True, pd
+        self._ard_d_ell = torch.zeros(x.shape[1], dtype=f32, device=self.device)
+        try:
+            loss, grads, mu, varn = self._loss_and_grads_checked(expanded, x, y, D, num_data, mll_type, global_rows, include_kl, False)
+        finally:
+            self._ard, self._matern, self._train_pd, self._ard_d_ell, self._ard_diag = False, False, None, None, None
+        g, rl = grads["raw_lengthscale"], params["raw_lengthscale"]
+        if rl.numel() != g.numel():                      # scalar lengthscale: d equal entries went in
+            g = g.sum(dim=-1, keepdim=True)
+        grads["raw_lengthscale"] = g.reshape(rl.shape)
+        return loss, grads, mu, varn
 
     def _loss_and_grads_checked(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
         ctx = _ops.Context.get(self.device)
@@ -2079,7 +2193,8 @@ class ElboEngine:
 
         dZ, dV = grads["inducing_points"], grads["inducing_directions"]
         kws = self._bytes("kbwd_ws", max(self._kernel_bwd_zx_bytes(M, B, d, p),
-                                         _ops.kernel_bwd_ard_workspace_bytes(M, p, M, p, d) if self._ard
+                                         _ops.kernel_bwd_matern52_workspace_bytes(M, p, M, p, d) if self._matern
+                                         else _ops.kernel_bwd_ard_workspace_bytes(M, p, M, p, d) if self._ard
                                          else _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, M, d, p)))
         # K_ZX-bar's kernel backward (HBM-bound read of 4 M' B' bytes) next to the fp64 products of L-bar and the Cholesky backward
         # (matrix-pipe bound): on the side stream from the moment the dense product is done, joined before the K_ZZ kernel backward
@@ -2119,8 +2234,9 @@ class ElboEngine:
             if zx_done is not None:
                 torch.cuda.current_stream(self.device).wait_event(zx_done)
             if self._ard:
-                _ops.kernel_bwd_ard(ctx, Kzzbar, packZ, M, p, packZ, M, p, d, self._ard_ell, hyp, True, dZ, dV if p > 0 else None,
-                                    self._ard_d_ell, d_hyp, kws)
+                bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
+                bwd(ctx, Kzzbar, packZ, M, p, packZ, M, p, d, self._ard_ell, hyp, True, dZ, dV if p > 0 else None, self._ard_d_ell, d_hyp,
+                    kws)
             else:
                 _ops.kernel_bwd(ctx, Kzzbar, packZ, M, packZ, M, d, p, hyp, True, dZ, dV, d_hyp, kws)
 
@@ -2128,7 +2244,8 @@ class ElboEngine:
             # the prior diagonal of the data: likelihood_terms priced it as s [1, 1 / ell^2] at ell = hyp[0] = 1 (scal[3] = sum of
             # var_bar, scal[4] the scalar lengthscale's share).  Both are replaced by the ARD diagonal's own backward -- d_hyp[1] +=
             # sum var_bar diag / s, d_ell[k] += -(2 s / ell_k) sum var_bar v~_k^2 -- and the scalar lengthscale slot stays empty
-            _ops.kernel_diag_ard_bwd(ctx, packX, B, pd, d, self._ard_ell, hyp, self._ard_diag, var_bar, self._ard_d_ell, d_hyp)
+            diag_bwd = _ops.kernel_diag_matern52_bwd if self._matern else _ops.kernel_diag_ard_bwd
+            diag_bwd(ctx, packX, B, pd, d, self._ard_ell, hyp, self._ard_diag, var_bar, self._ard_d_ell, d_hyp)
             scal[3:5].zero_()
             _ops.hyp_backward_ard(ctx, params["raw_lengthscale"].reshape(-1), params["raw_outputscale"].reshape(-1),
                                   params["raw_noise"].reshape(-1), self._ard_d_ell, torch.zeros(4, dtype=f32, device=dev),

@@ -68,6 +68,7 @@ class ElboEngine64(ElboEngine):
     def _refuse_rect(self, params, x, D):
         """float64 models predict with the model's own number of directions per data point: the rectangular assembly
         (csrc/assemble_wide.hip, ElboEngine.predict) is a float32 kernel"""
+        self._no_matern("a float64 engine")
         self._no_ard(params, "a float64 engine")
         p, pd =self._direction_counts(params, x, D, self.shared_directions)
         if pd != p:
@@ -424,6 +425,7 @@ class ElboEngine64(ElboEngine):
     def loss_and_grads(self, params, x, y, D, num_data, mll_type="ELBO", global_rows=None, include_kl=True, fast=None):
         """(loss, grads dict, mu, varn), all fp64; see ``ElboEngine.loss_and_grads`` for the arguments.  With natural parameters
         (``natural_vec``, ``natural_mat``) the gradients of those two slots are the expectation-parameter gradients NGD steps along."""
+        self._no_matern("a float64 engine")
         self._no_ard(params, "a float64 engine")
         if self.data_outputs != "values":
             p, pd = self._direction_counts(params, x, D, self.shared_directions)

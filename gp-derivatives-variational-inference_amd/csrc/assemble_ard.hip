@@ -351,10 +351,10 @@ extern "C" int dsvgp_kernel_bwd_ard_slabs(int n1, int p1, int n2, int p2, int d)
     return ard_bwd_plan(n1, p1, n2, p2, d, a) ? 0 : a.ns;
 }
 
-extern "C" int dsvgp_kernel_bwd_ard(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
-                                    const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
-                                    const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell,
-                                    float* d_hyp, void* workspace) {
+int kernel_bwd_ard_family(dsvgp_ctx* ctx, int family, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
+                          const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
+                          const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell, float* d_hyp,
+                          void* workspace) {
     if (!ctx || !G || !P1 || !self1 || !P2 || !self2 || !ell || !hyp || !d_x1 || !d_hyp || !workspace) return DSVGP_EINVAL;
     if (d_v1 && !vnorm1) return DSVGP_EINVAL;
     if (d < 1 || p1 < 0 || p2 < 0 || p1 + 1 > AQMAX || p2 + 1 > AQMAX || n1 < 0 || n2 < 0) return DSVGP_EINVAL;
@@ -368,9 +368,11 @@ extern "C" int dsvgp_kernel_bwd_ard(dsvgp_ctx* ctx, const void* G, int64_t ldg, 
     const int DP = dsvgp_packed_width(d), K4 = DP - 4, NP = (DP + 15) & ~15;
     float *slab, *partials, *TB;
     int ns, nparts;
-    // launches 1 and 2 of dsvgp_kernel_bwd_rect; the scalar lengthscale partial (partials[2 j + 1]) is not read
-    if (int rc = launch_kernel_bwd_rect_tiles(ctx->stream, G, ldg, g_is_double, P1, self1, n1, p1, P2, self2, n2, p2, d, hyp, workspace, &slab,
-                                              &ns, &partials, &nparts, &TB))
+    // launches 1 and 2 of dsvgp_kernel_bwd_rect (or the Matern family's Tbar tiles in place of launch 1); the scalar lengthscale partial
+    // (partials[2 j + 1]) is not read
+    if (int rc = (family ? launch_kernel_bwd_matern52_tiles : launch_kernel_bwd_rect_tiles)(ctx->stream, G, ldg, g_is_double, P1, self1, n1, p1,
+                                                                                            P2, self2, n2, p2, d, hyp, workspace, &slab, &ns,
+                                                                                            &partials, &nparts, &TB))
         return rc;
     float* cs = (float*)((char*)workspace + a.cs_off);
     float* E = (float*)((char*)workspace + a.e_off);
@@ -390,4 +392,12 @@ extern "C" int dsvgp_kernel_bwd_ard(dsvgp_ctx* ctx, const void* G, int64_t ldg, 
     hipLaunchKernelGGL(ard_reduce_kernel, dim3(nk + 1), dim3(ANT), 0, ctx->stream, E, erows, d, nk, ell, partials, nparts, hyp, d_ell, d_hyp);
     DSVGP_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int dsvgp_kernel_bwd_ard(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
+                                    const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
+                                    const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell,
+                                    float* d_hyp, void* workspace) {
+    return kernel_bwd_ard_family(ctx, 0, G, ldg, g_is_double, P1, self1, vnorm1, n1, p1, P2, self2, n2, p2, d, ell, hyp, symmetric, d_x1,
+                                 d_v1, d_ell, d_hyp, workspace);
 }

@@ -441,6 +441,38 @@ int launch_kernel_bwd_rect_tiles(hipStream_t st, const void* G, int64_t ldg, int
     return 0;
 }
 
+// the same tiles and contraction for another kernel family's tile kernels (assemble_matern.hip): the geometry and dynamic LDS of the forward
+// (backward = false: this file's forward tiles) or of the rectangular backward (its capped tiles, slab cut and workspace layout), and the
+// contraction launch by itself.  Refusals are those of dsvgp_kernel_fwd_rect / rect_bwd_plan.
+int kernel_rect_tiles_geometry(int n1, int p1, int n2, int p2, int d, bool backward, RectTilesGeom* g) {
+    if (n1 <= 0 || n2 <= 0 || d < 1 || p1 < 0 || p2 < 0 || p1 + 1 > WTMAX || p2 + 1 > WTMAX) return DSVGP_EINVAL;
+    g->q1 = p1 + 1; g->q2 = p2 + 1;
+    if ((int64_t)n1 * g->q1 > INT_MAX || (int64_t)n2 * g->q2 > INT_MAX || d > INT_MAX - 64) return DSVGP_EINVAL;
+    g->n1q = n1 * g->q1; g->n2q = n2 * g->q2;
+    g->DP = dsvgp_packed_width(d); g->K4 = g->DP - 4; g->NP = (g->DP + 15) & ~15;
+    TilePlan t;
+    if (backward) {
+        RectBwdPlan r;
+        if (int rc = rect_bwd_plan(n1, p1, n2, p2, d, r)) return rc;
+        t = r.w.t;
+        g->ns = r.w.ns; g->kper = r.w.kper; g->nparts = r.w.nparts; g->slab_f = r.w.slab_f; g->part_f = r.w.part_f;
+    } else {
+        t = tile_plan(g->q1, g->q2, false);
+        g->ns = g->kper = g->nparts = 0; g->slab_f = g->part_f = 0;
+    }
+    g->Rr = t.Rr; g->Rc = t.Rc; g->lds_fwd = t.lds_fwd; g->lds_tbar = t.lds_tbar;
+    g->gx = cdiv(g->n2q, t.Tc); g->gy = cdiv(g->n1q, t.Tr);
+    if (g->gy > 65535) return DSVGP_EINVAL;
+    return 0;
+}
+int launch_kernel_bwd_contract(hipStream_t st, const float* TB, const RectTilesGeom& g, const float* P2, float* slab) {
+    if (g.ns < 1 || g.ns > 65535) return DSVGP_EINVAL;
+    hipLaunchKernelGGL(kernel_bwd_wide_contract_kernel, dim3(cdiv(g.NP, CN), cdiv(g.n1q, CM), g.ns), dim3(WNT), 0, st, TB, g.n1q, g.n2q, P2,
+                       g.DP, g.NP, g.kper, slab);
+    DSVGP_LAUNCH_CHECK();
+    return 0;
+}
+
 extern "C" int dsvgp_kernel_bwd_rect(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
                                      const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
                                      const float* hyp, float* d_x1, float* d_v1, float* d_hyp, void* workspace) {

@@ -27,6 +27,7 @@ import torch.distributed as dist
 from . import _ops
 from .CiqDirectionalGradVariationalStrategy import CiqDirectionalGradVariationalStrategy
 from .DirectionalGradVariationalStrategy import DirectionalGradVariationalStrategy
+from .Matern52KernelDirectionalGrad import Matern52KernelDirectionalGrad
 from .RBFKernelDirectionalGrad import RBFKernelDirectionalGrad
 from .gp_shim import (ApproximateGP, CholeskyVariationalDistribution, ConstantMean, GaussianLikelihood,
                       NaturalVariationalDistribution, PredictiveLogLikelihood, ScaleKernel, VariationalELBO)
@@ -39,6 +40,8 @@ class GPModel(ApproximateGP):
     def __init__(self, inducing_points, inducing_directions, dim, learn_inducing_locations=True, ard_num_dims=None, **kwargs):
         # ``ard_num_dims`` (int, not in the reference; None = one scalar lengthscale): one lengthscale per input dimension,
         # raw_lengthscale [1, ard_num_dims] under the same state_dict key, as gpytorch's RBFKernel(ard_num_dims=)
+        # ``kernel`` (through **kwargs, like ``variational_strategy``; "rbf" by default): "matern52" builds the model on
+        # Matern52KernelDirectionalGrad -- gpytorch's MaternKernel(nu=2.5, ard_num_dims=) -- with the same parameters under the same keys
         torch.nn.Module.__init__(self)
         self.num_inducing = len(inducing_points)
         self.num_directions = int(len(inducing_directions) / self.num_inducing)  # num directions per point
@@ -64,7 +67,13 @@ class GPModel(ApproximateGP):
         self.mean_module = ConstantMean()
         if ard_num_dims is not None and int(ard_num_dims) != int(dim):
             raise ValueError("ard_num_dims must equal the input dimension (%d), got %s" % (dim, ard_num_dims))
-        self.covar_module = ScaleKernel(RBFKernelDirectionalGrad(ard_num_dims=ard_num_dims))
+        kernel = kwargs.get("kernel", "rbf")
+        if kernel not in ("rbf", "matern52"):
+            raise ValueError("kernel must be 'rbf' or 'matern52', got %r" % (kernel,))
+        if kernel == "matern52" and (self._ciq or kwargs.get("variational_distribution") == "NGD"):
+            raise ValueError("the Matern-5/2 kernel is built for the Cholesky-whitened model (not CIQ / natural parameters)")
+        kernel_class = Matern52KernelDirectionalGrad if kernel == "matern52" else RBFKernelDirectionalGrad
+        self.covar_module = ScaleKernel(kernel_class(ard_num_dims=ard_num_dims))
         if self._ciq:
             # stable initialization of lengthscale for CIQ (:58-60): lengthscale = 1 / num_inducing through the
             # inverse of the softplus constraint
@@ -78,6 +87,7 @@ class GPModel(ApproximateGP):
         eng.whitening = "ciq" if self._ciq else "cholesky"
         eng.data_outputs = "all"
         eng.shared_directions = False
+        eng.kernel = "matern52" if isinstance(self.covar_module.base_kernel, Matern52KernelDirectionalGrad) else "rbf"
         return eng
 
     # --- parameter plumbing for the HIP engine (order = _step.PARAM_NAMES) ---
@@ -474,8 +484,10 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
                    num_epochs=1, learning_rate_hypers=0.01, inducing_data_initialization=True, lr_sched=None,
                    mll_type="ELBO", gamma=0.1, fixed_inducing_locations=None, seed=None, tensors=None,
                    use_ngd=False, learning_rate_ngd=0.1, use_ciq=False, num_contour_quadrature=15, model_class=None,
-                   dfree=False, shared=False, data_directions=None, ard_num_dims=None):
+                   dfree=False, shared=False, data_directions=None, kernel="rbf", ard_num_dims=None):
     """Everything ``train_gp`` does before its loop (directional_vi.py:130-219); returns a TrainLoop.
+    ``kernel`` ("rbf", the default, or "matern52"): the covariance family -- Matern-5/2 (scalar lengthscale, or ARD with
+    ``ard_num_dims``) runs the engine's Matern step: Cholesky-whitened per-point model, float32, one rank.
     ``ard_num_dims`` (int, default None = one scalar lengthscale): one lengthscale per input dimension (must equal the input
     dimension) -- the engine's ARD step: Cholesky-whitened per-point model, float32, one rank.
     ``data_directions`` (int, default None = ``num_directions``): derivative columns of y per minibatch point, whatever the number of
@@ -489,6 +501,15 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
             raise ValueError("data_directions runs on one rank (dp): the rectangular training step is not built for a collective")
         if torch.get_default_dtype() == torch.float64 or (tensors is not None and tensors[0].dtype == torch.float64):
             raise ValueError("data_directions with a float64 dataset: the rectangular kernel backward is built in float32 only")
+    if kernel not in ("rbf", "matern52"):
+        raise ValueError("kernel must be 'rbf' or 'matern52', got %r" % (kernel,))
+    if kernel == "matern52":
+        if dfree or shared or use_ciq or use_ngd:
+            raise ValueError("dfree / shared / CIQ / NGD training is not built for the Matern-5/2 kernel (kernel='matern52')")
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("a collective with world > 1 is not built for the Matern-5/2 kernel (kernel='matern52')")
+        if torch.get_default_dtype() == torch.float64 or (tensors is not None and tensors[0].dtype == torch.float64):
+            raise ValueError("a float64 dataset is not built for the Matern-5/2 kernel (kernel='matern52'): the Matern kernels are float32")
     if ard_num_dims is not None:
         if dfree or shared or use_ciq or use_ngd:
             raise ValueError("dfree / shared / CIQ / NGD training is not built for ARD lengthscales (ard_num_dims)")
@@ -528,9 +549,11 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
     elif use_ngd:                                                         # :166-167
         model = model_class(inducing_points, inducing_directions, dim, variational_distribution="NGD",
                             learn_inducing_locations=learn_inducing_locations)
-    elif ard_num_dims is not None:
-        model = model_class(inducing_points, inducing_directions, dim, learn_inducing_locations=learn_inducing_locations,
-                            ard_num_dims=int(ard_num_dims))
+    elif ard_num_dims is not None or kernel != "rbf":
+        extra = {} if kernel == "rbf" else {"kernel": kernel}
+        if ard_num_dims is not None:
+            extra["ard_num_dims"] = int(ard_num_dims)
+        model = model_class(inducing_points, inducing_directions, dim, learn_inducing_locations=learn_inducing_locations, **extra)
     else:
         model = model_class(inducing_points, inducing_directions, dim,
                             learn_inducing_locations=learn_inducing_locations)
@@ -622,7 +645,8 @@ def train_gp(train_dataset, num_inducing=128,
       ``seed`` (int): seeds the minibatch permutation and the derivative-column sampling (must be equal
       on all ranks under torch.distributed; broadcast from rank 0 when omitted);
       ``max_steps`` (int): stop after this many optimisation steps;
-      ``ard_num_dims`` (int, the input dimension): one lengthscale per input dimension (``setup_training``).
+      ``ard_num_dims`` (int, the input dimension): one lengthscale per input dimension (``setup_training``);
+      ``kernel`` ("rbf" or "matern52"): the covariance family (``setup_training``).
     """
     assert num_directions == minibatch_dim
     loop = setup_training(train_dataset, num_inducing, num_directions, minibatch_size, minibatch_dim, num_epochs,
@@ -630,7 +654,8 @@ def train_gp(train_dataset, num_inducing=128,
                           fixed_inducing_locations, seed=args.get("seed"), use_ngd=use_ngd,
                           learning_rate_ngd=learning_rate_ngd, use_ciq=use_ciq,
                           num_contour_quadrature=num_contour_quadrature, model_class=args.get("_model_class"),
-                          shared=bool(args.get("_shared")), data_directions=data_directions, ard_num_dims=args.get("ard_num_dims"))
+                          shared=bool(args.get("_shared")), data_directions=data_directions, kernel=args.get("kernel", "rbf"),
+                          ard_num_dims=args.get("ard_num_dims"))
     n_samples = loop.X.shape[0]
     stride = (num_directions if loop.data_directions is None else loop.data_directions) + 1      # outputs per minibatch point
     max_steps = args.get("max_steps")

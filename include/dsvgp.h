@@ -213,6 +213,38 @@ int dsvgp_kernel_bwd_ard(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_do
                          const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
                          const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell, float* d_hyp,
                          void* workspace);
+/* ---- Matern-5/2 with directional derivatives (csrc/assemble_matern.hip) -------------------------------------------------------------
+ * The second kernel family, on the ARD packs above (dsvgp_pack_points_ard; a scalar lengthscale is ell[d] with equal entries) and
+ * dsvgp_hyp_forward_ard's hyp (hyp[0] = 1 is not read).  With r = x~1 - x~2, nn = |r|^2, a = sqrt(5 nn), e = exp(-a) and
+ *   f0 = (1 + a + a^2/3) e,  f1 = (5/3)(1 + a) e,  f2 = (25/3) e
+ * micro-block (i, j) is s [[f0, f1 w~_b], [-f1 u~_a, f1 v~_a.v~_b - f2 u~_a w~_b]] (u~_a = r.v~1_a, w~_b = r.v~2_b); the RBF kernel is the
+ * case f0 = f1 = f2 = exp(-nn/2).  All entries: fixed summation orders, no floating-point atomics, two identical calls are bitwise equal.
+ *
+ * dsvgp_kernel_fwd_matern52: out[n1*(p1+1), n2*(p2+1)] (float, or double when out_is_double), leading dimension ld, `jitter` added on the
+ * global diagonal (row index == column index: pass 0 unless both sides are the same pack -- K_ZZ).  Any d >= 1 and any 0 <= p1, p2 <= 95,
+ * independently; one launch on the tiles of dsvgp_kernel_fwd_rect, every element stored once.  On K_ZZ the value diagonal is s + jitter
+ * exactly.  DSVGP_EINVAL, nothing touched: whatever dsvgp_kernel_fwd_rect refuses, or `out` not aligned to its element size.
+ * dsvgp_kernel_fwd_matern52_lds_bytes: the dynamic LDS of that launch for the direction counts (host arithmetic; 0: refused).        */
+int dsvgp_kernel_fwd_matern52(dsvgp_ctx* ctx, const float* P1, const float* self1, int n1, int p1, const float* P2,
+                              const float* self2, int n2, int p2, int d, const float* hyp, float jitter, void* out, int64_t ld,
+                              int out_is_double);
+size_t dsvgp_kernel_fwd_matern52_lds_bytes(int p1, int p2);
+/* Backward of dsvgp_kernel_fwd_matern52: the arguments, optional pointers, `symmetric`, += semantics, alignment and refusals of
+ * dsvgp_kernel_bwd_ard.  Launches: the Matern Tbar tiles (the LDS of dsvgp_kernel_bwd_rect's Tbar launch), then the contraction and the
+ * points / column-sum / self-rows / reduce launches of dsvgp_kernel_bwd_ard unchanged.  d_hyp[1] += sum(G o K) / s, accumulated
+ * directly per tile.  A pair at distance 0 (K_ZZ's diagonal blocks, duplicate points) contributes finite, exact terms.
+ * workspace: dsvgp_kernel_bwd_matern52_workspace_bytes bytes: dsvgp_kernel_bwd_ard_workspace_bytes (the same layout) rounded up to a
+ * multiple of 16; 0 where that returns 0.                                                                                              */
+size_t dsvgp_kernel_bwd_matern52_workspace_bytes(int n1, int p1, int n2, int p2, int d);
+int dsvgp_kernel_bwd_matern52(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
+                              const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
+                              const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell, float* d_hyp,
+                              void* workspace);
+/* The prior diagonal out[i*(p+1)] = s, out[i*(p+1) + a] = (5/3) s |v~_ia|^2 and its backward: d_hyp[1] += sum gbar out / s,
+ * d_ell[k] += -(2 (5/3) s / ell_k) sum_{i, a >= 1} gbar_ia v~_iak^2.  Signatures and refusals of dsvgp_kernel_diag_ard / _bwd.        */
+int dsvgp_kernel_diag_matern52(dsvgp_ctx* ctx, const float* P, int n, int p, int d, const float* hyp, float* out);
+int dsvgp_kernel_diag_matern52_bwd(dsvgp_ctx* ctx, const float* P, int n, int p, int d, const float* ell, const float* hyp,
+                                   const float* out, const float* gbar, float* d_ell, float* d_hyp);
 /* 1 when dsvgp_kernel_fwd_canon / _bwd_canon take the geometry (d, p), 0 otherwise */
 int dsvgp_kernel_canon_supported(int d, int p);
 /* backward of dsvgp_kernel_fwd_canon (symmetric = 0 semantics; same workspace size as dsvgp_kernel_bwd) */
