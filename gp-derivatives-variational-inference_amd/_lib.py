@@ -220,6 +220,11 @@ SIGNATURES = {
     "dsvgp_paths_eval_own": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
     "dsvgp_paths_descend_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
     "dsvgp_paths_descend": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _i, _f, _i, _i, _p, _p, _p, _p, _p]),
+    "dsvgp_kmeans_workspace_bytes": (_z, [_i, _i, _i]),
+    "dsvgp_kmeans_assign": (_i, [_p, _p, _i, _i, _p, _i, _p, _p, _p]),
+    "dsvgp_kmeans_update": (_i, [_p, _p, _i, _i, _p, _p, _i, _p]),
+    "dsvgp_kmeans_lloyd": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "dsvgp_cluster_moments": (_i, [_p, _p, _i, _i, _p, _i, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1704,3 +1704,102 @@ def mfma_rate2(ctx, is_double=True, one_wave_per_simd=False, millis=40):
     check(lib.dsvgp_mfma_rate2(ctx.h, (1 if is_double else 0) | (2 if one_wave_per_simd else 0), int(millis), _ptr(scratch),
                                C.byref(out), C.byref(burst), C.byref(clk)), "dsvgp_mfma_rate2")
     return out.value, burst.value, clk.value
+
+
+# ---- data-driven initialisation (csrc/kmeans.hip) ---------------------------------------------------------------------------------
+i32 = torch.int32
+
+
+def kmeans_workspace_bytes(N, d, M):
+    return int(lib.dsvgp_kmeans_workspace_bytes(int(N), int(d), int(M)))
+
+
+def _kmeans_xz(x, Z):
+    _req(x, f32, "x", 2)
+    _req(Z, f32, "Z", 2)
+    if not x.is_contiguous() or not Z.is_contiguous() or Z.shape[1] != x.shape[1]:
+        raise ValueError("x [N, d] and Z [M, d] must be contiguous with one d, got %s and %s" % (tuple(x.shape), tuple(Z.shape)))
+    N, d = x.shape
+    M = Z.shape[0]
+    if N < 1 or d < 1 or M < 1 or M > N:
+        raise ValueError("k-means needs 1 <= M <= N and d >= 1, got N = %d, d = %d, M = %d" % (N, d, M))
+    return N, d, M
+
+
+def _kmeans_ws(N, d, M, workspace, device):
+    need = kmeans_workspace_bytes(N, d, M)
+    if d > 32 and need == 0:
+        raise ValueError("k-means at N = %d, d = %d, M = %d: an intermediate would pass 2^31 entries" % (N, d, M))
+    if need and workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    if need and workspace.numel() * workspace.element_size() < need:
+        raise ValueError("k-means workspace too small: %d bytes needed" % need)
+    return workspace if need else None
+
+
+def _kmeans_out(t, dtype, n, name, device):
+    if t is None:
+        return torch.empty(n, dtype=dtype, device=device)
+    _req(t, dtype, name, 1)
+    if t.numel() != n:
+        raise ValueError("%s must have %d entries, got %d" % (name, n, t.numel()))
+    return t
+
+
+def kmeans_assign(ctx, x, Z, labels=None, dist2=None, workspace=None):
+    """(labels int32 [N], dist2 float32 [N]): the nearest centroid of every point and the squared distance to it (dsvgp_kmeans_assign;
+    an exact tie goes to the lowest index).  ``workspace``: uint8 tensor of dsvgp_kmeans_workspace_bytes bytes (allocated when None)."""
+    N, d, M = _kmeans_xz(x, Z)
+    labels = _kmeans_out(labels, i32, N, "labels", x.device)
+    dist2 = _kmeans_out(dist2, f32, N, "dist2", x.device)
+    workspace = _kmeans_ws(N, d, M, workspace, x.device)
+    check(lib.dsvgp_kmeans_assign(ctx.h, _ptr(x), N, d, _ptr(Z), M, _ptr(labels), _ptr(dist2), _ptr(workspace)), "dsvgp_kmeans_assign")
+    return labels, dist2
+
+
+def kmeans_update_(ctx, x, labels, Z, counts=None):
+    """Z[m] <- mean of the rows of x labelled m, in place (an empty cluster keeps its row); returns counts int32 [M] (dsvgp_kmeans_update)"""
+    N, d, M = _kmeans_xz(x, Z)
+    _req(labels, i32, "labels", 1)
+    if labels.numel() != N:
+        raise ValueError("labels must have N = %d entries" % N)
+    counts = _kmeans_out(counts, i32, M, "counts", x.device)
+    check(lib.dsvgp_kmeans_update(ctx.h, _ptr(x), N, d, _ptr(labels), _ptr(Z), M, _ptr(counts)), "dsvgp_kmeans_update")
+    return counts
+
+
+def kmeans_lloyd_(ctx, x, Z, iterations, labels=None, dist2=None, counts=None, inertia=None, moved=None, workspace=None):
+    """``iterations`` Lloyd steps on Z in place and a closing assignment (dsvgp_kmeans_lloyd): returns (labels, dist2, counts, inertia
+    float64 [iterations + 1], moved int32 [iterations]) -- no host read; the caller looks at ``moved`` afterwards if it wants to"""
+    N, d, M = _kmeans_xz(x, Z)
+    iterations = int(iterations)
+    if iterations < 0:
+        raise ValueError("iterations must be >= 0, got %d" % iterations)
+    labels = _kmeans_out(labels, i32, N, "labels", x.device)
+    dist2 = _kmeans_out(dist2, f32, N, "dist2", x.device)
+    counts = _kmeans_out(counts, i32, M, "counts", x.device)
+    inertia = _kmeans_out(inertia, f64, iterations + 1, "inertia", x.device)
+    moved = _kmeans_out(moved, i32, iterations, "moved", x.device)
+    workspace = _kmeans_ws(N, d, M, workspace, x.device)
+    check(lib.dsvgp_kmeans_lloyd(ctx.h, _ptr(x), N, d, _ptr(Z), M, iterations, _ptr(labels), _ptr(dist2), _ptr(counts), _ptr(inertia),
+                                 _ptr(moved if iterations else None), _ptr(workspace)), "dsvgp_kmeans_lloyd")
+    return labels, dist2, counts, inertia, moved
+
+
+def cluster_moments(ctx, g, labels, M, out=None):
+    """C[M, d, d] float64 = sum over the rows of g labelled m of g_i g_i^T (dsvgp_cluster_moments; d <= 128), exactly symmetric"""
+    _req(g, f32, "g", 2)
+    _req(labels, i32, "labels", 1)
+    N, d = g.shape
+    M = int(M)
+    if not g.is_contiguous() or labels.numel() != N:
+        raise ValueError("g must be a contiguous [N, d] tensor with one label per row")
+    if N < 1 or M < 1 or M > N or not 1 <= d <= 128:
+        raise ValueError("cluster moments need 1 <= M <= N and 1 <= d <= 128, got N = %d, d = %d, M = %d" % (N, d, M))
+    if out is None:
+        out = torch.empty(M, d, d, dtype=f64, device=g.device)
+    _req(out, f64, "out", 3)
+    if out.shape != (M, d, d):
+        raise ValueError("out must be [%d, %d, %d]" % (M, d, d))
+    check(lib.dsvgp_cluster_moments(ctx.h, _ptr(g), N, d, _ptr(labels), M, _ptr(out), None), "dsvgp_cluster_moments")
+    return out

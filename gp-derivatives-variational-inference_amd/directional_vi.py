@@ -480,12 +480,38 @@ class TrainLoop:
         self._deferred_check_previous()
 
 
+def _kmeans_start(X, Y, num_inducing, num_directions, seed, dfree, shared):
+    """(inducing points, inducing directions) of ``inducing_data_initialization="kmeans"`` (initialization.py): k-means centroids of X
+    from a CPU generator seeded with ``seed``, and per point the leading eigenvectors of its cluster's gradient second moments
+    (``Y[:, 1:]``); ``shared``: ONE direction set [p, d] from the moments of all gradients as one cluster; value-only targets (dfree)
+    and inputs wider than the moment kernel keep canonical directions"""
+    from . import initialization as _init
+    gen = torch.Generator()
+    if seed is not None:
+        gen.manual_seed(int(seed))
+    else:
+        gen.seed()
+    dim = X.shape[1]
+    has_grad = (not dfree) and Y.dim() == 2 and Y.shape[1] == dim + 1 and dim <= _init.MOMENTS_MAX_DIM
+    if shared:
+        Z = _init.kmeans_inducing_points(X, num_inducing, generator=gen).centroids
+        if has_grad:
+            one = torch.zeros(X.shape[0], dtype=torch.int32, device=X.device)
+            V = _init.gradient_directions(Y[:, 1:], one, 1, num_directions)
+        else:
+            V = torch.eye(dim)[:num_directions]
+        return Z, V.to(X)
+    return _init.initialize_inducing(X, Y if has_grad else None, num_inducing, num_directions, generator=gen)
+
+
 def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_size=1, minibatch_dim=1,
                    num_epochs=1, learning_rate_hypers=0.01, inducing_data_initialization=True, lr_sched=None,
                    mll_type="ELBO", gamma=0.1, fixed_inducing_locations=None, seed=None, tensors=None,
                    use_ngd=False, learning_rate_ngd=0.1, use_ciq=False, num_contour_quadrature=15, model_class=None,
                    dfree=False, shared=False, data_directions=None, kernel="rbf", ard_num_dims=None):
     """Everything ``train_gp`` does before its loop (directional_vi.py:130-219); returns a TrainLoop.
+    ``inducing_data_initialization``: True (the first M data rows), False (uniform draws), or "kmeans" -- k-means centroids and gradient
+    directions from the training tensors (``_kmeans_start``; one rank; ``fixed_inducing_locations`` wins over it).
     ``kernel`` ("rbf", the default, or "matern52"): the covariance family -- Matern-5/2 (scalar lengthscale, or ARD with
     ``ard_num_dims``) runs the engine's Matern step: Cholesky-whitened per-point model, float32, one rank.
     ``ard_num_dims`` (int, default None = one scalar lengthscale): one lengthscale per input dimension (must equal the input
@@ -493,6 +519,11 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
     ``data_directions`` (int, default None = ``num_directions``): derivative columns of y per minibatch point, whatever the number of
     inducing directions (0: function values only; ``dim``: the full gradient) -- the engine's rectangular training step."""
     assert num_directions == minibatch_dim
+    if isinstance(inducing_data_initialization, str):
+        if inducing_data_initialization != "kmeans":
+            raise ValueError("inducing_data_initialization must be True, False or 'kmeans', got %r" % (inducing_data_initialization,))
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("inducing_data_initialization='kmeans' runs on one rank: the start is not replicated across a collective")
     if data_directions is not None:
         data_directions = int(data_directions)
         if dfree or shared or use_ciq:
@@ -530,13 +561,16 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
     n_samples, dim = X.shape
     num_data = (dim + 1) * n_samples                                      # :136
 
-    if inducing_data_initialization is True:
-        inducing_points = X[:num_inducing].clone()                        # first M data rows, :140-145
+    if inducing_data_initialization == "kmeans" and fixed_inducing_locations is None:
+        inducing_points, inducing_directions = _kmeans_start(X, Y, num_inducing, num_directions, seed, dfree, shared)
     else:
-        inducing_points = torch.rand(num_inducing, dim).to(X)             # :149
-    inducing_directions = torch.eye(dim)[:num_directions].repeat(num_inducing, 1).to(X)
-    if shared and inducing_data_initialization is not True:          # shared_directional_vi.py:150-155: not tiled
-        inducing_directions = torch.eye(dim)[:num_directions].to(X)
+        if inducing_data_initialization is True:
+            inducing_points = X[:num_inducing].clone()                        # first M data rows, :140-145
+        else:
+            inducing_points = torch.rand(num_inducing, dim).to(X)             # :149
+        inducing_directions = torch.eye(dim)[:num_directions].repeat(num_inducing, 1).to(X)
+        if shared and inducing_data_initialization is not True:          # shared_directional_vi.py:150-155: not tiled
+            inducing_directions = torch.eye(dim)[:num_directions].to(X)
 
     learn_inducing_locations = True
     if fixed_inducing_locations is not None:
@@ -640,6 +674,9 @@ def train_gp(train_dataset, num_inducing=128,
 
     ``data_directions`` (int, not in the reference; default None = ``num_directions``): every minibatch carries that many derivative
     columns of y per point -- 0: function values only, ``dim``: the full gradient -- whatever the number of inducing directions.
+
+    ``inducing_data_initialization="kmeans"`` (a value the reference does not have): k-means centroids of the inputs as inducing points
+    and the leading eigenvectors of each cluster's gradient second moments as its directions (``setup_training``).
 
     Extra keyword arguments understood through ``**args`` (all optional, ignored by the reference):
       ``seed`` (int): seeds the minibatch permutation and the derivative-column sampling (must be equal

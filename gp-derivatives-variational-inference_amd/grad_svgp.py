@@ -79,14 +79,26 @@ def setup_training(train_dataset, dim, num_inducing=128, minibatch_size=1, num_e
                    learning_rate_hypers=0.01, learning_rate_ngd=0.1, lr_sched=None, mll_type="ELBO", gamma=0.1,
                    tensors=None, **args):
     """Everything ``train_gp`` does before its loop (grad_svgp.py:41-127); returns a TrainLoop (``tensors``: an
-    already-resident (X, Y) pair instead of a Dataset)."""
+    already-resident (X, Y) pair instead of a Dataset; ``inducing_data_initialization="kmeans"`` through ``**args``: k-means centroids
+    of the inputs instead of uniform draws, one rank)."""
     if not torch.cuda.is_available():
         raise RuntimeError("train_gp needs an MI355X (HIP) device: this path has no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())
     X, Y = tensors if tensors is not None else _dataset_tensors(train_dataset, device)
     n_samples = X.shape[0]
 
-    inducing_points = torch.rand(num_inducing, dim).to(X)            # :61
+    start = args.get("inducing_data_initialization")
+    if isinstance(start, str):
+        if start != "kmeans":
+            raise ValueError("inducing_data_initialization must be 'kmeans' when it is a string, got %r" % (start,))
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError("inducing_data_initialization='kmeans' runs on one rank: the start is not replicated across a collective")
+        from .initialization import kmeans_inducing_points
+        gen = torch.Generator()
+        gen.manual_seed(int(args["seed"])) if args.get("seed") is not None else gen.seed()
+        inducing_points = kmeans_inducing_points(X, num_inducing, generator=gen).centroids      # (the directions are the full basis)
+    else:
+        inducing_points = torch.rand(num_inducing, dim).to(X)            # :61
     if use_ciq:                                                           # grad_svgp.py:63-65
         model = GPModel(inducing_points=inducing_points, variational_distribution="NGD", variational_strategy="CIQ").to(X)
         model.engine.ciq_num_quadrature = int(args.get("num_contour_quadrature", 15))

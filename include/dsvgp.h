@@ -917,6 +917,38 @@ int dsvgp_paths_descend(dsvgp_ctx* ctx, const float* weights, int M, int d, int 
                         const float* upper, int iterations, float initial_step, int maximize, int resume, float* values, float* grads,
                         float* steps, int* accepted, void* workspace);
 
+/* ---- data-driven initialisation (csrc/kmeans.hip): k-means for the inducing points, per-cluster second moments of the gradients for the
+ * inducing directions.  Every entry queues on the context's stream: no host read, no allocation, no synchronisation, no floating-point
+ * atomics; two identical calls return identical bits.  Data are fp32 (x[N, d], Z[M, d], dist2), labels and counts int32, sums fp64.
+ *   dsvgp_kmeans_assign   per point the nearest centroid (labels) and the squared distance to it (dist2); an exact tie goes to the lowest
+ *                         centroid index.  d <= 32: ONE fused kernel (a workgroup owns 64 points, lane = point in registers; centroids
+ *                         through LDS in chunks of 64 split over 8 waves; distance in the difference form sum_k (z_k - x_k)^2 by FMAs in
+ *                         the order of k; the waves' winners combined in the order 0..7): the result of a point depends on that point and
+ *                         on Z alone; workspace may be NULL.  Any other d: S = X~ Z~^T on the unsplit fp32 MFMA GEMM in row blocks of
+ *                         32768, X~ and Z~ centred on the column mean of Z, then a row-wise arg-min over |z~|^2 - 2 S (one wave per row,
+ *                         the lower index on equality), dist2 = max(|x~|^2 + min, 0); `workspace`: dsvgp_kmeans_workspace_bytes(N, d, M)
+ *                         bytes, 16-byte aligned (0 for d <= 32).
+ *   dsvgp_kmeans_update   Z[m] <- mean of the rows labelled m (fp64 sums, rounded once); an empty cluster keeps its row and reports
+ *                         count 0.  One workgroup per centroid walks all N labels in order; the order of every sum is fixed by N and
+ *                         `labels` alone.
+ *   dsvgp_kmeans_lloyd    `iterations` times assign -> inertia -> update, then a closing assignment against the final centroids:
+ *                         labels, dist2 and counts[M] (the cluster sizes) belong to that closing assignment; inertia[t] = sum dist2 of
+ *                         assignment t (double, iterations + 1 entries, fixed-order fp64 sum); moved[t] = number of labels that differ
+ *                         between assignments t and t + 1 (int, `iterations` entries; may be NULL when iterations = 0).  The iteration
+ *                         count is fixed: the caller reads `moved` afterwards if it wants to.  iterations = 0 is one assignment.  k calls
+ *                         of one iteration, each resumed from the previous call's Z, return the bits of one call of k.
+ *   dsvgp_cluster_moments C[M, d, d] (double) = sum_{i in m} g_i g_i^T per cluster (uncentred), exactly symmetric; d <= 128; grid
+ *                         (cluster, 32 x 32 tile of the upper triangle), the update's in-order walk; workspace is not used (may be NULL).
+ * DSVGP_EINVAL, with nothing touched: a null required pointer; N, d or M < 1; M > N; iterations < 0; on the composed route a missing or
+ * misaligned workspace or an intermediate that would pass 2^31 entries; d > 128 for the moments.  dsvgp_kmeans_workspace_bytes is a pure
+ * host function (0 for d <= 32 and for arguments the entries refuse).                                                               */
+size_t dsvgp_kmeans_workspace_bytes(int N, int d, int M);
+int dsvgp_kmeans_assign(dsvgp_ctx* ctx, const float* x, int N, int d, const float* Z, int M, int* labels, float* dist2, void* workspace);
+int dsvgp_kmeans_update(dsvgp_ctx* ctx, const float* x, int N, int d, const int* labels, float* Z, int M, int* counts);
+int dsvgp_kmeans_lloyd(dsvgp_ctx* ctx, const float* x, int N, int d, float* Z, int M, int iterations, int* labels, float* dist2,
+                       int* counts, double* inertia, int* moved, void* workspace);
+int dsvgp_cluster_moments(dsvgp_ctx* ctx, const float* g, int N, int d, const int* labels, int M, double* C, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the

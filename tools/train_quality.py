@@ -5,6 +5,7 @@ density of the function values on held-out rows).  GPU box tool; nothing here is
 
   python3 tools/train_quality.py --config c4 --epochs 1 --data welch --out gpurun_out/train_c4.json
   python3 tools/train_quality.py --config c2 --against-oracle 50        # first 50 steps beside oracle/train_ref.py's op sequence
+  python3 tools/train_quality.py --config c4 --epochs 1 --init kmeans    # k-means inducing points, gradient directions (same seed)
 
 ``--data sin``   the bench's synthetic function f = sin(2 pi |x|^2) on the unit cube (tests/testfun.py:4-12 in the reference);
 ``--data welch`` (d = 20 only) the 20-dimensional screening function of Welch et al. (1992) that the reference's experiments use
@@ -68,6 +69,9 @@ def parse(argv=None):
     ap.add_argument("--lr", type=float, default=0.01)
     ap.add_argument("--against-oracle", type=int, default=0,
                     help="C2-sized runs: this many steps beside oracle/train_ref's CPU trainer on IDENTICAL minibatches and columns")
+    ap.add_argument("--init", default="first", choices=["first", "kmeans"],
+                    help="start of the inducing set: the first M training rows and canonical directions (the reference's rule), or k-means "
+                         "centroids and gradient directions (inducing_data_initialization='kmeans')")
     ap.add_argument("--out", default=None)
     ap.add_argument("--eval-batch", type=int, default=4096)
     return ap.parse_args(argv)
@@ -89,15 +93,15 @@ def run(args):
     Yall = torch.cat([((Yall[:, :1] - mu) / sig), Yall[:, 1:] / sig], 1).float().contiguous()
     Xtr, Ytr, Xte, Yte = Xall[:N].contiguous(), Yall[:N].contiguous(), Xall[N:].contiguous(), Yall[N:].contiguous()
 
-    res = dict(workload=cfg["name"], data=kind, n_train=N, n_test=args.n_test, epochs=args.epochs, lr=args.lr,
+    res = dict(workload=cfg["name"], data=kind, init=args.init, n_train=N, n_test=args.n_test, epochs=args.epochs, lr=args.lr,
                minibatch=B, steps_per_epoch=(N + B - 1) // B, ragged_tail_rows=N % B)
 
     if args.against_oracle > 0:
         res["against_oracle"] = against_oracle(dvi, Xtr, Ytr, cfg, args.against_oracle, args.lr)
 
     loop = dsvgp_amd.setup_training(None, num_inducing=M, num_directions=p, minibatch_size=B, minibatch_dim=p,
-                                    num_epochs=args.epochs, learning_rate_hypers=args.lr, inducing_data_initialization=True,
-                                    seed=0, tensors=(Xtr, Ytr))
+                                    num_epochs=args.epochs, learning_rate_hypers=args.lr,
+                                    inducing_data_initialization=True if args.init == "first" else "kmeans", seed=0, tensors=(Xtr, Ytr))
     q = p + 1
     traj = []
     torch.cuda.synchronize()
