@@ -225,6 +225,16 @@ SIGNATURES = {
     "dsvgp_kmeans_update": (_i, [_p, _p, _i, _i, _p, _p, _i, _p]),
     "dsvgp_kmeans_lloyd": (_i, [_p, _p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "dsvgp_cluster_moments": (_i, [_p, _p, _i, _i, _p, _i, _p, _p]),
+    "dsvgp_var_route": (_i, [_i, _i]),
+    "dsvgp_var_chunk": (_i, [_i, _i]),
+    "dsvgp_var_weights_bytes": (_z, [_i, _i, _i]),
+    "dsvgp_var_workspace_bytes": (_z, [_i, _i, _i, _i, _i]),
+    "dsvgp_var_prepare": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "dsvgp_var_predict": (_i, [_p, _p, _p, _l, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "dsvgp_acq_eval": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
+    "dsvgp_acq_descend_workspace_bytes": (_z, [_i, _i, _i, _i]),
+    "dsvgp_acq_descend": (_i, [_p, _p, _p, _p, _l, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _f, _i, _p, _p, _p, _p,
+                               _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1324,6 +1324,150 @@ def paths_descend(ctx, weights, M, d, F, n, x, lower, upper, iterations, initial
     return x
 
 
+ACQ_KINDS = {"lcb_var": 0, "lcb": 1, "ei": 2}
+
+
+def var_route(d, p):
+    """route of dsvgp_var_predict for (d, p): "fused", "composed", or None for arguments it refuses"""
+    return {1: "fused", 2: "composed"}.get(int(lib.dsvgp_var_route(int(d), int(p))))
+
+
+def var_chunk(d, p):
+    """inducing points per LDS chunk of the fused variance kernel (0: the composed route)"""
+    return int(lib.dsvgp_var_chunk(int(d), int(p)))
+
+
+def var_weights_bytes(M, d, p):
+    return int(lib.dsvgp_var_weights_bytes(int(M), int(d), int(p)))
+
+
+def var_workspace_bytes(M, d, p, B, want_grad):
+    return int(lib.dsvgp_var_workspace_bytes(int(M), int(d), int(p), int(B), 1 if want_grad else 0))
+
+
+def acq_descend_workspace_bytes(M, d, p, B):
+    return int(lib.dsvgp_acq_descend_workspace_bytes(int(M), int(d), int(p), int(B)))
+
+
+def var_prepare(ctx, Z, V, p, hyp, center=None, weights=None):
+    """the inducing set -> the packed fp32 weights of the posterior-variance predictor (dsvgp_var_prepare; a float32 tensor of
+    dsvgp_var_weights_bytes(M, d, p) bytes)"""
+    _req(Z, f32, "Z", 2)
+    M, d = Z.shape
+    if p > 0:
+        _req(V, f32, "V", 2)
+        if V.shape != (M * p, d):
+            raise ValueError("directions must be [M*p, d] = [%d, %d], got %s" % (M * p, d, tuple(V.shape)))
+    if not Z.is_contiguous() or (p > 0 and not V.is_contiguous()):
+        raise ValueError("Z and V must be contiguous")
+    if center is not None:
+        _req(center, f32, "center", 1)
+        if center.shape != (d,):
+            raise ValueError("center must have shape [%d]" % d)
+    n = (var_weights_bytes(M, d, p) + 3) // 4
+    if n == 0:
+        raise ValueError("var_prepare: M, d, p = %d, %d, %d is not a shape the entry takes" % (M, d, p))
+    if weights is None:
+        weights = torch.empty(n, dtype=f32, device=Z.device)
+    _req(weights, f32, "weights", 1)
+    if weights.numel() < n:
+        raise ValueError("weights buffer too small: %d < %d floats" % (weights.numel(), n))
+    check(lib.dsvgp_var_prepare(ctx.h, _ptr(Z), _ptr(V if p > 0 else None), M, d, p, _ptr(hyp), _ptr(center), _ptr(weights)),
+          "dsvgp_var_prepare")
+    return weights
+
+
+def _req_var_state(weights, Q, packZ, M, d, p):
+    _req(weights, f32, "weights", 1)
+    _req(Q, f64, "Q", 2)
+    Mp = M * (p + 1)
+    if Q.shape != (Mp, Mp):
+        raise ValueError("Q must be [M (p + 1)]^2 = [%d, %d], got %s" % (Mp, Mp, tuple(Q.shape)))
+    PZ, sZ = packZ[0], packZ[1]
+    _req(PZ, f32, "packZ", 2)
+    _req(sZ, f32, "packZ self terms", 1)
+    if PZ.shape != (Mp, packed_width(d)) or sZ.shape[0] != Mp or not PZ.is_contiguous():
+        raise ValueError("packZ is not the contiguous pack of %d points with %d directions at d = %d" % (M, p, d))
+    return PZ, sZ
+
+
+def var_predict(ctx, weights, Q, packZ, hyp, M, d, p, x, var_out=None, grad_out=None, workspace=None):
+    """var_out [B] = sigma^2 of q(f) at x [B, d] (no likelihood noise) and, when ``grad_out`` [B, d] is given, its gradient
+    (dsvgp_var_predict).  ``Q``: float64 [M', M'], symmetric; ``packZ``: ``pack_points`` of the inducing set with the centre the weights
+    carry.  ``workspace``: uint8 tensor of dsvgp_var_workspace_bytes(M, d, p, B, grad_out is not None) bytes."""
+    PZ, sZ = _req_var_state(weights, Q, packZ, M, d, p)
+    _req(x, f32, "x", 2)
+    B = x.shape[0]
+    if x.shape[1] != d or not x.is_contiguous():
+        raise ValueError("x must be a contiguous [B, %d] tensor, got %s" % (d, tuple(x.shape)))
+    if var_out is None:
+        var_out = torch.empty(B, dtype=f32, device=x.device)
+    _req_own(var_out, (B,), "var_out")
+    if grad_out is not None:
+        _req_own(grad_out, (B, d), "grad_out")
+    need = var_workspace_bytes(M, d, p, B, grad_out is not None)
+    if need == 0:
+        raise ValueError("var_predict: M, d, p, B = %d, %d, %d, %d is not a shape the entry takes (split the batch)" % (M, d, p, B))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        raise ValueError("var_predict workspace too small: %d bytes needed" % need)
+    check(lib.dsvgp_var_predict(ctx.h, _ptr(weights), _ptr(Q), _ld(Q), _ptr(PZ), _ptr(sZ), _ptr(hyp), M, d, p, _ptr(x), B, _ptr(var_out),
+                                _ptr(grad_out), _ptr(workspace)), "dsvgp_var_predict")
+    return var_out
+
+
+def acq_eval(ctx, kind, maximize, beta, best, mu, gmu, var, gvar, d, out=None, gout=None):
+    """acquisition values out [B] and, when ``gout`` [B, d] is given, gradients from mu [B], gmu [B, d], var [B], gvar [B, d]
+    (dsvgp_acq_eval; without ``gout`` the two gradients may be None).  ``kind``: a key of ACQ_KINDS; ``beta`` / ``best``: device float32
+    scalars (the unused one may be None)."""
+    B = mu.shape[0]
+    _req_own(mu, (B,), "mu")
+    _req_own(var, (B,), "var")
+    if gout is not None:
+        _req_own(gmu, (B, d), "gmu")
+        _req_own(gvar, (B, d), "gvar")
+        _req_own(gout, (B, d), "gout")
+    if out is None:
+        out = torch.empty(B, dtype=f32, device=mu.device)
+    _req_own(out, (B,), "out")
+    for name, t in (("beta", beta), ("best", best)):
+        if t is not None:
+            _req_own(t, t.shape, name)
+    check(lib.dsvgp_acq_eval(ctx.h, ACQ_KINDS[kind], 1 if maximize else 0, _ptr(beta), _ptr(best), _ptr(mu), _ptr(gmu), _ptr(var), _ptr(gvar),
+                             B, d, _ptr(out), _ptr(gout)), "dsvgp_acq_eval")
+    return out
+
+
+def acq_descend(ctx, mean_weights, weights, Q, packZ, hyp, M, d, p, x, lower, upper, kind, beta, best, maximize, iterations, initial_step,
+                resume, values, grads, steps, accepted, workspace):
+    """``iterations`` projected gradient steps of B starts on the acquisition, in place on x [B, d] and the state tensors values [B],
+    grads [B, d], steps [B] (float32) and accepted [B] (int32) (dsvgp_acq_descend).  ``workspace``: uint8 tensor of
+    dsvgp_acq_descend_workspace_bytes(M, d, p, B) bytes."""
+    PZ, sZ = _req_var_state(weights, Q, packZ, M, d, p)
+    _req(mean_weights, f32, "mean_weights", 1)
+    _req(x, f32, "x", 2)
+    B = x.shape[0]
+    _req_own(x, (B, d), "x")
+    _req_own(lower, (d,), "lower")
+    _req_own(upper, (d,), "upper")
+    _req_own(values, (B,), "values")
+    _req_own(grads, (B, d), "grads")
+    _req_own(steps, (B,), "steps")
+    _req_own(accepted, (B,), "accepted", torch.int32)
+    for name, t in (("beta", beta), ("best", best)):
+        if t is not None:
+            _req_own(t, t.shape, name)
+    need = acq_descend_workspace_bytes(M, d, p, B)
+    if need == 0:
+        raise ValueError("acq_descend: M, d, p, B = %d, %d, %d, %d is not a shape the entry takes" % (M, d, p, B))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        raise ValueError("acq_descend workspace too small: %d bytes needed" % need)
+    check(lib.dsvgp_acq_descend(ctx.h, _ptr(mean_weights), _ptr(weights), _ptr(Q), _ld(Q), _ptr(PZ), _ptr(sZ), _ptr(hyp), M, d, p, _ptr(x), B,
+                                _ptr(lower), _ptr(upper), ACQ_KINDS[kind], _ptr(beta), _ptr(best), 1 if maximize else 0, int(iterations),
+                                float(initial_step), 1 if resume else 0, _ptr(values), _ptr(grads), _ptr(steps), _ptr(accepted),
+                                _ptr(workspace)), "dsvgp_acq_descend")
+    return x
+
+
 def likelihood_terms(ctx, mu, var, y, p, hyp, mll_type, global_rows, mu_bar, var_bar, varn, scalars):
     check(lib.dsvgp_likelihood_terms(ctx.h, _ptr(mu), _ptr(var), _ptr(_req(y, f32, "y", 1)), mu.shape[0], p, _ptr(hyp),
                                      int(mll_type), float(global_rows), _ptr(mu_bar), _ptr(var_bar), _ptr(varn),

@@ -395,6 +395,178 @@ class SamplePaths:
         return torch.cat([vals.unsqueeze(-1), rows], dim=2).reshape(self.num_samples, B * (pd + 1))
 
 
+class VariancePredictor:
+    """Posterior variance of the function value with its gradient, and the confidence-bound / expected-improvement acquisitions
+    built on it, of a FROZEN model (``ElboEngine.variance_predictor``; csrc/predict_variance.hip):
+        sigma^2(x) = s + 1e-4 + k(x) . Q k(x),   grad sigma^2(x) = 2 (dk/dx)^T Q k(x),   Q = L^-T (S - I) L^-1  (float64)
+    One K_ZX assembly and one fp64 product V = Q K_ZX per batch, then one fused kernel (d <= 32) or a column reduction and a kernel
+    backward; no solve per batch and no second solve for the gradient.  Holds its own buffers: the packed weights, the inducing pack,
+    Q (float64 [M', M']: 72 MB at M' = 3000), the ``MeanPredictor`` of the same state and a workspace with K_ZX and V [M', B] (fp32;
+    V is accumulated in fp64 and rounded once) that grows to ``workspace_budget`` bytes at most -- larger batches go through in row
+    blocks.  The engine's evaluation cache and training workspaces are not used after construction.  Valid for the parameter values
+    it was built from.  Shared directions: the zero middle term is taken as S = 0, Q = -K~^-1, so sigma^2 = s + 1e-4 - k . K~^-1 k
+    there (``predict`` reports the constant s + 1e-4 for that strategy)."""
+
+    KINDS = ("lcb_var", "lcb", "ei")
+
+    def __init__(self, device, weights, Q, packZ, hyp, M, d, p, mean, workspace_budget=1 << 30):
+        self.device = torch.device(device)
+        self.weights, self.Q, self.packZ, self.hyp = weights, Q, packZ, hyp
+        self.M, self.d, self.p = int(M), int(d), int(p)
+        self.mean = mean                            # the MeanPredictor of the same parameter state
+        self.workspace_budget = int(workspace_budget)
+        self.route = _ops.var_route(self.d, self.p)
+        self._ws = None
+
+    def _fit_rows(self, B, need):
+        """rows per call of a C entry whose workspace on r rows is ``need(r)`` bytes: all of them when that fits the budget, else the
+        largest block that does (at least one row; 0 = refused: an intermediate past 2^31 entries)"""
+        if 0 < need(B) <= self.workspace_budget:
+            return B
+        lo, hi = 1, B
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            if 0 < need(mid) <= self.workspace_budget:
+                lo = mid
+            else:
+                hi = mid - 1
+        return lo
+
+    def _buffer(self, need):
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = None
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws
+
+    def _check_x(self, x, what="x"):
+        if not torch.is_tensor(x) or not x.is_cuda:
+            raise _lib.DsvgpError("%s must live on the GPU: the DSVGP hot path has no CPU fallback" % what)
+        if x.dim() == 1:
+            x = x.unsqueeze(-1)
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise ValueError("%s must be [B, d] = [B, %d], got %s" % (what, self.d, tuple(x.shape)))
+        return x.to(f32).contiguous()
+
+    def _run(self, x, want_grad):
+        x = self._check_x(x)
+        ctx = _ops.Context.get(self.device)
+        B = x.shape[0]
+        var = torch.empty(B, dtype=f32, device=self.device)
+        grad = torch.empty(B, self.d, dtype=f32, device=self.device) if want_grad else None
+        if B == 0:
+            return var, grad
+        need = lambda r: _ops.var_workspace_bytes(self.M, self.d, self.p, r, want_grad)
+        rows = self._fit_rows(B, need)
+        for r0 in range(0, B, rows):
+            r1 = min(B, r0 + rows)
+            _ops.var_predict(ctx, self.weights, self.Q, self.packZ, self.hyp, self.M, self.d, self.p, x[r0:r1], var[r0:r1],
+                             grad[r0:r1] if want_grad else None, self._buffer(need(r1 - r0)))
+        return var, grad
+
+    @torch.no_grad()
+    def variance(self, x, with_noise=False):
+        """sigma^2 [B] of q(f) at x [B, d]; ``with_noise``: plus the likelihood noise, clamped at 1e-6 (what ``predict`` returns)"""
+        var = self._run(x, False)[0]
+        return (var + self.hyp[2]).clamp_min_(1e-6) if with_noise else var
+
+    @torch.no_grad()
+    def variance_and_gradient(self, x):
+        """(sigma^2 [B], grad sigma^2 [B, d]) of q(f); ``variance`` returns the same values bits"""
+        return self._run(x, True)
+
+    def _scalars(self, kind, beta, best):
+        if kind not in self.KINDS:
+            raise ValueError("acquisition kind must be one of %s, got %r" % (list(self.KINDS), kind))
+        if kind == "ei" and best is None:
+            raise ValueError("the expected improvement needs ``best``: the incumbent value")
+        dev = lambda v: (v.detach().to(device=self.device, dtype=f32).reshape(1).contiguous() if torch.is_tensor(v)
+                         else torch.full((1,), float(v), dtype=f32, device=self.device))
+        return dev(2.0 if beta is None else beta), (None if best is None else dev(best))
+
+    @torch.no_grad()
+    def acquisition(self, x, kind="lcb", beta=None, best=None, maximize=False, gradients=False):
+        """Acquisition values [B] (with ``gradients``: and their gradients [B, d]) at x [B, d], every kind stated so that SMALLER is
+        better for a minimiser of the modelled function: "lcb_var" mu - beta sigma^2 (the reference's literal form), "lcb"
+        mu - beta sigma with sigma = sqrt(max(sigma^2, 1e-6)), "ei" -E[max(best - f, 0)].  ``maximize``: the same for a maximiser --
+        the model mirrored (mu -> -mu, best -> -best), still smaller is better.  ``beta`` (default 2) and ``best``: floats or device
+        scalars; nothing is read on the host."""
+        beta_t, best_t = self._scalars(kind, beta, best)
+        x = self._check_x(x)
+        ctx = _ops.Context.get(self.device)
+        B = x.shape[0]
+        out = torch.empty(B, dtype=f32, device=self.device)
+        gout = torch.empty(B, self.d, dtype=f32, device=self.device) if gradients else None
+        if B == 0:
+            return (out, gout) if gradients else out
+        if gradients:
+            mu, gmu = self.mean.value_and_gradient(x)
+            var, gvar = self._run(x, True)
+        else:
+            mu, gmu = self.mean.mean(x), None
+            var, gvar = self._run(x, False)
+        _ops.acq_eval(ctx, kind, maximize, beta_t, best_t, mu, gmu, var, gvar, self.d, out, gout)
+        return (out, gout) if gradients else out
+
+    @torch.no_grad()
+    def descend(self, x0, lower, upper, kind="lcb", beta=None, best=None, maximize=False, iterations=20, initial_step=None, state=None):
+        """``iterations`` projected gradient steps of every start x0 [B, d] on the acquisition ``kind`` inside the box [lower, upper]
+        ([d] each), one C call with no host read (dsvgp_acq_descend): ``SamplePaths.descend``'s rule -- one trial per iteration,
+        accepted when it passes the Armijo test with c1 = 1e-4, the start's step length doubled after an accepted trial and halved
+        after a rejected one; ``initial_step`` (a length in x; None: a quarter lengthscale) divided by |grad| is the first step
+        length.  Returns a ``PathDescent`` with [B, ...] shapes; the acquisition values never get worse.  ``state``: a previous
+        ``PathDescent`` to continue from (``x0`` is then not read and may be None).  ``x0`` is not modified."""
+        beta_t, best_t = self._scalars(kind, beta, best)
+        resume = state is not None
+        iterations = int(iterations)
+        if iterations < 0:
+            raise ValueError("descend needs iterations >= 0, got %d" % iterations)
+        src = state.x if resume else x0
+        x = self._check_x(src, "state.x" if resume else "x0")
+        B, d = x.shape
+        box = []
+        for name, t in (("lower", lower), ("upper", upper)):
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise _lib.DsvgpError("%s must live on the GPU: the DSVGP hot path has no CPU fallback" % name)
+            if tuple(t.shape) != (d,):
+                raise ValueError("%s must be [d] = [%d], got %s" % (name, d, tuple(t.shape)))
+            box.append(t.to(f32).contiguous())
+        if x.data_ptr() == src.data_ptr():
+            x = x.clone()                           # the entry works in place
+        if resume:
+            for name, t, shape in (("values", state.values, (B,)), ("gradients", state.gradients, (B, d)),
+                                   ("steps", state.steps, (B,)), ("accepted", state.accepted, (B,))):
+                if not torch.is_tensor(t) or not t.is_cuda:
+                    raise _lib.DsvgpError("state.%s must live on the GPU" % name)
+                if tuple(t.shape) != shape:
+                    raise ValueError("state.%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
+            values, grads = state.values.to(f32).clone(), state.gradients.to(f32).clone()
+            steps, accepted = state.steps.to(f32).clone(), state.accepted.to(torch.int32).clone()
+        else:
+            values = torch.empty(B, dtype=f32, device=self.device)
+            grads = torch.empty(B, d, dtype=f32, device=self.device)
+            steps = torch.empty(B, dtype=f32, device=self.device)
+            accepted = torch.empty(B, dtype=torch.int32, device=self.device)
+        out = PathDescent(x, values, grads, steps, accepted)
+        if B == 0:
+            return out
+        ctx = _ops.Context.get(self.device)
+        step0 = -1.0 if initial_step is None else float(initial_step)
+        need = lambda r: _ops.acq_descend_workspace_bytes(self.M, d, self.p, r)
+        rows = self._fit_rows(B, need)
+        args = (self.mean.weights, self.weights, self.Q, self.packZ, self.hyp, self.M, d, self.p)
+        tail = (kind, beta_t, best_t, maximize, iterations, step0, resume)
+        if rows >= B:
+            _ops.acq_descend(ctx, *args, x, box[0], box[1], *tail, values, grads, steps, accepted, self._buffer(need(B)))
+            return out
+        for r0 in range(0, B, rows):                # the starts are independent: blocks of them, one call each
+            r1 = min(B, r0 + rows)
+            part = [t[r0:r1].contiguous() for t in out]
+            _ops.acq_descend(ctx, *args, part[0], box[0], box[1], *tail, part[1], part[2], part[3], part[4], self._buffer(need(r1 - r0)))
+            for t, q in zip(out, part):
+                t[r0:r1] = q
+        return out
+
+
 class ElboEngine:
     """Owns the HBM workspaces of one (M', B', d, p) configuration on one GPU."""
 
@@ -1118,6 +1290,59 @@ class ElboEngine:
         source = (alpha.reshape(Mp), keep(params["inducing_points"]), keep(params["inducing_directions"]) if p > 0 else None, p,
                   keep(hyp), keep(params["constant"]), keep(self.center))
         return MeanPredictor(self.device, weights, M, d, values_only=self.data_outputs == "values", hvp_source=source)
+
+    @torch.no_grad()
+    def variance_predictor(self, params, workspace_budget=1 << 30):
+        """``VariancePredictor`` of the current parameter values: Q = L^-T (S - I) L^-1 in float64 from TWO transposed solves with
+        M' columns against the factor of ``_factor`` (jitter ladder included), symmetrised once, the inducing set packed by
+        dsvgp_var_prepare, and the ``MeanPredictor`` of the same state from the same factor.  Natural parameters, shared directions
+        (zero middle term: S = 0, Q = -K~^-1), p = 0 and p = d are the same code.  The factorisation runs in the engine's factor
+        buffers, so the evaluation cache of ``predict`` is dropped (it refactors on its next call)."""
+        self._no_matern("variance_predictor (and the acquisitions built on it)")
+        self._no_ard(params, "variance_predictor (and the acquisitions built on it)")
+        if self.whitening == "ciq":
+            raise NotImplementedError("posterior-variance predictor with CIQ whitening: Q there needs K^{-1/2} by msMINRES "
+                                      "(contour-integral quadrature), which is not built; use predict()")
+        ctx = _ops.Context.get(self.device)
+        self._eval_cache = None
+        if "natural_vec" in params:
+            m32, LS32, _, _ = self._natural_to_mu_chol(ctx, params["natural_vec"], params["natural_mat"])
+            params = {k: v for k, v in params.items() if not k.startswith("natural_")}
+            params["variational_mean"], params["chol_variational_covar"] = m32, LS32
+        no_middle = bool(self.shared_directions)
+        if self.shared_directions:
+            params, _ = self._shared_expand(params)
+        hyp, packZ, L, (M, d, p, Mp) = self._factor(ctx, params, sync=True)
+        m, LS = params["variational_mean"], params["chol_variational_covar"]
+        if m.shape[0] != Mp:
+            raise ValueError("q(u) has %d values, the inducing set M (p + 1) = %d" % (m.shape[0], Mp))
+        dev = self.device
+        T = torch.empty(Mp, Mp, dtype=f64, device=dev)                                     # S - I
+        if no_middle:
+            T.zero_()
+        else:
+            if tuple(LS.shape) != (Mp, Mp):
+                raise ValueError("chol_variational_covar must be [%d, %d], got %s" % (Mp, Mp, tuple(LS.shape)))
+            LS64 = torch.tril(LS).to(f64).contiguous()
+            _ops.gemm(ctx, TRANS_B, LS64, LS64, T)
+        T.diagonal().sub_(1.0)
+        X = torch.empty(Mp, Mp, dtype=f64, device=dev)
+        _ops.trsm(ctx, L, T, True, X, None, self.trsm_nb, self._inverse_ws, reuse_inverse=True)        # L^-T (S - I)
+        Xt = X.t().contiguous()                                                                        # (S - I) L^-1
+        _ops.trsm(ctx, L, Xt, True, X, None, self.trsm_nb, self._inverse_ws, reuse_inverse=True)       # L^-T (S - I) L^-1
+        Q = (0.5 * (X + X.t())).contiguous()
+        del T, X, Xt
+        Z = params["inducing_points"].contiguous()
+        V = params["inducing_directions"].contiguous() if p > 0 else None
+        weights = _ops.var_prepare(ctx, Z, V, p, hyp, self.center)
+        # the mean of the same state, from the same factor (``mean_predictor``'s steps)
+        alpha = torch.empty(Mp, 1, dtype=f64, device=dev)
+        _ops.trsm(ctx, L, m.to(f64).reshape(Mp, 1).contiguous(), True, alpha, None, self.trsm_nb, self._inverse_ws, reuse_inverse=True)
+        mean_weights = _ops.mean_prepare(ctx, alpha.reshape(Mp), Z, V, p, hyp, params["constant"], self.center)
+        keep = lambda t: t.detach().clone().contiguous()
+        source = (alpha.reshape(Mp), keep(Z), keep(V) if p > 0 else None, p, keep(hyp), keep(params["constant"]), keep(self.center))
+        mean = MeanPredictor(dev, mean_weights, M, d, values_only=self.data_outputs == "values", hvp_source=source)
+        return VariancePredictor(dev, weights, Q, (packZ[0], packZ[1]), keep(hyp), M, d, p, mean, workspace_budget)
 
     @torch.no_grad()
     def sample_paths(self, params, num_samples, num_features=2048, generator=None, base_samples=None):

@@ -823,6 +823,32 @@ def thompson_candidates(paths, candidates, lower, upper, num_starts=8, iteration
     return res.x[rows, best], res.values[rows, best], top.values[:, 0]
 
 
+def acquisition_candidates(predictor, candidates, lower, upper, kind="lcb", beta=2.0, best=None, maximize=False, num_starts=8,
+                           iterations=20):
+    """One confidence-bound / expected-improvement step with refinement, in the pattern of ``thompson_candidates``: the acquisition
+    ``kind`` of ``predictor`` (``model._variance_predictor()`` / ``ElboEngine.variance_predictor``; smaller is better) is evaluated
+    at the ``candidates`` [N, d], its ``num_starts`` best become the starts of ``predictor.descend`` inside the box [lower, upper]
+    ([d] each) and the best refined start is returned: (x_next [d], a_next, a_candidates_best) with a_next never worse than
+    a_candidates_best, the best acquisition value over the candidates (where the reference's loops stop: the arg-min of
+    ``preds.mean - lcb_beta * preds.variance``, experiments/rover/bo_traditional.py:214)."""
+    X = candidates.to(device=predictor.device, dtype=torch.float32)
+    if X.dim() == 1:
+        X = X.unsqueeze(-1)
+    if X.dim() != 2 or X.shape[0] < 1 or X.shape[1] != predictor.d:
+        raise ValueError("candidates must be [N, d] = [N >= 1, %d], got %s" % (predictor.d, tuple(X.shape)))
+    k = max(1, min(int(num_starts), X.shape[0]))
+    lower, upper = lower.to(predictor.device), upper.to(predictor.device)
+    vals = predictor.acquisition(X, kind, beta, best, maximize)          # [N]
+    top = torch.topk(vals, k, largest=False)
+    # (a start outside the box is clamped by the descent, which may raise its value: the candidates' best stays in the comparison)
+    res = predictor.descend(X[top.indices], lower, upper, kind, beta, best, maximize, iterations=iterations)
+    i = res.values.argmin()
+    a_best = top.values[0]
+    take = res.values[i] <= a_best
+    x_next = torch.where(take, res.x[i], X[top.indices[0]])
+    return x_next, torch.where(take, res.values[i], a_best), a_best
+
+
 def eval_values(test_dataset, model, likelihood, minibatch_size=1):
     """``eval_gp(...)`` followed by ``[::p+1]``: predictive means / variances (with likelihood noise) of the FUNCTION VALUES,
     what the reference's callers keep of it (tests/test_dsvgp.py:99-101, the experiments' MSE / NLL reports).  Same batching and

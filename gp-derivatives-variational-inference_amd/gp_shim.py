@@ -429,6 +429,49 @@ class ApproximateGP(torch.nn.Module):
         paths = self.sample_paths(num_samples, num_features, generator)
         return thompson_candidates(paths, candidates, lower, upper, num_starts, iterations, maximize)
 
+    # ---- posterior variance with its gradient and the acquisitions on it (what the reference's confidence-bound callers read from
+    #      ``preds.variance``: experiments/rover/bo_traditional.py:214, experiments/GNN_bo/bo.py:171-173) ----
+    def _variance_predictor(self):
+        """The engine's ``VariancePredictor`` for the current parameters, cached in eval mode and keyed like ``_mean_predictor``"""
+        engine = self.engine            # (ElboEngine64 -- a float64 model -- refuses: NotImplementedError)
+        vs = self.variational_strategy
+        if hasattr(vs, "_strategy_is_updated") and not vs._strategy_is_updated():
+            vs._whiten_legacy_parameters()
+        if self.training and hasattr(vs, "_maybe_init"):
+            vs._maybe_init()
+        params = self._param_dict(None)
+        key = tuple((t.data_ptr(), t._version) for k, t in params.items() if k != "raw_noise")
+        key += (engine.whitening, engine.data_outputs, engine.shared_directions)
+        cached = self.__dict__.get("_variance_cache")
+        if not self.training and cached is not None and cached[0] == key and cached[1] is engine:
+            return cached[2]
+        pred = engine.variance_predictor(params)
+        self.__dict__["_variance_cache"] = (key, engine, pred) if not self.training else None
+        return pred
+
+    def posterior_variance(self, x, likelihood=None):
+        """Variance [B] of the function value at x [B, d] under q(f) (``likelihood`` given: plus its noise), from
+        ``ElboEngine.variance_predictor``: one fp64 product per batch, no solve.  Not differentiable."""
+        var = self._variance_predictor().variance(x)
+        return var if likelihood is None else (var + likelihood.noise.detach().reshape(()).to(var)).clamp_min_(1e-6)
+
+    def posterior_variance_gradient(self, x):
+        """Gradient [B, d] of the variance of the function value at x [B, d]"""
+        return self._variance_predictor().variance_and_gradient(x)[1]
+
+    def acquisition(self, x, kind="lcb", beta=2.0, best=None, maximize=False):
+        """Acquisition values [B] at x [B, d], smaller is better: "lcb_var" mu - beta sigma^2, "lcb" mu - beta sigma, "ei" the
+        negative expected improvement below ``best`` (``VariancePredictor.acquisition``)"""
+        return self._variance_predictor().acquisition(x, kind, beta, best, maximize)
+
+    def acquisition_step(self, candidates, lower, upper, kind="lcb", beta=2.0, best=None, maximize=False, num_starts=8, iterations=20):
+        """``directional_vi.acquisition_candidates`` on this model's ``VariancePredictor``: the acquisition over the candidates, its
+        ``num_starts`` best refined by the on-device descent inside the box -> (x_next [d], a_next, a_candidates_best).  Refuses where
+        ``variance_predictor`` refuses (ARD, Matern-5/2, CIQ whitening, float64 models)."""
+        from .directional_vi import acquisition_candidates
+        return acquisition_candidates(self._variance_predictor(), candidates, lower, upper, kind, beta, best, maximize, num_starts,
+                                      iterations)
+
     def posterior_mean(self, x, derivative_directions=None):
         """Predictive mean at x [B, d]: [B (pd + 1)] interleaved with pd = len(derivative_directions) // B rows per point
         (``None``: function values only); equals ``likelihood(self(x, derivative_directions=D)).mean`` without assembling

@@ -15,7 +15,7 @@ import torch
 
 from . import directional_vi as _dvi
 from .SharedDirectionalGradVariationalStrategy import DirectionalGradVariationalStrategy
-from .directional_vi import eval_gp, eval_gradient_nll, eval_gradients, eval_mean, eval_paths, eval_values, select_cols_of_y, thompson_candidates  # noqa: F401
+from .directional_vi import acquisition_candidates, eval_gp, eval_gradient_nll, eval_gradients, eval_mean, eval_paths, eval_values, select_cols_of_y, thompson_candidates  # noqa: F401
 from .gp_shim import CholeskyVariationalDistribution, ConstantMean, NaturalVariationalDistribution, ScaleKernel
 from .RBFKernelDirectionalGrad import RBFKernelDirectionalGrad
 

@@ -949,6 +949,68 @@ int dsvgp_kmeans_lloyd(dsvgp_ctx* ctx, const float* x, int N, int d, float* Z, i
                        int* counts, double* inertia, int* moved, void* workspace);
 int dsvgp_cluster_moments(dsvgp_ctx* ctx, const float* g, int N, int d, const int* labels, int M, double* C, void* workspace);
 
+/* ---- posterior variance of a frozen model with its gradient, acquisitions and their descent (csrc/predict_variance.hip): what the
+ * reference's confidence-bound callers read from `preds.variance` (experiments/rover/bo_traditional.py:214 `preds.mean - lcb_beta *
+ * preds.variance`, experiments/GNN_bo/bo.py:171-173 `preds.variance.sqrt()`), plus the gradient the reference does not have.
+ * Cholesky-whitened strategy, value rows (DirectionalGradVariationalStrategy.py:188-205).  With K~ = s K_ZZ + j I = L L^T, S = L_S L_S^T,
+ * k(x) = s K_Z'x and Q = L^-T (S - I) L^-1 [M', M'] (double, exactly symmetric, formed by the caller ONCE per parameter state: two
+ * dsvgp_trsm calls with trans = 1):
+ *     v(x) = Q k(x),   sigma^2(x) = s + 1e-4 + k(x) . v(x)   (q(f), no likelihood noise),   grad sigma^2(x) = 2 (dk/dx)^T v(x)
+ * Q stays in double and V = Q K_ZX is accumulated in double (Q rounded to float costs three digits of sigma^2: the sum cancels);
+ * V is rounded once to float and everything after it is float.
+ *   dsvgp_var_prepare    Z[M,d], V[M*p,d] (raw directions, normalised here; NULL when p = 0; p <= 95), hyp, center[d] (NULL = 0; MUST be
+ *                        the centre the inducing pack below was made with) -> weights: dsvgp_var_weights_bytes(M, d, p) bytes, 16-byte
+ *                        aligned, fp32: {ell, s, 1/ell, s/ell, ..}, center, Z~ = (Z - center) / ell, the unit directions; rows padded to
+ *                        multiples of 4 floats.  One launch.
+ *   dsvgp_var_predict    Q (leading dimension ldq >= M' = M(p+1)), PZ / selfZ = what dsvgp_pack_points wrote for (Z, V, p), x[B,d] ->
+ *                        var_out[B], grad_out (NULL or [B,d]).  One batch: K_ZX [M', B] by dsvgp_pack_points + dsvgp_kernel_fwd_rect
+ *                        (data side p = 0), V = Q K_ZX on the fp64 MFMA GEMM with the float right operand, never split along K (no
+ *                        atomics), then one of two routes (dsvgp_var_route(d, p): 1 = fused, 2 = composed, 0 = refused arguments):
+ *                        fused: d <= 32 and dsvgp_var_chunk(d, p) = min(64, floor(12288 / ((p + 1) pad4(d)))) rounded down to a multiple
+ *                        of 8 is >= 8 (a chunk of that many inducing points with their unit directions is staged in 48 KB of LDS): ONE
+ *                        kernel, a workgroup of 8 waves owns 64 points (lane = point, weights read from V[:, b]), partial sums added in
+ *                        the order 0..7; grad_out = NULL returns the same values bits.  composed (any other shape): one kernel for
+ *                        sigma^2 = s + 1e-4 + colsum(K_ZX o V) (row slices of 256, fixed order) that also writes G = 2 V^T [B, M'], a
+ *                        fixed-order combine, then dsvgp_kernel_bwd_rect(G, side 1 = the x pack, side 2 = the inducing pack) into the
+ *                        zeroed grad_out.  `workspace`: dsvgp_var_workspace_bytes(M, d, p, B, want_grad) bytes, 16-byte aligned, never 0
+ *                        for a shape the entry takes: the x pack (B (pad4(d) + 4) + pad4(B) floats), K_ZX and V (M' pad4(B) floats
+ *                        each) on both routes; composed adds ceil(M' / 256) pad4(B) floats and, with the gradient, B pad4(M') + 4 floats
+ *                        and dsvgp_kernel_bwd_rect's workspace.
+ *   dsvgp_acq_eval       mu[B], gmu[B,d], var[B], gvar[B,d] -> out[B] and gout (NULL or [B,d]; gmu / gvar may be NULL without it).  All
+ *                        kinds are stated for MINIMISATION of the modelled function; maximize != 0 mirrors the model (mu -> -mu,
+ *                        best -> -best).  kind 0 "lcb_var": mu - beta sigma^2 (the reference's literal form); 1 "lcb": mu - beta sigma,
+ *                        sigma = sqrt(max(sigma^2, 1e-6)); 2 "ei": -[(best - mu) Phi(z) + sigma phi(z)], z = (best - mu) / sigma, with
+ *                        gradient Phi(z) grad mu - phi(z) grad sigma, grad sigma = grad sigma^2 / (2 sigma), taken as 0 where sigma^2 is
+ *                        clamped.  beta / best: device floats (the one the kind does not use may be NULL).  One pointwise launch.
+ *   dsvgp_acq_descend    dsvgp_paths_descend's rule with n = 1 on the acquisition of B starts x[B,d] (in: starts, out: iterates) inside
+ *                        [lower, upper]: resume = 0: x <- clamp(x); (f, g) by dsvgp_mean_predict + dsvgp_var_predict + dsvgp_acq_eval;
+ *                        eta = step0 / max(|g|, 1e-30), step0 = initial_step, or 0.25 ell when initial_step <= 0; accepted = 0.
+ *                        resume = 1: x, values, grads, steps, accepted are the state a previous call left.  Then `iterations` times, per
+ *                        start: y = clamp(x - eta g); accept iff f_y <= f + 1e-4 g.(y - x) (a NaN f_y rejects): x, f, g <- y, f_y, g_y,
+ *                        eta <- min(2 eta, 1e30), accepted += 1; else eta <- eta / 2.  One step kernel (one wave per start, fixed-order
+ *                        wave sums).  The acquisition is always minimised (`maximize` goes to dsvgp_acq_eval); values never increase;
+ *                        iterates stay in the box; iterations = 0 gives the start state.  mean_weights: dsvgp_mean_prepare's, of the
+ *                        same state.  `workspace`: dsvgp_acq_descend_workspace_bytes(M, d, p, B) bytes, 16-byte aligned.
+ * Every entry queues on the context's stream: no host read, no allocation, no synchronisation, no floating-point atomics, fixed summation
+ * orders; two identical calls return identical bits.  DSVGP_EINVAL: a null required pointer, M, d or B < 1, p outside [0, 95], a kind
+ * outside 0..2, iterations < 0, ldq < M', or an intermediate that would pass 2^31 entries (split the batch); DSVGP_EALIGN: a misaligned
+ * weights, workspace, PZ or Q.  The size, route and chunk helpers are pure host functions (0 for arguments the entries refuse). */
+int dsvgp_var_route(int d, int p);
+int dsvgp_var_chunk(int d, int p);
+size_t dsvgp_var_weights_bytes(int M, int d, int p);
+size_t dsvgp_var_workspace_bytes(int M, int d, int p, int B, int want_grad);
+int dsvgp_var_prepare(dsvgp_ctx* ctx, const float* Z, const float* V, int M, int d, int p, const float* hyp, const float* center,
+                      float* weights);
+int dsvgp_var_predict(dsvgp_ctx* ctx, const float* weights, const double* Q, int64_t ldq, const float* PZ, const float* selfZ,
+                      const float* hyp, int M, int d, int p, const float* x, int B, float* var_out, float* grad_out, void* workspace);
+int dsvgp_acq_eval(dsvgp_ctx* ctx, int kind, int maximize, const float* beta, const float* best, const float* mu, const float* gmu,
+                   const float* var, const float* gvar, int B, int d, float* out, float* gout);
+size_t dsvgp_acq_descend_workspace_bytes(int M, int d, int p, int B);
+int dsvgp_acq_descend(dsvgp_ctx* ctx, const float* mean_weights, const float* var_weights, const double* Q, int64_t ldq, const float* PZ,
+                      const float* selfZ, const float* hyp, int M, int d, int p, float* x, int B, const float* lower, const float* upper,
+                      int kind, const float* beta, const float* best, int maximize, int iterations, float initial_step, int resume,
+                      float* values, float* grads, float* steps, int* accepted, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
