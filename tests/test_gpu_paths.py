@@ -306,9 +306,14 @@ def test_peak_memory_is_the_outputs_plus_the_reported_workspace(dsvgp, gpu_devic
     # the measurement must not depend on which modules ran before: a free cached block up to 1 MiB larger than an output is handed out
     # whole by the caching allocator and counted in full, and such blocks come and go with every GPU test module that runs earlier
     torch.cuda.empty_cache()
+    # ... and emptying the cache does not return the free pieces of segments that tensors kept alive by earlier modules still sit in: a free
+    # piece less than 1 MiB larger than the gradient output is handed out whole as well (seen: 6475776 > 5506048 bytes).  The call allocates
+    # from a pool of its own, which starts without free pieces; the statistics are the device's and count it like any other allocation.
+    pool = torch.cuda.MemPool()
     torch.cuda.reset_peak_memory_stats(dev)
     base = torch.cuda.memory_allocated(dev)
-    vals, grads = paths.values_and_gradients(x)
+    with torch.cuda.use_mem_pool(pool):
+        vals, grads = paths.values_and_gradients(x)
     torch.cuda.synchronize(dev)
     peak = torch.cuda.max_memory_allocated(dev) - base
     outputs = 4 * (n * B + n * B * d)
@@ -317,6 +322,8 @@ def test_peak_memory_is_the_outputs_plus_the_reported_workspace(dsvgp, gpu_devic
     assert torch.isfinite(vals).all() and torch.isfinite(grads).all()
     assert peak <= allowed, (peak, allowed)
     assert peak < 4 * B * B                                                          # nothing of size B x B
+    del vals, grads                                                                  # (before the pool they live in)
+    del pool
 
 
 # ------------------------------------------------------------------ 7: refusals

@@ -45,21 +45,7 @@ def _raw(v):
 
 
 # ------------------------------------------------------------------ the yardstick
-def rect_kernel(x1, v1, p1, x2, v2, p2, ell):
-    """K(x1, x2; v1, v2) [n1 (p1 + 1), n2 (p2 + 1)] with p1 != p2 from the oracle's square kernel: an entry depends only on its own
-    row and column directions, so the shorter side is padded with arbitrary directions and the padded rows / columns are dropped"""
-    n1, n2, d = x1.shape[0], x2.shape[0], x1.shape[1]
-    P = max(p1, p2, 1)
-    g = torch.Generator().manual_seed(11)
-
-    def pad(v, n, p):
-        out = torch.randn(n, P, d, generator=g, dtype=x1.dtype)
-        if p:
-            out[:, :p] = v.reshape(n, p, d)
-        return out.reshape(n * P, d)
-
-    K = O.kernel_matrix(x1, x2, pad(v1, n1, p1), pad(v2, n2, p2), ell).reshape(n1, P + 1, n2, P + 1)
-    return K[:, :p1 + 1, :, :p2 + 1].reshape(n1 * (p1 + 1), n2 * (p2 + 1))
+from _conditioning import rect_kernel        # (the padded square kernel; shared with the per-block conditioning tests)
 
 
 def rect_predictive(P64, x, D, pd):
