@@ -235,6 +235,12 @@ SIGNATURES = {
     "dsvgp_acq_descend_workspace_bytes": (_z, [_i, _i, _i, _i]),
     "dsvgp_acq_descend": (_i, [_p, _p, _p, _p, _l, _p, _p, _p, _i, _i, _i, _p, _i, _p, _p, _i, _p, _p, _i, _i, _f, _i, _p, _p, _p, _p,
                                _p]),
+    "dsvgp_collapsed_state_bytes": (_z, [_i]),
+    "dsvgp_collapsed_workspace_bytes": (_z, [_i]),
+    "dsvgp_collapsed_reset": (_i, [_p, _p, _i]),
+    "dsvgp_collapsed_accumulate": (_i, [_p, _p, _i, _p, _l, _i, _p, _p, _p]),
+    "dsvgp_collapsed_solve": (_i, [_p, _p, _i, _p, _d, _p, _p, _l, _p, _p, _l, _p, _p, _p]),
+    "dsvgp_collapsed_evaluate": (_i, [_p, _p, _i, _p, _p, _l, _p, _d, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1947,3 +1947,78 @@ def cluster_moments(ctx, g, labels, M, out=None):
         raise ValueError("out must be [%d, %d, %d]" % (M, d, d))
     check(lib.dsvgp_cluster_moments(ctx.h, _ptr(g), N, d, _ptr(labels), M, _ptr(out), None), "dsvgp_cluster_moments")
     return out
+
+
+# ---- closed-form optimal q(u) from one-pass statistics (csrc/collapsed.hip) ---------------------------------------------------
+COLLAPSED_MAX_MP = 8192
+
+
+def collapsed_state(Mp, device):
+    """zeroed statistics of ``collapsed_accumulate``: float64 [8 + (M' + 1)^2] -- sum of the prior diagonal, R, six reserved words, then
+    tril([A ; r^T][A ; r^T]^T) row-major (rows < M': tril G; row M': b^T, then yy)"""
+    Mp = int(Mp)
+    if Mp < 1:
+        raise ValueError("collapsed statistics need M' >= 1, got %d" % Mp)
+    return torch.zeros(int(lib.dsvgp_collapsed_state_bytes(Mp)) // 8, dtype=f64, device=device)
+
+
+def _req_collapsed_state(state, Mp):
+    _req(state, f64, "state", 1)
+    if state.numel() * 8 != int(lib.dsvgp_collapsed_state_bytes(int(Mp))):
+        raise ValueError("state is not the collapsed statistics of M' = %d (collapsed_state)" % Mp)
+    return state
+
+
+def collapsed_workspace(Mp, device):
+    nbytes = int(lib.dsvgp_collapsed_workspace_bytes(int(Mp)))
+    if nbytes == 0:
+        raise ValueError("collapsed solve / evaluate take 1 <= M' <= %d, got %d" % (COLLAPSED_MAX_MP, Mp))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def collapsed_reset_(ctx, state, Mp):
+    check(lib.dsvgp_collapsed_reset(ctx.h, _ptr(_req_collapsed_state(state, Mp)), int(Mp)), "dsvgp_collapsed_reset")
+
+
+def collapsed_accumulate_(ctx, state, Mp, A64, Bp, y, constant, prior_diag):
+    """state += statistics of one chunk.  A64 [M' + 1, >= Bp] float64: rows < M' hold A = L^-1 K_ZX (``trsm``'s X64); row M' is written here
+    (r = y - constant).  y, prior_diag: float32 [Bp]; constant: float32 [1]"""
+    _req_collapsed_state(state, Mp)
+    _req(A64, f64, "A64", 2)
+    if A64.shape[0] != Mp + 1 or A64.shape[1] < Bp:
+        raise ValueError("A64 must be [M' + 1, >= B'] = [%d, >= %d], got %s" % (Mp + 1, Bp, tuple(A64.shape)))
+    for t, name in ((y, "y"), (prior_diag, "prior_diag")):
+        _req(t, f32, name, 1)
+        if t.numel() != Bp:
+            raise ValueError("%s must have B' = %d entries, got %d" % (name, Bp, t.numel()))
+    _req(constant, f32, "constant", 1)
+    check(lib.dsvgp_collapsed_accumulate(ctx.h, _ptr(state), int(Mp), _ptr(A64), _ld(A64), int(Bp), _ptr(y), _ptr(constant),
+                                         _ptr(prior_diag)), "dsvgp_collapsed_accumulate")
+
+
+def collapsed_solve(ctx, state, Mp, hyp, num_data, workspace, want_natural=True):
+    """(m*, L_S*, natural_vec, natural_mat, scalars[8] float64, info int32[1]) -- all on the device, nothing read"""
+    _req_collapsed_state(state, Mp)
+    dev = state.device
+    m = torch.empty(Mp, dtype=f32, device=dev)
+    LS = torch.empty(Mp, Mp, dtype=f32, device=dev)
+    nv = torch.empty(Mp, dtype=f32, device=dev) if want_natural else None
+    nm = torch.empty(Mp, Mp, dtype=f32, device=dev) if want_natural else None
+    scal = torch.empty(8, dtype=f64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib.dsvgp_collapsed_solve(ctx.h, _ptr(state), int(Mp), _ptr(hyp), float(num_data), _ptr(m), _ptr(LS), Mp, _ptr(nv), _ptr(nm), Mp,
+                                    _ptr(scal), _ptr(info), _ptr(workspace)), "dsvgp_collapsed_solve")
+    return m, LS, nv, nm, scal, info
+
+
+def collapsed_evaluate(ctx, state, Mp, m, LS, hyp, num_data, workspace):
+    """scalars[8] float64 (loss, sum ll, KL, sum |residual|^2, sum varn, R, kappa, tr G) of the caller's float32 (m, tril L_S)"""
+    _req_collapsed_state(state, Mp)
+    _req(m, f32, "variational_mean", 1)
+    _req(LS, f32, "chol_variational_covar", 2)
+    if m.numel() != Mp or LS.shape != (Mp, Mp):
+        raise ValueError("variational_mean / chol_variational_covar must be [%d] / [%d, %d]" % (Mp, Mp, Mp))
+    scal = torch.empty(8, dtype=f64, device=state.device)
+    check(lib.dsvgp_collapsed_evaluate(ctx.h, _ptr(state), int(Mp), _ptr(m), _ptr(LS), _ld(LS), _ptr(hyp), float(num_data), _ptr(scal),
+                                       _ptr(workspace)), "dsvgp_collapsed_evaluate")
+    return scal

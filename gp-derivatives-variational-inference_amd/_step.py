@@ -567,6 +567,173 @@ class VariancePredictor:
         return out
 
 
+CollapsedValue = collections.namedtuple("CollapsedValue", "loss terms")
+_COLLAPSED_TERMS = ("loss", "log_likelihood", "kl", "residual", "varn", "rows", "kappa", "trace_G")
+
+
+class CollapsedResult:
+    """The closed-form optimum of q(u) for the statistics, noise and ``num_data`` it was solved with: float32 ``variational_mean`` [M'],
+    ``chol_variational_covar`` [M', M'] (lower, strict upper triangle exactly zero), gpytorch's ``natural_vec`` / ``natural_mat`` of the
+    same distribution, and float64 host scalars: ``loss`` (the full-data objective at the optimum) and ``terms``."""
+
+    def __init__(self, m, LS, nat_vec, nat_mat, terms, num_data):
+        self.variational_mean, self.chol_variational_covar = m, LS
+        self.natural_vec, self.natural_mat = nat_vec, nat_mat
+        self.terms, self.loss, self.num_data = terms, terms["loss"], num_data
+
+
+class CollapsedAccumulator:
+    """One-pass sufficient statistics of the data in the whitened basis of ONE parameter state (``ElboEngine.collapsed_accumulator``;
+    csrc/collapsed.hip): G = sum A A^T, b = sum A r, yy = sum r^T r, the prior diagonal's sum and the row count R,
+    all float64.  ``add`` queues a chunked pass (no host read); ``solve`` returns the maximiser of the ELBO over q(u) (Titsias 2009) and
+    ``evaluate`` the full-data ELBO of any q(u), each with one host read.  It keeps its own copy of the factor, its inverse and the packs:
+    the engine may go on with other work.  Valid for the hyper-parameters, inducing points and directions it was built from.
+    Repeats are NOT bitwise equal: the fp64 Gram product's split-K slices meet in atomics on the live statistics (run-order rounding of
+    G, b and yy, ~1e-16 relative); the two scalar sums and everything in ``solve`` / ``evaluate`` have fixed orders."""
+
+    def __init__(self, engine, hyp, packZ, L, dims, inverse_ws, center, constant, ell, matern, workspace_budget):
+        self.device = engine.device
+        self.M, self.d, self.p, self.Mp = dims
+        self._hyp, self._packZ, self._L, self._center, self._constant = hyp, packZ, L, center, constant
+        self._ell, self._matern = ell, matern
+        self._nb = engine.trsm_nb
+        self._inv = inverse_ws                                   # L^-1 | L^-T (2 M'^2 doubles): the head of every solve's workspace
+        self.workspace_budget = int(workspace_budget)
+        self._state = _ops.collapsed_state(self.Mp, self.device)
+        self._rows = 0
+        self._buf = {}
+        self._solve_ws = None
+
+    # ---- chunking -------------------------------------------------------------------------------
+    def row_bytes(self, pd):
+        """bytes of chunk workspace per data point carrying ``pd`` directions: K_ZX (fp32), [A ; r^T] (fp64), the solve's staging rows and
+        the data pack"""
+        nb = 64
+        while nb < min(self._nb, self.Mp):
+            nb *= 2
+        per_col = 4 * self.Mp + 8 * (self.Mp + 1) + 8 * nb + 4 * (_ops.packed_width(self.d) + 3)
+        return per_col * (int(pd) + 1)
+
+    def chunk_rows(self, pd):
+        """data points per chunk at ``pd`` directions per point under the workspace budget (at least one)"""
+        return max(1, self.workspace_budget // self.row_bytes(pd))
+
+    def _get(self, name, numel, dtype):
+        t = self._buf.get(name)
+        if t is None or t.numel() < numel or t.dtype != dtype:
+            t = torch.empty(int(numel), dtype=dtype, device=self.device)
+            self._buf[name] = t
+        return t[:numel]
+
+    @property
+    def rows(self):
+        """R: output rows accumulated so far (host count)"""
+        return self._rows
+
+    @torch.no_grad()
+    def reset(self):
+        _ops.collapsed_reset_(_ops.Context.get(self.device), self._state, self.Mp)
+        self._rows = 0
+
+    @torch.no_grad()
+    def add(self, x, y, D=None):
+        """statistics += those of the points ``x`` [B, d] with targets ``y`` [B (pd + 1)] (interleaved) and directions ``D`` [B pd, d]
+        (None: values only), in row chunks that fit the budget.  K_ZX always comes from the rectangular assembly, so a chunk's bits do
+        not depend on where the chunks are cut; no host read."""
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise ValueError("x must be [B, %d], got %s" % (self.d, tuple(x.shape)))
+        B = x.shape[0]
+        pd = 0
+        if D is not None and D.numel():
+            if D.dim() != 2 or D.shape[1] != self.d or B == 0 or D.shape[0] % B:
+                raise ValueError("derivative directions must be [B * pd, d] = [%d * pd, %d], got %s" % (B, self.d, tuple(D.shape)))
+            pd = D.shape[0] // B
+        if pd > 95:
+            raise ValueError("at most 95 derivative directions per data point, got %d" % pd)
+        if y.shape != (B * (pd + 1),):
+            raise ValueError("y must be the interleaved target vector of length B*(pd+1)=%d" % (B * (pd + 1)))
+        for t, name in ((x, "x"), (y, "y")) + (((D, "D"),) if pd else ()):
+            if t.dtype != f32 or not t.is_cuda:
+                raise TypeError("%s must be a float32 tensor on the GPU" % name)
+        if B == 0:
+            return self
+        ctx = _ops.Context.get(self.device)
+        Mp, q, rows = self.Mp, pd + 1, self.chunk_rows(pd)
+        ws_bytes = _lib.lib.dsvgp_trsm_workspace_bytes(Mp, min(rows, B) * q, self._nb)
+        ws = self._buf.get("trsm_ws")
+        if ws is None or ws.numel() < ws_bytes:
+            ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=self.device)
+            ws[:self._inv.numel()].copy_(self._inv)
+            self._buf["trsm_ws"] = ws
+        fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
+        y = y.contiguous()
+        for r0 in range(0, B, rows):
+            nb_ = min(rows, B - r0)
+            Bp = nb_ * q
+            xc = x[r0:r0 + nb_].contiguous()
+            Dc = D[r0 * pd:(r0 + nb_) * pd].contiguous() if pd else None
+            if self._ell is not None:
+                packX = _ops.pack_points_ard(ctx, xc, Dc, pd, self._ell, self._center)
+                diag = (_ops.kernel_diag_matern52 if self._matern else _ops.kernel_diag_ard)(ctx, packX, nb_, pd, self.d, self._hyp)
+            else:
+                packX = _ops.pack_points(ctx, xc, Dc, pd, self._hyp, self._center)
+                diag = _ops.kernel_diag(ctx, nb_, pd, self._hyp)
+            Kzx = fwd(ctx, self._packZ, self.M, self.p, packX, nb_, pd, self.d, self._hyp, out=self._get("Kzx", Mp * Bp, f32).view(Mp, Bp))
+            A64 = self._get("A64", (Mp + 1) * Bp, f64).view(Mp + 1, Bp)
+            _ops.trsm(ctx, self._L, Kzx, False, A64[:Mp], None, self._nb, ws, reuse_inverse=True)
+            _ops.collapsed_accumulate_(ctx, self._state, Mp, A64, Bp, y[r0 * q:(r0 + nb_) * q], self._constant, diag)
+        self._rows += B * q
+        return self
+
+    # ---- results ---------------------------------------------------------------------------------
+    def statistics(self):
+        """(G [M', M'] lower triangle, b [M'], yy, prior-diagonal sum, R) as float64 device tensors (copies; diagnostics and tests)"""
+        Mp = self.Mp
+        T = self._state[8:].view(Mp + 1, Mp + 1)
+        return T[:Mp, :Mp].clone(), T[Mp, :Mp].clone(), T[Mp, Mp].clone(), self._state[0].clone(), self._state[1].clone()
+
+    def _num_data(self, num_data):
+        if self._rows == 0:
+            raise ValueError("the collapsed statistics are empty (R = 0): add data before solve / evaluate")
+        num_data = float(self._rows if num_data is None else num_data)
+        if not num_data > 0.0:
+            raise ValueError("num_data must be positive, got %r" % (num_data,))
+        return num_data
+
+    def _workspace(self):
+        if self._solve_ws is None:
+            self._solve_ws = _ops.collapsed_workspace(self.Mp, self.device)
+        return self._solve_ws
+
+    @staticmethod
+    def _terms(host):
+        return dict(zip(_COLLAPSED_TERMS, host))
+
+    @torch.no_grad()
+    def solve(self, num_data=None):
+        """``CollapsedResult``: the maximiser of the ELBO over q(u) for ``num_data`` (default R: the plain full-data ELBO).  One host read."""
+        num_data = self._num_data(num_data)
+        ctx = _ops.Context.get(self.device)
+        m, LS, nv, nm, scal, info = _ops.collapsed_solve(ctx, self._state, self.Mp, self._hyp, num_data, self._workspace())
+        host = torch.cat([scal, info.to(f64)]).tolist()                    # the one host read
+        code = int(host[8])
+        if code > 0:
+            raise NotPSDError("collapsed solve: I + kappa G is not positive definite at leading minor %d (kappa = %.3e)" % (code, host[6]))
+        if code != 0:
+            raise ValueError("collapsed solve: a statistic is not finite (a NaN or Inf in y, x or the directions that were added)")
+        return CollapsedResult(m, LS, nv, nm, self._terms(host[:8]), num_data)
+
+    @torch.no_grad()
+    def evaluate(self, variational_mean, chol_variational_covar, num_data=None):
+        """(loss, terms) of the full-data ELBO at the caller's float32 q(u), from the statistics alone.  One host read."""
+        num_data = self._num_data(num_data)
+        ctx = _ops.Context.get(self.device)
+        scal = _ops.collapsed_evaluate(ctx, self._state, self.Mp, variational_mean.contiguous(), chol_variational_covar.contiguous(),
+                                       self._hyp, num_data, self._workspace())
+        terms = self._terms(scal.tolist())
+        return CollapsedValue(terms["loss"], terms)
+
+
 class ElboEngine:
     """Owns the HBM workspaces of one (M', B', d, p) configuration on one GPU."""
 
@@ -1343,6 +1510,51 @@ class ElboEngine:
         source = (alpha.reshape(Mp), keep(Z), keep(V) if p > 0 else None, p, keep(hyp), keep(params["constant"]), keep(self.center))
         mean = MeanPredictor(dev, mean_weights, M, d, values_only=self.data_outputs == "values", hvp_source=source)
         return VariancePredictor(dev, weights, Q, (packZ[0], packZ[1]), keep(hyp), M, d, p, mean, workspace_budget)
+
+    @torch.no_grad()
+    def collapsed_accumulator(self, params, workspace_budget=1 << 30):
+        """``CollapsedAccumulator`` of the current hyper-parameters, inducing points and directions: K_ZZ is factored once through
+        ``_factor`` (jitter ladder included) with the kernel in use -- RBF, ARD (raw_lengthscale [1, d]) or Matern-5/2 -- and the factor,
+        its inverse and the packs are copied out of the engine's buffers.  q(u) itself is not read: the accumulator computes it.  The
+        factorisation runs in the engine's factor buffers, so the evaluation cache of ``predict`` is dropped."""
+        if self.whitening == "ciq":
+            raise ValueError("the closed-form optimal q(u) is not built for CIQ whitening: its whitened basis is K^{-1/2}, not L^-1, and "
+                             "the statistics G = A A^T would need the msMINRES solves of every data column")
+        if self.shared_directions:
+            raise ValueError("the closed-form optimal q(u) is not built for the shared-directions strategy (shared_directions): its q(u) "
+                             "lives on M + p values and its middle term is zero")
+        coll = self.collective
+        if coll is not None and coll.world > 1:
+            raise ValueError("the closed-form optimal q(u) accumulates on one rank: a collective with world = %d is not built for it "
+                             "(data-parallel accumulation is a follow-up)" % coll.world)
+        matern = self._is_matern()
+        Z = params["inducing_points"]
+        if Z.dtype != f32:
+            raise ValueError("the closed-form optimal q(u) is built for float32 models, got %s" % Z.dtype)
+        d = Z.shape[1]
+        rl = params["raw_lengthscale"]
+        ard = matern or self._is_ard(params)
+        if ard and rl.numel() not in ((1, d) if matern else (d,)):
+            raise ValueError("raw_lengthscale must have %s (%d), got %d" % ("1 entry or one per input dimension" if matern else
+                                                                          "one entry per input dimension", d, rl.numel()))
+        sub = {k: params[k] for k in ("inducing_points", "inducing_directions", "raw_outputscale", "raw_noise")}
+        sub["raw_lengthscale"] = rl.reshape(1, -1).expand(1, d).contiguous() if ard else rl
+        ctx = _ops.Context.get(self.device)
+        self._eval_cache = None
+        self._ard, self._matern = ard, matern
+        try:
+            hyp, packZ, L, dims = self._factor(ctx, sub, sync=True)
+            ell = self._ard_ell.detach().clone() if ard else None
+        finally:
+            self._ard = self._matern = False
+        Mp = dims[3]
+        if Mp > _ops.COLLAPSED_MAX_MP:
+            raise ValueError("the closed-form optimal q(u) takes M' <= %d (explicit-inverse regime of the Cholesky), got %d"
+                             % (_ops.COLLAPSED_MAX_MP, Mp))
+        keep = lambda t: t.detach().clone().contiguous()
+        inverse = self._inverse_ws[:16 * Mp * Mp].clone()
+        return CollapsedAccumulator(self, keep(hyp), tuple(keep(t) for t in packZ), keep(L), dims, inverse, keep(self.center),
+                                    keep(params["constant"]).reshape(-1)[:1], ell, matern, workspace_budget)
 
     @torch.no_grad()
     def sample_paths(self, params, num_samples, num_features=2048, generator=None, base_samples=None):

@@ -359,6 +359,10 @@ class ElboEngine64(ElboEngine):
         raise NotImplementedError("the posterior-variance predictor (csrc/predict_variance.hip) is built for the float32 model mode only, "
                                   "not for float64 models; use predict()")
 
+    def collapsed_accumulator(self, params, workspace_budget=1 << 30):
+        raise NotImplementedError("the closed-form optimal q(u) (csrc/collapsed.hip) is built for the float32 model mode only, not for "
+                                  "float64 models; its statistics are float64 already")
+
     def sample_paths(self, params, num_samples, num_features=2048, generator=None, base_samples=None):
         raise NotImplementedError("pathwise posterior samples (csrc/paths.hip) are built for the float32 model mode only, not for "
                                   "float64 models; use predict_joint() and its samples")

@@ -474,6 +474,26 @@ class TrainLoop:
                 for g, lr in zip(o.param_groups, ls):
                     g["lr"] = lr
 
+    def refit_variational(self, minibatch_size=4096, data_directions=None, num_data=None, seed=None):
+        """``fit_variational`` on the loop's resident (X, Y): q(u) <- the closed-form optimum for the current hyper-parameters and
+        inducing set, with ``num_data`` the loop's own by default (the optimum of the objective the steps minimise).  The fused
+        optimiser's moments (and step counts) of the tensors it overwrote start again from zero.  Returns the result object."""
+        self.finish()
+        if self.dp is not None:
+            raise ValueError("refit_variational runs on one rank: a collective with world > 1 is not built for it")
+        if num_data is None:
+            num_data = self.mll.num_data
+        result = fit_variational(self.model, self.likelihood, (self.X, self.Y), minibatch_size=minibatch_size,
+                                 data_directions=data_directions, num_data=num_data, seed=seed)
+        for prm in self.model.variational_parameters():
+            st = self.variational_optimizer.state.get(prm)
+            if st:
+                st["step"] = 0
+                st["exp_avg"].zero_()
+                st["exp_avg_sq"].zero_()
+            prm.grad = None
+        return result
+
     def finish(self):
         """drain the replay pipeline (the status of the last replayed / deferred step is checked here)"""
         self._graph_check_previous()
@@ -508,7 +528,8 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
                    num_epochs=1, learning_rate_hypers=0.01, inducing_data_initialization=True, lr_sched=None,
                    mll_type="ELBO", gamma=0.1, fixed_inducing_locations=None, seed=None, tensors=None,
                    use_ngd=False, learning_rate_ngd=0.1, use_ciq=False, num_contour_quadrature=15, model_class=None,
-                   dfree=False, shared=False, data_directions=None, kernel="rbf", ard_num_dims=None):
+                   dfree=False, shared=False, variational_initialization=None, data_directions=None, kernel="rbf",
+                   ard_num_dims=None):
     """Everything ``train_gp`` does before its loop (directional_vi.py:130-219); returns a TrainLoop.
     ``inducing_data_initialization``: True (the first M data rows), False (uniform draws), or "kmeans" -- k-means centroids and gradient
     directions from the training tensors (``_kmeans_start``; one rank; ``fixed_inducing_locations`` wins over it).
@@ -517,8 +538,12 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
     ``ard_num_dims`` (int, default None = one scalar lengthscale): one lengthscale per input dimension (must equal the input
     dimension) -- the engine's ARD step: Cholesky-whitened per-point model, float32, one rank.
     ``data_directions`` (int, default None = ``num_directions``): derivative columns of y per minibatch point, whatever the number of
-    inducing directions (0: function values only; ``dim``: the full gradient) -- the engine's rectangular training step."""
+    inducing directions (0: function values only; ``dim``: the full gradient) -- the engine's rectangular training step.
+    ``variational_initialization`` (None, the default: q(u) = N(1e-3 randn, I) as the reference; or "optimal"): one
+    ``TrainLoop.refit_variational`` before the first step -- q(u) starts at the closed-form optimum for the initial hyper-parameters."""
     assert num_directions == minibatch_dim
+    if variational_initialization not in (None, "optimal"):
+        raise ValueError("variational_initialization must be None or 'optimal', got %r" % (variational_initialization,))
     if isinstance(inducing_data_initialization, str):
         if inducing_data_initialization != "kmeans":
             raise ValueError("inducing_data_initialization must be True, False or 'kmeans', got %r" % (inducing_data_initialization,))
@@ -652,6 +677,8 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
                              % (min(dim, 95), data_directions))
         if data_directions != num_directions:            # (equal counts: today's step, nothing to set)
             loop.data_directions = model.data_directions = data_directions
+    if variational_initialization == "optimal":
+        loop.refit_variational(data_directions=data_directions, seed=seed)
     return loop
 
 
@@ -683,7 +710,8 @@ def train_gp(train_dataset, num_inducing=128,
       on all ranks under torch.distributed; broadcast from rank 0 when omitted);
       ``max_steps`` (int): stop after this many optimisation steps;
       ``ard_num_dims`` (int, the input dimension): one lengthscale per input dimension (``setup_training``);
-      ``kernel`` ("rbf" or "matern52"): the covariance family (``setup_training``).
+      ``kernel`` ("rbf" or "matern52"): the covariance family (``setup_training``);
+      ``variational_initialization`` (None or "optimal"): start q(u) at its closed-form optimum (``setup_training``).
     """
     assert num_directions == minibatch_dim
     loop = setup_training(train_dataset, num_inducing, num_directions, minibatch_size, minibatch_dim, num_epochs,
@@ -692,7 +720,7 @@ def train_gp(train_dataset, num_inducing=128,
                           learning_rate_ngd=learning_rate_ngd, use_ciq=use_ciq,
                           num_contour_quadrature=num_contour_quadrature, model_class=args.get("_model_class"),
                           shared=bool(args.get("_shared")), data_directions=data_directions, kernel=args.get("kernel", "rbf"),
-                          ard_num_dims=args.get("ard_num_dims"))
+                          ard_num_dims=args.get("ard_num_dims"), variational_initialization=args.get("variational_initialization"))
     n_samples = loop.X.shape[0]
     stride = (num_directions if loop.data_directions is None else loop.data_directions) + 1      # outputs per minibatch point
     max_steps = args.get("max_steps")
@@ -720,6 +748,61 @@ def train_gp(train_dataset, num_inducing=128,
         print(f"Done! loss: {loss.item()}")
         print("\nDone Training!")
     return loop.model, loop.likelihood
+
+
+def fit_variational(model, likelihood, dataset_or_tensors, minibatch_size=4096, data_directions=None, num_data=None, seed=None,
+                    workspace_budget=1 << 30):
+    """q(u) <- the maximiser of the ELBO over q(u) for the model's current hyper-parameters, inducing points and directions (Titsias
+    2009; ``ElboEngine.collapsed_accumulator``), from ONE pass over the data in chunks of ``minibatch_size`` points.
+    ``dataset_or_tensors``: a Dataset of (x[d], y[d+1]) pairs or resident (X, Y) tensors.  ``data_directions``: None -- the model's
+    ``num_directions`` canonical derivative columns per chunk, drawn as ``select_cols_of_y`` draws them (from ``random.Random(seed)``, or
+    the global ``random`` without a seed); an int -- that many; "all" -- the full gradient (d <= 95).  Scalar targets: values only.
+    ``num_data`` defaults to the harness's own, (dim + 1) n_samples, so the optimum is that of the objective ``train_gp`` minimises.
+    ``workspace_budget``: bytes of chunk workspace of the accumulator (a chunk of ``minibatch_size`` points is cut further to fit it).
+    Writes (m*, L_S*) -- or (natural_vec, natural_mat) of a NaturalVariationalDistribution -- into the model and returns the result
+    object (``variational_mean``, ``chol_variational_covar``, ``natural_vec``, ``natural_mat``, ``loss``, ``terms``)."""
+    vs = model.variational_strategy
+    device = vs.inducing_points.device
+    if isinstance(dataset_or_tensors, (tuple, list)) and len(dataset_or_tensors) == 2 and torch.is_tensor(dataset_or_tensors[0]):
+        X, Y = (t.to(device) for t in dataset_or_tensors)
+    else:
+        X, Y = _dataset_tensors(dataset_or_tensors, device, vs.inducing_points.dtype)
+    if Y.dim() == 1:
+        Y = Y.reshape(-1, 1)
+    n_samples, dim = X.shape
+    if hasattr(vs, "_maybe_init"):
+        vs._maybe_init()                                  # (a later first training call must not re-initialise what is written here)
+    acc = model.engine.collapsed_accumulator(model._param_dict(likelihood), workspace_budget=workspace_budget)
+    if Y.shape[1] == 1:
+        pd = 0
+    elif data_directions is None:
+        pd = int(model.num_directions)
+    elif data_directions == "all":
+        pd = dim
+    else:
+        pd = int(data_directions)
+    if Y.shape[1] not in (1, dim + 1) or not 0 <= pd <= min(dim, 95) or (pd > 0 and Y.shape[1] == 1):
+        raise ValueError("fit_variational takes targets with 1 or dim + 1 = %d columns and 0 <= data_directions <= min(dim, 95) = %d, "
+                         "got %d columns and %d directions" % (dim + 1, min(dim, 95), Y.shape[1], pd))
+    rng = random.Random(seed) if seed is not None else random
+    E_canonical = torch.eye(dim, device=device, dtype=X.dtype)
+    minibatch_size = max(1, int(minibatch_size))
+    for start in range(0, n_samples, minibatch_size):
+        x_batch = X[start:start + minibatch_size]
+        idx_y = list(range(dim + 1)) if pd == dim else sorted(rng.sample(range(1, dim + 1), pd) + [0])
+        y_batch = Y[start:start + minibatch_size][:, idx_y].reshape(-1)
+        D = E_canonical[[c - 1 for c in idx_y[1:]]].repeat(x_batch.shape[0], 1) if pd else None
+        acc.add(x_batch, y_batch, D)
+    result = acc.solve((dim + 1) * n_samples if num_data is None else num_data)
+    vd = vs._variational_distribution
+    with torch.no_grad():
+        if isinstance(vd, NaturalVariationalDistribution):
+            vd.natural_vec.copy_(result.natural_vec)
+            vd.natural_mat.copy_(result.natural_mat)
+        else:
+            vd.variational_mean.copy_(result.variational_mean)
+            vd.chol_variational_covar.copy_(result.chol_variational_covar)
+    return result
 
 
 def eval_gp(test_dataset, model, likelihood,

@@ -382,6 +382,13 @@ class ApproximateGP(torch.nn.Module):
                 for p in mod.parameters(recurse=False):
                     yield p
 
+    def fit_variational(self, likelihood, dataset_or_tensors, minibatch_size=4096, data_directions=None, num_data=None, seed=None):
+        """q(u) <- its closed-form optimum for the current hyper-parameters and inducing set, from one pass over the data: the method
+        form of ``directional_vi.fit_variational`` (Titsias 2009; ``ElboEngine.collapsed_accumulator``).  Returns the result object."""
+        from .directional_vi import fit_variational
+        return fit_variational(self, likelihood, dataset_or_tensors, minibatch_size=minibatch_size, data_directions=data_directions,
+                               num_data=num_data, seed=seed)
+
     # ---- posterior mean without the predictive distribution (what the reference's mean-only callers read from
     #      ``likelihood(model(x, derivative_directions=D)).mean``: experiments/bunny/exp_bunny.py:189-195,
     #      experiments/rover/bo_traditional.py:214, experiments/GNN_bo/bo.py:172) ----

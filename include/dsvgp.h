@@ -1011,6 +1011,42 @@ int dsvgp_acq_descend(dsvgp_ctx* ctx, const float* mean_weights, const float* va
                       int kind, const float* beta, const float* best, int maximize, int iterations, float initial_step, int resume,
                       float* values, float* grads, float* steps, int* accepted, void* workspace);
 
+/* ---- closed-form optimal q(u) (Titsias 2009) from one-pass statistics, and the full-data ELBO of any q(u) (csrc/collapsed.hip,
+ * DESIGN.md section 23).  With the Gaussian likelihood and fixed hyper-parameters / inducing points the maximiser of the ELBO over q(u) is
+ *   B = I + kappa G,  S* = B^-1,  m* = kappa B^-1 b,  kappa = num_data / (R noise),   G = sum A A^T, b = sum A r, yy = sum r^T r, r = y - c
+ * in the whitened basis A = L^-1 K_ZX, R = rows accumulated.  The statistics live in a caller-owned `state` of
+ * dsvgp_collapsed_state_bytes(Mp) bytes (8-byte aligned): doubles [0] = sum of the prior diagonal, [1] = R, [2..7] reserved, then the
+ * row-major (Mp+1) x (Mp+1) matrix tril([A ; r^T][A ; r^T]^T): rows < Mp hold tril G, row Mp holds b^T and, last, yy; its strict upper
+ * triangle stays zero.
+ *   dsvgp_collapsed_reset       state <- 0 (one memset).
+ *   dsvgp_collapsed_accumulate  A64: (Mp + 1) x Bp doubles, leading dimension lda >= Bp, rows < Mp = A as dsvgp_trsm wrote it (X64); row Mp
+ *                               is WRITTEN here: r = y - constant[0] in float64.  Then the matrix += tril([A ; r^T][A ; r^T]^T) in place on the
+ *                               fp64 MFMA GEMM (beta = 1; its split-K slices meet in fp64 atomics on the live state: run-order rounding of G,
+ *                               b and yy), and [0] += sum prior_diag[Bp], [1] += Bp in one launch with a fixed summation order (no atomics).
+ *                               prior_diag: dsvgp_kernel_diag / _ard / _matern52 of the chunk (without the 1e-4 jitter).  Bp = 0: returns 0,
+ *                               nothing is touched.
+ *   dsvgp_collapsed_solve       the optimum for hyp[2] = noise and num_data (> 0): m[Mp], LS[Mp, ldls] = chol(S*) (lower, strict upper triangle
+ *                               exactly zero), nat_vec[Mp] = kappa b, nat_mat[Mp, ldnm] = -B / 2 (exactly symmetric) as float32 -- gpytorch's
+ *                               natural parameters -- and scalars[8] (float64): loss, sum ll, KL, sum |residual|^2, sum varn at the optimum,
+ *                               then R, kappa, tr G.  loss = -(sum ll / R - KL / num_data), the objective of dsvgp_likelihood_terms +
+ *                               dsvgp_kl_terms with all R rows as one batch.  J B J = Lt Lt^T is factored by dsvgp_potrf_inverse (J = exchange
+ *                               matrix) and chol(S*) = J Lt^-T J is read off its inverse: no second factorisation.  Every output pointer may be
+ *                               NULL.  *info (device int): 0, k > 0 (leading minor k of J B J not positive definite), -1 (a non-finite
+ *                               statistic), -2 (R = 0); with info != 0 the float outputs and scalars[0..4] are NaN.  Never reads the host.
+ *   dsvgp_collapsed_evaluate    scalars[8] as above for the caller's float32 (m, tril LS): <S, G> = sum(G L_S o L_S) with G L_S on the fp64 MFMA
+ *                               GEMM, m^T G m, KL -- float64 arithmetic, fixed summation orders, no M' x B' object.
+ * `workspace`: dsvgp_collapsed_workspace_bytes(Mp) bytes, 16-byte aligned, for solve and evaluate.  DSVGP_EINVAL: a null required pointer,
+ * Mp <= 0, Mp > 8192 (solve / evaluate: the explicit-inverse regime), lda < Bp, ldls / ldnm < Mp, num_data <= 0 -- nothing is touched.   */
+size_t dsvgp_collapsed_state_bytes(int Mp);
+size_t dsvgp_collapsed_workspace_bytes(int Mp);
+int dsvgp_collapsed_reset(dsvgp_ctx* ctx, void* state, int Mp);
+int dsvgp_collapsed_accumulate(dsvgp_ctx* ctx, void* state, int Mp, double* A64, int64_t lda, int Bp, const float* y,
+                               const float* constant, const float* prior_diag);
+int dsvgp_collapsed_solve(dsvgp_ctx* ctx, const void* state, int Mp, const float* hyp, double num_data, float* m, float* LS, int64_t ldls,
+                          float* nat_vec, float* nat_mat, int64_t ldnm, double* scalars, int* info, void* workspace);
+int dsvgp_collapsed_evaluate(dsvgp_ctx* ctx, const void* state, int Mp, const float* m, const float* LS, int64_t ldls, const float* hyp,
+                             double num_data, double* scalars, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
