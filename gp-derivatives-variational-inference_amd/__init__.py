@@ -18,9 +18,9 @@ from . import grad_svgp  # noqa: F401
 from . import dfree_directional_vi  # noqa: F401
 from . import shared_directional_vi  # noqa: F401
 from . import traditional_vi  # noqa: F401
-from ._step import CollapsedAccumulator, CollapsedResult, ElboEngine, MeanPredictor, NotPSDError, PathDescent, SamplePaths, VariancePredictor, NGD_PARAM_NAMES, PARAM_NAMES  # noqa: F401
+from ._step import COLLAPSED_GRAD_NAMES, CollapsedAccumulator, CollapsedResult, ElboEngine, MeanPredictor, NotPSDError, PathDescent, SamplePaths, VariancePredictor, NGD_PARAM_NAMES, PARAM_NAMES  # noqa: F401
 from ._step64 import ElboEngine64  # noqa: F401
-from .directional_vi import GPModel, TrainLoop, acquisition_candidates, eval_gp, eval_gradient_nll, eval_gradients, eval_mean, eval_paths, eval_values, fit_variational, select_cols_of_y, setup_training, thompson_candidates, train_gp  # noqa: F401
+from .directional_vi import GPModel, TrainLoop, acquisition_candidates, collapsed_loss_and_grads, eval_gp, eval_gradient_nll, eval_gradients, eval_mean, eval_paths, eval_values, fit_variational, select_cols_of_y, setup_training, thompson_candidates, train_collapsed, train_gp  # noqa: F401
 from . import initialization  # noqa: F401
 from .initialization import KMeansResult, gradient_directions, initialize_inducing, kmeans_inducing_points  # noqa: F401
 from .gp_shim import (GaussianLikelihood, NaturalVariationalDistribution, PredictiveLogLikelihood,  # noqa: F401

@@ -241,6 +241,10 @@ SIGNATURES = {
     "dsvgp_collapsed_accumulate": (_i, [_p, _p, _i, _p, _l, _i, _p, _p, _p]),
     "dsvgp_collapsed_solve": (_i, [_p, _p, _i, _p, _d, _p, _p, _l, _p, _p, _l, _p, _p, _p]),
     "dsvgp_collapsed_evaluate": (_i, [_p, _p, _i, _p, _p, _l, _p, _d, _p, _p]),
+    "dsvgp_collapsed_grad_workspace_bytes": (_z, [_i]),
+    "dsvgp_collapsed_grad_chunk_bytes": (_z, [_i, _i]),
+    "dsvgp_collapsed_grad_prepare": (_i, [_p, _p, _i, _p, _p, _l, _p, _p, _d, _p, _p, _l, _p, _l, _p, _p, _p]),
+    "dsvgp_collapsed_grad_chunk": (_i, [_p, _i, _i, _p, _l, _p, _p, _p, _l, _p, _p, _p, _l, _p, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

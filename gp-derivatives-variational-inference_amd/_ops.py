@@ -2022,3 +2022,71 @@ def collapsed_evaluate(ctx, state, Mp, m, LS, hyp, num_data, workspace):
     check(lib.dsvgp_collapsed_evaluate(ctx.h, _ptr(state), int(Mp), _ptr(m), _ptr(LS), _ld(LS), _ptr(hyp), float(num_data), _ptr(scal),
                                        _ptr(workspace)), "dsvgp_collapsed_evaluate")
     return scal
+
+
+# ---- gradients of the collapsed bound at the optimum (csrc/collapsed.hip) --------------------------------
+COLLAPSED_ADJOINTS = ("w", "d_noise", "d_diag", "loss", "residual", "varn", "kappa", "rows")
+
+
+def collapsed_grad_workspace_bytes(Mp):
+    """bytes of ``collapsed_grad_prepare``'s workspace (pure host arithmetic); 0 for an M' it does not take"""
+    return int(lib.dsvgp_collapsed_grad_workspace_bytes(int(Mp)))
+
+
+def collapsed_grad_chunk_bytes(Mp, Bp):
+    """bytes of ``collapsed_grad_chunk``'s workspace (pure host arithmetic); 0 for refused arguments"""
+    return int(lib.dsvgp_collapsed_grad_chunk_bytes(int(Mp), int(Bp)))
+
+
+def collapsed_grad_prepare(ctx, state, Mp, m, LS, inverse, hyp, num_data, workspace=None):
+    """(alpha [M'], Q [M', M'], K~-bar [M', M'], adj [8] float64, info int32[1]) of the optimum (m, LS) that ``collapsed_solve`` returned
+    for the same statistics, hyp and num_data; ``inverse``: L^-1 | L^-T (2 M'^2 doubles, as bytes or float64).  Nothing is read."""
+    _req_collapsed_state(state, Mp)
+    _req(m, f32, "variational_mean", 1)
+    _req(LS, f32, "chol_variational_covar", 2)
+    if m.numel() != Mp or LS.shape != (Mp, Mp):
+        raise ValueError("variational_mean / chol_variational_covar must be [%d] / [%d, %d]" % (Mp, Mp, Mp))
+    if inverse.numel() * inverse.element_size() < 16 * Mp * Mp:
+        raise ValueError("inverse must hold L^-1 | L^-T: 2 M'^2 = %d doubles" % (2 * Mp * Mp))
+    nbytes = collapsed_grad_workspace_bytes(Mp)
+    if nbytes == 0:
+        raise ValueError("the collapsed gradients take 1 <= M' <= %d, got %d" % (COLLAPSED_MAX_MP, Mp))
+    dev = state.device
+    if workspace is None or workspace.numel() < nbytes:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    alpha = torch.empty(Mp, dtype=f64, device=dev)
+    ldq = (Mp + 1) & ~1                    # an even leading dimension: the per-chunk product reads Q 16 bytes at a time also at odd M'
+    Q = torch.empty(Mp, ldq, dtype=f64, device=dev)[:, :Mp]
+    Kb = torch.empty(Mp, Mp, dtype=f64, device=dev)
+    adj = torch.empty(8, dtype=f64, device=dev)
+    info = torch.empty(1, dtype=torch.int32, device=dev)
+    check(lib.dsvgp_collapsed_grad_prepare(ctx.h, _ptr(state), int(Mp), _ptr(m), _ptr(LS), _ld(LS), _ptr(inverse), _ptr(hyp),
+                                           float(num_data), _ptr(alpha), _ptr(Q), ldq, _ptr(Kb), Mp, _ptr(adj), _ptr(info),
+                                           _ptr(workspace)), "dsvgp_collapsed_grad_prepare")
+    return alpha, Q, Kb, adj, info
+
+
+def collapsed_grad_chunk(ctx, Mp, Kzx, y, constant, Q, alpha, adj, K_bar, diag_bar, rho_sum, workspace):
+    """K_bar [M', B'] (float32) = 2 w (Q Kzx - alpha rho^T) of one chunk, diag_bar [B'] (or None) = dg-bar, rho_sum[0] += sum rho.  Every
+    buffer is the caller's: no allocation, no host read"""
+    _req(Kzx, f32, "Kzx", 2)
+    _req(K_bar, f32, "K_bar", 2)
+    Bp = Kzx.shape[1]
+    if Kzx.shape[0] != Mp or K_bar.shape != Kzx.shape:
+        raise ValueError("Kzx and K_bar must both be [M', B'] = [%d, B'], got %s and %s" % (Mp, tuple(Kzx.shape), tuple(K_bar.shape)))
+    _req(y, f32, "y", 1)
+    if y.numel() != Bp or (diag_bar is not None and (diag_bar.numel() != Bp or diag_bar.dtype != f32)):
+        raise ValueError("y and diag_bar must have B' = %d float32 entries" % Bp)
+    _req(constant, f32, "constant", 1)
+    _req(Q, f64, "Q", 2)
+    if Q.shape != (Mp, Mp):
+        raise ValueError("Q must be [M', M'] = [%d, %d], got %s" % (Mp, Mp, tuple(Q.shape)))
+    for t, name, numel in ((alpha, "alpha", Mp), (adj, "adj", 8), (rho_sum, "rho_sum", 1)):
+        if t.dtype != f64 or t.numel() != numel or not t.is_contiguous():
+            raise ValueError("%s must be %d contiguous float64 values" % (name, numel))
+    nbytes = collapsed_grad_chunk_bytes(Mp, Bp)
+    if nbytes == 0 or workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError("collapsed_grad_chunk needs a workspace of collapsed_grad_chunk_bytes(M', B') = %d bytes" % nbytes)
+    check(lib.dsvgp_collapsed_grad_chunk(ctx.h, int(Mp), int(Bp), _ptr(Kzx), _ld(Kzx), _ptr(y), _ptr(constant), _ptr(Q), _ld(Q), _ptr(alpha),
+                                         _ptr(adj), _ptr(K_bar), _ld(K_bar), _ptr(diag_bar), _ptr(rho_sum), _ptr(workspace)),
+          "dsvgp_collapsed_grad_chunk")

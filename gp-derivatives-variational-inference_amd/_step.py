@@ -569,6 +569,8 @@ class VariancePredictor:
 
 CollapsedValue = collections.namedtuple("CollapsedValue", "loss terms")
 _COLLAPSED_TERMS = ("loss", "log_likelihood", "kl", "residual", "varn", "rows", "kappa", "trace_G")
+# what the collapsed bound still depends on once q(u) is optimal: the keys of ``CollapsedAccumulator.finish_backward``'s gradients
+COLLAPSED_GRAD_NAMES = ("raw_lengthscale", "raw_outputscale", "raw_noise", "constant", "inducing_points", "inducing_directions")
 
 
 class CollapsedResult:
@@ -603,20 +605,27 @@ class CollapsedAccumulator:
         self._rows = 0
         self._buf = {}
         self._solve_ws = None
+        self._solved = self._bwd = None              # (num_data, rows) of the last solve; the state of a running backward pass
+        self._raw = self._shapes = None              # raw hyper-parameters and gradient shapes (set by ``collapsed_accumulator``)
 
     # ---- chunking -------------------------------------------------------------------------------
-    def row_bytes(self, pd):
+    def row_bytes(self, pd, backward=False):
         """bytes of chunk workspace per data point carrying ``pd`` directions: K_ZX (fp32), [A ; r^T] (fp64), the solve's staging rows and
-        the data pack"""
+        the data pack.  ``backward``: the chunk of ``add_backward`` instead -- K_ZX and K_ZX-bar (fp32), the kernel backward's T-bar
+        tiles (fp32), the residual's slab partials and rho (fp64), the prior diagonal with its adjoint, and the data pack"""
+        if backward:
+            slabs = (self.Mp + 255) // 256
+            per_col = 3 * 4 * self.Mp + 8 * (slabs + 1) + 8 + 4 * (_ops.packed_width(self.d) + 3)
+            return per_col * (int(pd) + 1)
         nb = 64
         while nb < min(self._nb, self.Mp):
             nb *= 2
         per_col = 4 * self.Mp + 8 * (self.Mp + 1) + 8 * nb + 4 * (_ops.packed_width(self.d) + 3)
         return per_col * (int(pd) + 1)
 
-    def chunk_rows(self, pd):
+    def chunk_rows(self, pd, backward=False):
         """data points per chunk at ``pd`` directions per point under the workspace budget (at least one)"""
-        return max(1, self.workspace_budget // self.row_bytes(pd))
+        return max(1, self.workspace_budget // self.row_bytes(pd, backward))
 
     def _get(self, name, numel, dtype):
         t = self._buf.get(name)
@@ -634,12 +643,16 @@ class CollapsedAccumulator:
     def reset(self):
         _ops.collapsed_reset_(_ops.Context.get(self.device), self._state, self.Mp)
         self._rows = 0
+        self._solved = self._bwd = None
 
-    @torch.no_grad()
-    def add(self, x, y, D=None):
-        """statistics += those of the points ``x`` [B, d] with targets ``y`` [B (pd + 1)] (interleaved) and directions ``D`` [B pd, d]
-        (None: values only), in row chunks that fit the budget.  K_ZX always comes from the rectangular assembly, so a chunk's bits do
-        not depend on where the chunks are cut; no host read."""
+    def _no_open_backward(self, what):
+        """a backward pass belongs to the statistics and the solve it began with: neither may move before it is finished"""
+        if self._bwd is not None:
+            raise ValueError("%s() between begin_backward and finish_backward: the gradients hold only for the statistics and the solve "
+                             "the pass began with -- finish the backward pass, begin a new one or reset() first" % what)
+
+    def _check_data(self, x, y, D):
+        """(B, pd) of one ``add`` / ``add_backward`` call, or the error that names what is wrong with it"""
         if x.dim() != 2 or x.shape[1] != self.d:
             raise ValueError("x must be [B, %d], got %s" % (self.d, tuple(x.shape)))
         B = x.shape[0]
@@ -655,6 +668,15 @@ class CollapsedAccumulator:
         for t, name in ((x, "x"), (y, "y")) + (((D, "D"),) if pd else ()):
             if t.dtype != f32 or not t.is_cuda:
                 raise TypeError("%s must be a float32 tensor on the GPU" % name)
+        return B, pd
+
+    @torch.no_grad()
+    def add(self, x, y, D=None):
+        """statistics += those of the points ``x`` [B, d] with targets ``y`` [B (pd + 1)] (interleaved) and directions ``D`` [B pd, d]
+        (None: values only), in row chunks that fit the budget.  K_ZX always comes from the rectangular assembly, so a chunk's bits do
+        not depend on where the chunks are cut; no host read."""
+        self._no_open_backward("add")
+        B, pd = self._check_data(x, y, D)
         if B == 0:
             return self
         ctx = _ops.Context.get(self.device)
@@ -712,6 +734,7 @@ class CollapsedAccumulator:
     @torch.no_grad()
     def solve(self, num_data=None):
         """``CollapsedResult``: the maximiser of the ELBO over q(u) for ``num_data`` (default R: the plain full-data ELBO).  One host read."""
+        self._no_open_backward("solve")
         num_data = self._num_data(num_data)
         ctx = _ops.Context.get(self.device)
         m, LS, nv, nm, scal, info = _ops.collapsed_solve(ctx, self._state, self.Mp, self._hyp, num_data, self._workspace())
@@ -721,6 +744,7 @@ class CollapsedAccumulator:
             raise NotPSDError("collapsed solve: I + kappa G is not positive definite at leading minor %d (kappa = %.3e)" % (code, host[6]))
         if code != 0:
             raise ValueError("collapsed solve: a statistic is not finite (a NaN or Inf in y, x or the directions that were added)")
+        self._solved = (num_data, self._rows)
         return CollapsedResult(m, LS, nv, nm, self._terms(host[:8]), num_data)
 
     @torch.no_grad()
@@ -732,6 +756,150 @@ class CollapsedAccumulator:
                                        self._hyp, num_data, self._workspace())
         terms = self._terms(scal.tolist())
         return CollapsedValue(terms["loss"], terms)
+
+    # ---- gradients of the collapsed bound -------------------------------------
+    @torch.no_grad()
+    def begin_backward(self, result):
+        """Start the second pass: the gradients of the collapsed loss l_c(theta) = loss(m*(theta), L_S*(theta); theta) with respect to
+        hyper-parameters, inducing points and directions.  ``result`` must be what ``solve`` last returned for THESE statistics: by the
+        envelope theorem the total derivative equals the partial one at the fixed whitened optimum, which holds at no other q(u).
+        Queues alpha = L^-T m, Q = L^-T (S - I) L^-1, K~-bar and the scalar adjoints (dsvgp_collapsed_grad_prepare); no host read."""
+        if not isinstance(result, CollapsedResult):
+            raise TypeError("begin_backward takes the CollapsedResult of solve(), got %s" % type(result).__name__)
+        solved = self._solved
+        if solved is None or solved[1] != self._rows:
+            raise ValueError("begin_backward needs the result of a solve() of the current statistics (R = %d): call solve() after the "
+                             "last add()" % self._rows)
+        if float(result.num_data) != solved[0] or int(result.terms["rows"]) != self._rows:
+            raise ValueError("begin_backward: the result was solved for num_data = %r on %d rows, the accumulator's last solve for "
+                             "num_data = %r on %d rows -- the gradients hold only at the optimum of the same statistics"
+                             % (result.num_data, int(result.terms["rows"]), solved[0], self._rows))
+        m, LS = result.variational_mean, result.chol_variational_covar
+        for t, name, shape in ((m, "variational_mean", (self.Mp,)), (LS, "chol_variational_covar", (self.Mp, self.Mp))):
+            if not t.is_cuda or t.dtype != f32:
+                raise TypeError("%s must be a float32 tensor on the GPU" % name)
+            if tuple(t.shape) != shape:
+                raise ValueError("%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
+        ctx = _ops.Context.get(self.device)
+        dev, M, d, p = self.device, self.M, self.d, self.p
+        ws = self._buf.get("grad_ws")
+        if ws is None:
+            ws = self._buf["grad_ws"] = torch.empty(_ops.collapsed_grad_workspace_bytes(self.Mp), dtype=torch.uint8, device=dev)
+        alpha, Q, Kzz_bar, adj, info = _ops.collapsed_grad_prepare(ctx, self._state, self.Mp, m.contiguous(), LS.contiguous(), self._inv,
+                                                                   self._hyp, solved[0], ws)
+        self._bwd = {"alpha": alpha, "Q": Q, "Kzz_bar": Kzz_bar, "adj": adj, "info": info, "rows": 0, "points": 0,
+                     "rho_sum": torch.zeros(1, dtype=f64, device=dev),
+                     "dZ": torch.zeros(M, d, dtype=f32, device=dev), "dV": torch.zeros(M * p, d, dtype=f32, device=dev),
+                     "d_hyp": torch.zeros(4, dtype=f32, device=dev),
+                     "d_ell": torch.zeros(d, dtype=f32, device=dev) if self._ell is not None else None}
+        return self
+
+    def _kernel_bwd_bytes(self, n2, p2, symmetric):
+        M, d, p = self.M, self.d, self.p
+        if self._matern:
+            return _ops.kernel_bwd_matern52_workspace_bytes(M, p, n2, p2, d)
+        if self._ell is not None:
+            return _ops.kernel_bwd_ard_workspace_bytes(M, p, n2, p2, d)
+        if symmetric:
+            return int(_lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, n2, d, p))
+        return _ops.kernel_bwd_rect_workspace_bytes(M, p, n2, p2, d)
+
+    @torch.no_grad()
+    def add_backward(self, x, y, D=None):
+        """The second pass over the data of ``add`` (same arguments, same checks, any chunking of the calls): per chunk the assembly of
+        ``add``, K_ZX-bar = 2 w (Q K_ZX - alpha rho^T) in one C call (dsvgp_collapsed_grad_chunk) and the kernel backward with the
+        inducing side as side 1, accumulated in call order into the gradients of the inducing points, the directions and the kernel
+        hyper-parameters; ARD / Matern: the prior diagonal's backward per chunk.  No host read."""
+        st = self._bwd
+        if st is None:
+            raise ValueError("add_backward needs begin_backward(result) first")
+        B, pd = self._check_data(x, y, D)
+        if B == 0:
+            return self
+        ctx = _ops.Context.get(self.device)
+        M, d, p, Mp, q = self.M, self.d, self.p, self.Mp, pd + 1
+        rows = self.chunk_rows(pd, backward=True)
+        fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
+        dZ, dV, d_hyp, d_ell = st["dZ"], st["dV"], st["d_hyp"], st["d_ell"]
+        y = y.contiguous()
+        nmax = min(rows, B)
+        kws = self._get("kbwd_ws", self._kernel_bwd_bytes(nmax, pd, False), torch.uint8)
+        cws = self._get("cgrad_ws", _ops.collapsed_grad_chunk_bytes(Mp, nmax * q) // 8, f64)
+        for r0 in range(0, B, rows):
+            nb_ = min(rows, B - r0)
+            Bp = nb_ * q
+            xc = x[r0:r0 + nb_].contiguous()
+            Dc = D[r0 * pd:(r0 + nb_) * pd].contiguous() if pd else None
+            diag = dbar = None
+            if self._ell is not None:
+                packX = _ops.pack_points_ard(ctx, xc, Dc, pd, self._ell, self._center)
+                diag = (_ops.kernel_diag_matern52 if self._matern else _ops.kernel_diag_ard)(ctx, packX, nb_, pd, d, self._hyp)
+                dbar = self._get("diag_bar", Bp, f32)
+            else:
+                packX = _ops.pack_points(ctx, xc, Dc, pd, self._hyp, self._center)
+            ld = (Bp + 3) // 4 * 4                   # rows 16-byte addressable: the product's float operand takes the vector-load kernels
+            Kzx = fwd(ctx, self._packZ, M, p, packX, nb_, pd, d, self._hyp, out=self._get("Kzx", Mp * ld, f32).view(Mp, ld)[:, :Bp])
+            Kbar = self._get("Kbar", Mp * ld, f32).view(Mp, ld)[:, :Bp]
+            _ops.collapsed_grad_chunk(ctx, Mp, Kzx, y[r0 * q:(r0 + nb_) * q], self._constant, st["Q"], st["alpha"], st["adj"], Kbar, dbar,
+                                      st["rho_sum"], cws)
+            if self._ell is not None:
+                bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
+                bwd(ctx, Kbar, self._packZ, M, p, packX, nb_, pd, d, self._ell, self._hyp, False, dZ, dV if p > 0 else None, d_ell, d_hyp, kws)
+                diag_bwd = _ops.kernel_diag_matern52_bwd if self._matern else _ops.kernel_diag_ard_bwd
+                diag_bwd(ctx, packX, nb_, pd, d, self._ell, self._hyp, diag, dbar, d_ell, d_hyp)
+            else:
+                _ops.kernel_bwd_rect(ctx, Kbar, self._packZ, M, p, packX, nb_, pd, d, self._hyp, dZ, dV, d_hyp, kws)
+        st["rows"] += B * q
+        st["points"] += B
+        return self
+
+    @torch.no_grad()
+    def finish_backward(self):
+        """(loss, grads): the collapsed loss at the optimum (float64 host scalar) and its gradients under the keys and shapes of
+        ``loss_and_grads`` -- raw_lengthscale, raw_outputscale, raw_noise, constant, inducing_points, inducing_directions.  Adds the
+        symmetric kernel backward of K~-bar (the jitter carries no gradient), the prior diagonal's, the noise and the constant terms,
+        and maps to the raw parameters.  One host read (status, loss and the sum of the residuals)."""
+        st = self._bwd
+        if st is None:
+            raise ValueError("finish_backward needs begin_backward(result) and the add_backward pass first")
+        if st["rows"] != self._rows:
+            raise ValueError("finish_backward: add_backward has seen %d rows, the statistics hold R = %d: the second pass must cover the "
+                             "data of the first" % (st["rows"], self._rows))
+        ctx = _ops.Context.get(self.device)
+        dev, M, d, p = self.device, self.M, self.d, self.p
+        dZ, dV, d_hyp, d_ell, adj = st["dZ"], st["dV"], st["d_hyp"], st["d_ell"], st["adj"]
+        kws = self._get("kbwd_ws", self._kernel_bwd_bytes(M, p, True), torch.uint8)
+        if self._ell is not None:
+            bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
+            bwd(ctx, st["Kzz_bar"], self._packZ, M, p, self._packZ, M, p, d, self._ell, self._hyp, True, dZ, dV if p > 0 else None, d_ell,
+                d_hyp, kws)
+        else:
+            _ops.kernel_bwd(ctx, st["Kzz_bar"], self._packZ, M, self._packZ, M, d, p, self._hyp, True, dZ, dV, d_hyp, kws)
+            # the scalar RBF prior diagonal s [1, 1 / ell^2, ...]: dg-bar = w on every entry, in closed form
+            ell, s, n_der = self._hyp[0].to(f64), self._hyp[1].to(f64), float(st["rows"] - st["points"])
+            d_hyp[0] += (adj[2] * s * n_der * (-2.0) / (ell * ell * ell)).to(f32)
+            d_hyp[1] += (adj[2] * (float(st["points"]) + n_der / (ell * ell))).to(f32)
+        d_hyp[2] += adj[1].to(f32)
+        rl, rs, rn = self._raw
+        g_l, g_s, g_n = torch.zeros_like(rl), torch.zeros_like(rs), torch.zeros_like(rn)
+        if self._ell is not None:
+            _ops.hyp_backward_ard(ctx, rl, rs, rn, d_ell, d_hyp, g_l, g_s, g_n)
+        else:
+            _ops.hyp_backward(ctx, rl, rs, rn, d_hyp, g_l, g_s, g_n)
+        host = torch.cat([adj, st["rho_sum"], st["info"].to(f64)]).tolist()            # the one host read
+        self._bwd = None
+        if int(host[9]) != 0 or not all(math.isfinite(v) for v in host[:9]):
+            raise ValueError("collapsed backward: a statistic, the optimum or a residual is not finite (a NaN or Inf in y, x or the "
+                             "directions that were added)")
+        shapes = self._shapes
+        if g_l.numel() != int(torch.Size(shapes["raw_lengthscale"]).numel()):           # scalar lengthscale: d equal entries went in
+            g_l = g_l.sum(dim=-1, keepdim=True)
+        grads = {"raw_lengthscale": g_l.reshape(shapes["raw_lengthscale"]), "raw_outputscale": g_s.reshape(shapes["raw_outputscale"]),
+                 "raw_noise": g_n.reshape(shapes["raw_noise"]),
+                 "constant": (-2.0 * adj[0] * st["rho_sum"]).to(f32).reshape(shapes["constant"]),
+                 "inducing_points": dZ.reshape(shapes["inducing_points"]),
+                 "inducing_directions": dV.reshape(shapes["inducing_directions"])}
+        return host[3], grads
 
 
 class ElboEngine:
@@ -1553,8 +1721,13 @@ class ElboEngine:
                              % (_ops.COLLAPSED_MAX_MP, Mp))
         keep = lambda t: t.detach().clone().contiguous()
         inverse = self._inverse_ws[:16 * Mp * Mp].clone()
-        return CollapsedAccumulator(self, keep(hyp), tuple(keep(t) for t in packZ), keep(L), dims, inverse, keep(self.center),
-                                    keep(params["constant"]).reshape(-1)[:1], ell, matern, workspace_budget)
+        acc = CollapsedAccumulator(self, keep(hyp), tuple(keep(t) for t in packZ), keep(L), dims, inverse, keep(self.center),
+                                   keep(params["constant"]).reshape(-1)[:1], ell, matern, workspace_budget)
+        # what the backward pass maps its gradients to: the raw hyper-parameters (ARD / Matern: the [d] lengthscales that went in) and
+        # the shapes ``loss_and_grads`` returns
+        acc._raw = tuple(keep(sub[k]).reshape(-1) for k in ("raw_lengthscale", "raw_outputscale", "raw_noise"))
+        acc._shapes = {k: tuple(params[k].shape) for k in COLLAPSED_GRAD_NAMES}
+        return acc
 
     @torch.no_grad()
     def sample_paths(self, params, num_samples, num_features=2048, generator=None, base_samples=None):

@@ -323,3 +323,243 @@ extern "C" int dsvgp_collapsed_evaluate(dsvgp_ctx* ctx, const void* state, int M
     DSVGP_LAUNCH_CHECK();
     return 0;
 }
+
+// ================================================================================================================================
+// Gradients of the collapsed bound with respect to hyper-parameters and inducing points at the optimum of the same statistics
+// (DESIGN.md section 24).  Envelope: the total derivative equals the partial one at fixed whitened (m*, S*), so only the expected
+// log-likelihood contributes.  With alpha = L^-T m, Q = L^-T (S - I) L^-1, w = 1 / (2 R noise), rho = r - K^T alpha:
+//     K-bar (chunk)  = 2 w (Q K - alpha rho^T)                      K~-bar = (Q + alpha alpha^T + kappa L^-T G L^-1) / (2 num_data)
+//     dg-bar = w     c-bar = -2 w sum rho                            d/d noise = -(E + V) / (2 R noise^2) + 1 / noise
+// adj (doubles): [0] w, [1] d loss / d noise, [2] dg-bar, [3] loss, [4] E, [5] V, [6] kappa, [7] R
+namespace {
+
+constexpr int CG_NADJ = 8;
+constexpr int CG_SLAB = 256;                 // rows of K_ZX per slab of the residual's column reduction
+constexpr int CG_EROWS = 32;                 // rows of K-bar per workgroup of the epilogue
+
+struct GradLayout { size_t Gs, T, X, Y, part, scal, flags, total; int ldw; };   // prepare's workspace, in doubles
+GradLayout grad_layout(int n) {
+    GradLayout l{};
+    l.ldw = (n + 1) & ~1;
+    const size_t nn = al((size_t)n * l.ldw);
+    size_t o = 0;
+    l.Gs = o; o += nn;                       // symmetric G
+    l.T = o; o += nn;                        // S - I              -> L^-T G L^-1
+    l.X = o; o += nn;                        // L^-T (S - I)       -> L^-T G
+    l.Y = o; o += nn;                        // fp64 tril L_S      -> L^-T (S - I) L^-1
+    l.part = o; o += al((size_t)CS_NPART * n);
+    l.scal = o; o += 8;
+    l.flags = o; o += 8;
+    l.total = o;
+    return l;
+}
+
+// T = S - I in place, and the per-row partials of collapsed_finish_kernel's closed forms at the optimum.  One thread per row.
+__global__ __launch_bounds__(256) void cgrad_diag_kernel(const double* __restrict__ state, int n, const float* __restrict__ m,
+                                                         const float* __restrict__ LS, int64_t ldls, double* __restrict__ T, int ldw,
+                                                         double* __restrict__ part) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const double* St = state + CS_HEAD;
+    const int ldt = n + 1;
+    const double sii = T[(int64_t)i * ldw + i], mi = (double)m[i];
+    T[(int64_t)i * ldw + i] = sii - 1.0;
+    part[0 * n + i] = 0.0;
+    part[1 * n + i] = sii;
+    part[2 * n + i] = 0.0;
+    part[3 * n + i] = mi * mi;
+    part[4 * n + i] = mi * St[(int64_t)n * ldt + i];
+    part[5 * n + i] = St[(int64_t)i * ldt + i];
+    part[6 * n + i] = log((double)LS[(int64_t)i * ldls + i]);
+}
+
+// alpha = L^-T m from the stored transposed image of the inverse (only k >= i of its row i is read): one block per entry, fixed order
+__global__ __launch_bounds__(256) void cgrad_alpha_kernel(const double* __restrict__ DinvT, int n, const float* __restrict__ m,
+                                                          double* __restrict__ alpha) {
+    __shared__ double sh[256];
+    const int i = blockIdx.x;
+    double s = 0.0;
+    for (int k = i + threadIdx.x; k < n; k += 256) s += DinvT[(int64_t)i * n + k] * (double)m[k];
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) alpha[i] = s;
+}
+
+// Q and K~-bar, exactly symmetric, from the two raw products; block 0 also writes the scalar adjoints.  A non-finite entry raises
+// the flag (integer atomic).  One block per row.
+__global__ __launch_bounds__(256) void cgrad_final_kernel(int n, const float* __restrict__ hyp, double num_data,
+                                                          const double* __restrict__ Yq, const double* __restrict__ Zg, int ldw,
+                                                          const double* __restrict__ alpha, const double* __restrict__ scal,
+                                                          double* __restrict__ Q, int64_t ldq, double* __restrict__ Kb, int64_t ldkb,
+                                                          double* __restrict__ adj, int* __restrict__ info) {
+    const int i = blockIdx.x;
+    const double kappa = scal[6], ai = alpha[i], half = 0.5 / num_data;
+    bool bad = false;
+    for (int j = threadIdx.x; j < n; j += 256) {
+        const double q = 0.5 * (Yq[(int64_t)i * ldw + j] + Yq[(int64_t)j * ldw + i]);
+        const double z = 0.5 * (Zg[(int64_t)i * ldw + j] + Zg[(int64_t)j * ldw + i]);
+        const double k = (q + ai * alpha[j] + kappa * z) * half;
+        if (!isfinite(q) || !isfinite(k)) bad = true;
+        Q[(int64_t)i * ldq + j] = q;
+        Kb[(int64_t)i * ldkb + j] = k;
+    }
+    if (i == 0 && threadIdx.x == 0) {
+        const double R = scal[5], noise = (double)hyp[2], E = scal[3], V = scal[4];
+        const double w = 0.5 / (R * noise);
+        const double out[CG_NADJ] = {w, -(E + V) / (2.0 * R * noise * noise) + 1.0 / noise, w, scal[0], E, V, kappa, R};
+        for (int c = 0; c < CG_NADJ; ++c) {
+            if (!isfinite(out[c])) bad = true;
+            adj[c] = out[c];
+        }
+        if (!(R > 0.0)) bad = true;
+    }
+    if (bad) atomicOr(info, 1);
+}
+
+// the residual's column reduction, pass 1: part[slab][j] = sum over the slab's rows i of alpha_i K_ij, rows in ascending order.
+// One thread per column (coalesced along j), the slab's alpha in LDS.
+__global__ __launch_bounds__(256) void cgrad_reduce_kernel(const float* __restrict__ K, int64_t ldk, int Mp, int Bp,
+                                                           const double* __restrict__ alpha, double* __restrict__ part) {
+    __shared__ double sa[CG_SLAB];
+    const int i0 = blockIdx.y * CG_SLAB;
+    const int rows = (Mp - i0 < CG_SLAB) ? (Mp - i0) : CG_SLAB;
+    if ((int)threadIdx.x < rows) sa[threadIdx.x] = alpha[i0 + threadIdx.x];
+    __syncthreads();
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= Bp) return;
+    const float* col = K + (int64_t)i0 * ldk + j;
+    double s = 0.0;
+    for (int i = 0; i < rows; ++i) s += sa[i] * (double)col[(int64_t)i * ldk];
+    part[(int64_t)blockIdx.y * Bp + j] = s;
+}
+
+// pass 2: rho_j = (y_j - c) - sum over the slabs in ascending order; the constant prior-diagonal adjoint for the diagonal's backward
+__global__ __launch_bounds__(256) void cgrad_combine_kernel(const double* __restrict__ part, int nslab, int Bp, const float* __restrict__ y,
+                                                            const float* __restrict__ constant, const double* __restrict__ adj,
+                                                            double* __restrict__ rho, float* __restrict__ diag_bar) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= Bp) return;
+    double s = 0.0;
+    for (int t = 0; t < nslab; ++t) s += part[(int64_t)t * Bp + j];
+    rho[j] = ((double)y[j] - (double)constant[0]) - s;
+    if (diag_bar) diag_bar[j] = (float)adj[2];
+}
+
+// the epilogue, in place: K-bar_ij = 2 w (V_ij - alpha_i rho_j), rounded once.  Block (0, 0) alone adds sum rho onto the accumulator:
+// strided chains joined by a fixed tree, one writer.
+__global__ __launch_bounds__(256) void cgrad_epilogue_kernel(float* __restrict__ Kb, int64_t ldkb, int Mp, int Bp,
+                                                             const double* __restrict__ alpha, const double* __restrict__ rho,
+                                                             const double* __restrict__ adj, double* __restrict__ rho_sum) {
+    __shared__ double sh[256];
+    const int i0 = blockIdx.y * CG_EROWS;
+    const int rows = (Mp - i0 < CG_EROWS) ? (Mp - i0) : CG_EROWS;
+    const double w2 = 2.0 * adj[0];
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < Bp) {
+        const double rj = rho[j];
+        float* col = Kb + (int64_t)i0 * ldkb + j;
+        for (int i = 0; i < rows; ++i) col[(int64_t)i * ldkb] = (float)(w2 * ((double)col[(int64_t)i * ldkb] - alpha[i0 + i] * rj));
+    }
+    if (blockIdx.x != 0 || blockIdx.y != 0) return;
+    double s = 0.0;
+    for (int64_t t = threadIdx.x; t < Bp; t += 256) s += rho[t];
+    s = block_sum(s, sh);
+    if (threadIdx.x == 0) rho_sum[0] += s;
+}
+
+}  // namespace
+
+extern "C" size_t dsvgp_collapsed_grad_workspace_bytes(int Mp) {
+    if (Mp <= 0 || Mp > CS_MAX_MP) return 0;
+    return sizeof(double) * grad_layout(Mp).total + 64;
+}
+
+extern "C" size_t dsvgp_collapsed_grad_chunk_bytes(int Mp, int Bp) {
+    if (Mp <= 0 || Mp > CS_MAX_MP || Bp <= 0) return 0;
+    return sizeof(double) * ((size_t)cdiv(Mp, CG_SLAB) + 1) * (size_t)Bp;
+}
+
+extern "C" int dsvgp_collapsed_grad_prepare(dsvgp_ctx* ctx, const void* state, int Mp, const float* m, const float* LS, int64_t ldls,
+                                            const double* inverse, const float* hyp, double num_data, double* alpha, double* Q,
+                                            int64_t ldq, double* Kzz_bar, int64_t ldkb, double* adj, int* info, void* workspace) {
+    if (!ctx || !state || !m || !LS || !inverse || !hyp || !alpha || !Q || !Kzz_bar || !adj || !info || !workspace || Mp <= 0 ||
+        Mp > CS_MAX_MP || ldls < Mp || ldq < Mp || ldkb < Mp || !(num_data > 0.0))
+        return DSVGP_EINVAL;
+    if (((uintptr_t)state % 8) || ((uintptr_t)inverse % 8) || ((uintptr_t)alpha % 8) || ((uintptr_t)Q % 8) || ((uintptr_t)Kzz_bar % 8) ||
+        ((uintptr_t)adj % 8) || ((uintptr_t)workspace % 16))
+        return DSVGP_EALIGN;
+    const int n = Mp;
+    const GradLayout l = grad_layout(n);
+    const double* st = (const double*)state;
+    double* ws = (double*)workspace;
+    hipStream_t s = ctx->stream;
+    hipError_t e = hipMemsetAsync(info, 0, sizeof(int), s);
+    if (e != hipSuccess) return 1000 + (int)e;
+    hipLaunchKernelGGL(collapsed_widen_kernel, dim3(n), dim3(256), 0, s, st, n, LS, ldls, ws + l.Gs, ws + l.Y, l.ldw);
+    DSVGP_LAUNCH_CHECK();
+    auto product = [&](const double* A, int64_t lda, const double* B, int64_t ldb, double* C, int flags) {
+        GemmArgs g{};
+        g.M = n; g.N = n; g.K = n;
+        g.A = A; g.B = B; g.C = C;
+        g.lda = lda; g.ldb = ldb; g.ldc = l.ldw;
+        g.alpha = 1.0; g.beta = 0.0; g.flags = flags;
+        g.batch = 1; g.splitk = 1;
+        g.slab = ctx->det_slab; g.slab_bytes = ctx->det_bytes;
+        return launch_gemm(s, 1, g);
+    };
+    const bool pz = ctx->prezeroed;
+    ctx->prezeroed = false;
+    int rc = product(ws + l.Y, l.ldw, ws + l.Y, l.ldw, ws + l.T, DSVGP_GEMM_TRANS_B);                       // S = L_S L_S^T
+    if (!rc) {
+        hipLaunchKernelGGL(cgrad_diag_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, st, n, m, LS, ldls, ws + l.T, l.ldw, ws + l.part);
+        hipLaunchKernelGGL(collapsed_finish_kernel, dim3(1), dim3(1024), 0, s, st, n, hyp, num_data, ws + l.part, 1, (const int*)nullptr,
+                           ws + l.scal, (int*)nullptr);
+        hipLaunchKernelGGL(cgrad_alpha_kernel, dim3(n), dim3(256), 0, s, inverse + (size_t)n * n, n, m, alpha);
+        const hipError_t el = hipGetLastError();
+        if (el != hipSuccess) rc = 1000 + (int)el;
+    }
+    // Q = L^-T (S - I) L^-1 and L^-T G L^-1: two triangular fp64 products each, against the stored inverse
+    if (!rc) rc = product(inverse, n, ws + l.T, l.ldw, ws + l.X, DSVGP_GEMM_TRANS_A | DSVGP_GEMM_A_UPPER);
+    if (!rc) rc = product(ws + l.X, l.ldw, inverse, n, ws + l.Y, DSVGP_GEMM_B_LOWER);
+    if (!rc) rc = product(inverse, n, ws + l.Gs, l.ldw, ws + l.X, DSVGP_GEMM_TRANS_A | DSVGP_GEMM_A_UPPER);
+    if (!rc) rc = product(ws + l.X, l.ldw, inverse, n, ws + l.T, DSVGP_GEMM_B_LOWER);
+    ctx->prezeroed = pz;
+    if (rc) return rc;
+    hipLaunchKernelGGL(cgrad_final_kernel, dim3(n), dim3(256), 0, s, n, hyp, num_data, ws + l.Y, ws + l.T, l.ldw, alpha, ws + l.scal, Q, ldq,
+                       Kzz_bar, ldkb, adj, info);
+    DSVGP_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int dsvgp_collapsed_grad_chunk(dsvgp_ctx* ctx, int Mp, int Bp, const float* Kzx, int64_t ldk, const float* y,
+                                          const float* constant, const double* Q, int64_t ldq, const double* alpha, const double* adj,
+                                          float* K_bar, int64_t ldkb, float* diag_bar, double* rho_sum, void* workspace) {
+    if (!ctx || !Kzx || !y || !constant || !Q || !alpha || !adj || !K_bar || !rho_sum || !workspace || Mp <= 0 || Mp > CS_MAX_MP ||
+        Bp <= 0 || ldk < Bp || ldkb < Bp || ldq < Mp)
+        return DSVGP_EINVAL;
+    {   // K_bar is written while Kzx is still being read: the two extents must not overlap anywhere
+        const uintptr_t k0 = (uintptr_t)Kzx, k1 = k0 + sizeof(float) * ((size_t)(Mp - 1) * ldk + Bp);
+        const uintptr_t b0 = (uintptr_t)K_bar, b1 = b0 + sizeof(float) * ((size_t)(Mp - 1) * ldkb + Bp);
+        if (k0 < b1 && b0 < k1) return DSVGP_EINVAL;
+    }
+    if (((uintptr_t)Q % 8) || ((uintptr_t)alpha % 8) || ((uintptr_t)adj % 8) || ((uintptr_t)rho_sum % 8) || ((uintptr_t)workspace % 8) ||
+        ((uintptr_t)Kzx % 4) || ((uintptr_t)K_bar % 4))
+        return DSVGP_EALIGN;
+    hipStream_t s = ctx->stream;
+    const int nslab = cdiv(Mp, CG_SLAB), gx = cdiv(Bp, 256);
+    double* part = (double*)workspace;
+    double* rho = part + (size_t)nslab * Bp;
+    hipLaunchKernelGGL(cgrad_reduce_kernel, dim3(gx, nslab), dim3(256), 0, s, Kzx, ldk, Mp, Bp, alpha, part);
+    hipLaunchKernelGGL(cgrad_combine_kernel, dim3(gx), dim3(256), 0, s, part, nslab, Bp, y, constant, adj, rho, diag_bar);
+    DSVGP_LAUNCH_CHECK();
+    // V = Q K_ZX, fp64 accumulation over the float right operand, rounded once to fp32 (the form of dsvgp_var_predict): never split
+    // along K -- only the fp32 copy is asked for -- so the product has one fixed order.  Q is exactly symmetric: read as its transpose
+    GemmArgs g{};
+    g.M = Mp; g.N = Bp; g.K = Mp; g.A = Q; g.B = Kzx; g.C = nullptr; g.C32 = K_bar;
+    g.lda = ldq; g.ldb = ldk; g.ldc = 0; g.ldc32 = ldkb;
+    g.alpha = 1.0; g.beta = 0.0; g.flags = DSVGP_GEMM_TRANS_A | DSVGP_GEMM_B_IS_FLOAT; g.batch = 1; g.splitk = 1;
+    g.slab = K_bar; g.slab_bytes = 0;
+    if (int rc = launch_gemm(s, 1, g)) return rc;
+    hipLaunchKernelGGL(cgrad_epilogue_kernel, dim3(gx, cdiv(Mp, CG_EROWS)), dim3(256), 0, s, K_bar, ldkb, Mp, Bp, alpha, rho, adj, rho_sum);
+    DSVGP_LAUNCH_CHECK();
+    return 0;
+}

@@ -761,6 +761,17 @@ def fit_variational(model, likelihood, dataset_or_tensors, minibatch_size=4096, 
     ``workspace_budget``: bytes of chunk workspace of the accumulator (a chunk of ``minibatch_size`` points is cut further to fit it).
     Writes (m*, L_S*) -- or (natural_vec, natural_mat) of a NaturalVariationalDistribution -- into the model and returns the result
     object (``variational_mean``, ``chol_variational_covar``, ``natural_vec``, ``natural_mat``, ``loss``, ``terms``)."""
+    acc, X, Y, pd = _collapsed_setup(model, likelihood, dataset_or_tensors, data_directions, workspace_budget, "fit_variational")
+    n_samples, dim = X.shape
+    for x_batch, y_batch, D in _collapsed_chunks(X, Y, pd, minibatch_size, _collapsed_columns(n_samples, dim, pd, minibatch_size, seed)):
+        acc.add(x_batch, y_batch, D)
+    result = acc.solve((dim + 1) * n_samples if num_data is None else num_data)
+    _write_variational(model, result)
+    return result
+
+
+def _collapsed_setup(model, likelihood, dataset_or_tensors, data_directions, workspace_budget, what):
+    """(accumulator of the model's current state, resident X, Y [n, 1 or dim + 1], derivative columns per chunk) of one collapsed pass"""
     vs = model.variational_strategy
     device = vs.inducing_points.device
     if isinstance(dataset_or_tensors, (tuple, list)) and len(dataset_or_tensors) == 2 and torch.is_tensor(dataset_or_tensors[0]):
@@ -769,7 +780,7 @@ def fit_variational(model, likelihood, dataset_or_tensors, minibatch_size=4096, 
         X, Y = _dataset_tensors(dataset_or_tensors, device, vs.inducing_points.dtype)
     if Y.dim() == 1:
         Y = Y.reshape(-1, 1)
-    n_samples, dim = X.shape
+    dim = X.shape[1]
     if hasattr(vs, "_maybe_init"):
         vs._maybe_init()                                  # (a later first training call must not re-initialise what is written here)
     acc = model.engine.collapsed_accumulator(model._param_dict(likelihood), workspace_budget=workspace_budget)
@@ -782,19 +793,34 @@ def fit_variational(model, likelihood, dataset_or_tensors, minibatch_size=4096, 
     else:
         pd = int(data_directions)
     if Y.shape[1] not in (1, dim + 1) or not 0 <= pd <= min(dim, 95) or (pd > 0 and Y.shape[1] == 1):
-        raise ValueError("fit_variational takes targets with 1 or dim + 1 = %d columns and 0 <= data_directions <= min(dim, 95) = %d, "
-                         "got %d columns and %d directions" % (dim + 1, min(dim, 95), Y.shape[1], pd))
+        raise ValueError("%s takes targets with 1 or dim + 1 = %d columns and 0 <= data_directions <= min(dim, 95) = %d, "
+                         "got %d columns and %d directions" % (what, dim + 1, min(dim, 95), Y.shape[1], pd))
+    return acc, X, Y, pd
+
+
+def _collapsed_columns(n_samples, dim, pd, minibatch_size, seed):
+    """the columns of y of every chunk of a pass, drawn as ``select_cols_of_y`` draws them (from ``random.Random(seed)``, or the global
+    ``random`` without a seed): a list, so that a second pass over the same chunks takes the same columns"""
     rng = random.Random(seed) if seed is not None else random
-    E_canonical = torch.eye(dim, device=device, dtype=X.dtype)
-    minibatch_size = max(1, int(minibatch_size))
-    for start in range(0, n_samples, minibatch_size):
-        x_batch = X[start:start + minibatch_size]
-        idx_y = list(range(dim + 1)) if pd == dim else sorted(rng.sample(range(1, dim + 1), pd) + [0])
-        y_batch = Y[start:start + minibatch_size][:, idx_y].reshape(-1)
+    step = max(1, int(minibatch_size))
+    return [list(range(dim + 1)) if pd == dim else sorted(rng.sample(range(1, dim + 1), pd) + [0]) for _ in range(0, n_samples, step)]
+
+
+def _collapsed_chunks(X, Y, pd, minibatch_size, columns):
+    """(x, interleaved y, canonical directions or None) of every chunk of ``minibatch_size`` points with its drawn columns"""
+    dim = X.shape[1]
+    E_canonical = torch.eye(dim, device=X.device, dtype=X.dtype)
+    step = max(1, int(minibatch_size))
+    for start, idx_y in zip(range(0, X.shape[0], step), columns):
+        x_batch = X[start:start + step]
+        y_batch = Y[start:start + step][:, idx_y].reshape(-1)
         D = E_canonical[[c - 1 for c in idx_y[1:]]].repeat(x_batch.shape[0], 1) if pd else None
-        acc.add(x_batch, y_batch, D)
-    result = acc.solve((dim + 1) * n_samples if num_data is None else num_data)
-    vd = vs._variational_distribution
+        yield x_batch, y_batch, D
+
+
+def _write_variational(model, result):
+    """q(u) of the model <- the optimum: (m*, L_S*), or the natural pair of a NaturalVariationalDistribution"""
+    vd = model.variational_strategy._variational_distribution
     with torch.no_grad():
         if isinstance(vd, NaturalVariationalDistribution):
             vd.natural_vec.copy_(result.natural_vec)
@@ -802,7 +828,68 @@ def fit_variational(model, likelihood, dataset_or_tensors, minibatch_size=4096, 
         else:
             vd.variational_mean.copy_(result.variational_mean)
             vd.chol_variational_covar.copy_(result.chol_variational_covar)
+
+
+def collapsed_loss_and_grads(model, likelihood, dataset_or_tensors, minibatch_size=4096, data_directions=None, num_data=None, seed=None,
+                             workspace_budget=1 << 30, write_variational=True):
+    """The collapsed bound (Titsias' SGPR objective: the ELBO with q(u) at its closed-form optimum) and its gradients with respect to
+    the lengthscale(s), outputscale, noise, constant, inducing points and inducing directions, from TWO passes over the data in chunks
+    of ``minibatch_size`` points: the statistics pass of ``fit_variational``, then ``CollapsedAccumulator.add_backward`` over the same
+    chunks with the same drawn derivative columns.  Arguments as ``fit_variational``.  Fills ``.grad`` of the model's and the
+    likelihood's hyper-parameters, the inducing points and the directions (those that require a gradient; added onto an existing
+    ``.grad``); the variational tensors get none -- with ``write_variational`` they are set to the optimum itself.  Returns the result
+    object of the solve (``loss``: the collapsed loss these gradients belong to)."""
+    acc, X, Y, pd = _collapsed_setup(model, likelihood, dataset_or_tensors, data_directions, workspace_budget, "collapsed_loss_and_grads")
+    n_samples, dim = X.shape
+    columns = _collapsed_columns(n_samples, dim, pd, minibatch_size, seed)
+    for x_batch, y_batch, D in _collapsed_chunks(X, Y, pd, minibatch_size, columns):
+        acc.add(x_batch, y_batch, D)
+    result = acc.solve((dim + 1) * n_samples if num_data is None else num_data)
+    acc.begin_backward(result)
+    for x_batch, y_batch, D in _collapsed_chunks(X, Y, pd, minibatch_size, columns):
+        acc.add_backward(x_batch, y_batch, D)
+    _, grads = acc.finish_backward()
+    if write_variational:
+        _write_variational(model, result)
+    for prm, name in zip(model._param_list(likelihood), model._param_names()):
+        if name in grads and isinstance(prm, torch.nn.Parameter) and prm.requires_grad:
+            g = grads[name].view_as(prm)
+            prm.grad = g if prm.grad is None else prm.grad.add_(g)
     return result
+
+
+def train_collapsed(train_dataset, num_inducing=128, num_directions=1, num_iterations=50, learning_rate_hypers=0.01, minibatch_size=4096,
+                    data_directions=None, inducing_data_initialization=True, fixed_inducing_locations=None, kernel="rbf",
+                    ard_num_dims=None, seed=None, num_data=None, workspace_budget=1 << 30, verbose=True, tensors=None):
+    """Train a derivative GP on its hyper-parameters, inducing points and inducing directions alone, with q(u) exact at every iterate
+    (Titsias' SGPR for the directional-derivative model; RBF, ARD and Matern-5/2).  The model is built the way ``setup_training``
+    builds it (``kernel``, ``ard_num_dims``, ``inducing_data_initialization``, ``fixed_inducing_locations``, ``seed`` and ``verbose``
+    as ``train_gp`` understands them); each of the ``num_iterations`` iterations is one ``collapsed_loss_and_grads`` over the whole data
+    set -- chunks of ``minibatch_size`` points, derivative columns drawn once per iteration -- and one Adam step at
+    ``learning_rate_hypers``; a final ``fit_variational`` leaves q(u) at the optimum of the final hyper-parameters.
+    Returns (model, likelihood)."""
+    loop = setup_training(train_dataset, num_inducing, num_directions, minibatch_size, num_directions, 1, learning_rate_hypers,
+                          inducing_data_initialization, None, "ELBO", 0.1, fixed_inducing_locations, seed=seed, tensors=tensors,
+                          data_directions=data_directions, kernel=kernel, ard_num_dims=ard_num_dims)
+    model, likelihood = loop.model, loop.likelihood
+    optimizer = loop.hyperparameter_optimizer
+    rng = random.Random(seed) if seed is not None else random
+    pass_seed = lambda: rng.randrange(2 ** 31)
+    result = None
+    for it in range(int(num_iterations)):
+        for prm in list(model.parameters()) + list(likelihood.parameters()):
+            prm.grad = None
+        result = collapsed_loss_and_grads(model, likelihood, (loop.X, loop.Y), minibatch_size=minibatch_size, data_directions=data_directions,
+                                          num_data=num_data, seed=pass_seed(), workspace_budget=workspace_budget, write_variational=False)
+        optimizer.step()
+        if verbose and it % 10 == 0:
+            print(f"Iteration: {it}; collapsed loss: {result.loss}")
+            sys.stdout.flush()
+    fit_variational(model, likelihood, (loop.X, loop.Y), minibatch_size=minibatch_size, data_directions=data_directions, num_data=num_data,
+                    seed=pass_seed(), workspace_budget=workspace_budget)
+    if verbose and result is not None:
+        print(f"Done! collapsed loss: {result.loss}")
+    return model, likelihood
 
 
 def eval_gp(test_dataset, model, likelihood,

@@ -389,6 +389,16 @@ class ApproximateGP(torch.nn.Module):
         return fit_variational(self, likelihood, dataset_or_tensors, minibatch_size=minibatch_size, data_directions=data_directions,
                                num_data=num_data, seed=seed)
 
+    def collapsed_loss_and_grads(self, likelihood, dataset_or_tensors, minibatch_size=4096, data_directions=None, num_data=None, seed=None,
+                                 workspace_budget=1 << 30, write_variational=True):
+        """The collapsed bound (the ELBO with q(u) at its closed-form optimum) from two passes over the data, its gradients written to
+        ``.grad`` of the hyper-parameters, inducing points and directions: the method form of
+        ``directional_vi.collapsed_loss_and_grads`` (``CollapsedAccumulator.add_backward``).  Returns the result object."""
+        from .directional_vi import collapsed_loss_and_grads
+        return collapsed_loss_and_grads(self, likelihood, dataset_or_tensors, minibatch_size=minibatch_size, data_directions=data_directions,
+                                        num_data=num_data, seed=seed, workspace_budget=workspace_budget,
+                                        write_variational=write_variational)
+
     # ---- posterior mean without the predictive distribution (what the reference's mean-only callers read from
     #      ``likelihood(model(x, derivative_directions=D)).mean``: experiments/bunny/exp_bunny.py:189-195,
     #      experiments/rover/bo_traditional.py:214, experiments/GNN_bo/bo.py:172) ----

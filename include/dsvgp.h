@@ -1047,6 +1047,36 @@ int dsvgp_collapsed_solve(dsvgp_ctx* ctx, const void* state, int Mp, const float
 int dsvgp_collapsed_evaluate(dsvgp_ctx* ctx, const void* state, int Mp, const float* m, const float* LS, int64_t ldls, const float* hyp,
                              double num_data, double* scalars, void* workspace);
 
+/* ---- gradients of the collapsed bound at the optimum (csrc/collapsed.hip): SGPR training, the second pass.
+ * Valid ONLY for (m, LS) = the result of dsvgp_collapsed_solve on the same statistics, hyp and num_data: by the envelope theorem the total
+ * derivative then equals the partial one at fixed whitened q(u), and the upstream of K~ = s K_ZZ + jitter I needs no Cholesky backward.
+ * With alpha = L^-T m, Q = L^-T (S - I) L^-1, w = 1 / (2 R noise), rho = (y - c) - K_ZX^T alpha:
+ *   K_ZX-bar = 2 w (Q K_ZX - alpha rho^T)        K~-bar = (Q + alpha alpha^T + kappa L^-T G L^-1) / (2 num_data)        dg-bar = w
+ *   c-bar = -2 w sum rho                          d loss / d noise = -(E + V) / (2 R noise^2) + 1 / noise
+ *   dsvgp_collapsed_grad_prepare   once per backward pass.  inverse: L^-1 | L^-T of the factor of K~, 2 Mp^2 doubles with leading dimension Mp
+ *                                  (the head of dsvgp_trsm's workspace after dsvgp_potrf_inverse).  Writes alpha[Mp], Q[Mp, ldq] and
+ *                                  Kzz_bar[Mp, ldkb] (float64, both exactly symmetric; four triangular fp64 MFMA products and S = L_S L_S^T),
+ *                                  adj[8] (float64): w, d loss / d noise, dg-bar, loss, E = sum |residual|^2, V = sum varn, kappa, R; and
+ *                                  *info (device int): 0, or 1 when a statistic, (m, LS) or a result is not finite or R = 0 (nothing faults;
+ *                                  the outputs are then not to be used).  workspace: dsvgp_collapsed_grad_workspace_bytes(Mp), 16-byte aligned.
+ *   dsvgp_collapsed_grad_chunk     per chunk: K_bar[Mp, ldkb] (float32, must not overlap Kzx) = K_ZX-bar of the chunk's float32 Kzx[Mp, ldk],
+ *                                  ready for dsvgp_kernel_bwd_rect / _ard / _matern52 with the inducing side as side 1; diag_bar[Bp] (may be
+ *                                  NULL) = dg-bar for the prior diagonal's backward; rho_sum[0] += sum rho (one writer, fixed order).
+ *                                  Launches: the residual's column reduction in row slabs of 256 and its fixed-order combine, Q Kzx on the
+ *                                  fp64 MFMA GEMM over the float operand (one K slice, rounded once), the in-place epilogue.  No
+ *                                  floating-point atomics, no host read, no allocation: two identical calls give bitwise equal results.
+ *                                  workspace: dsvgp_collapsed_grad_chunk_bytes(Mp, Bp), 8-byte aligned.
+ * The size helpers return 0 for refused arguments (Mp <= 0, Mp > 8192, Bp <= 0).  DSVGP_EINVAL: a null required pointer, Mp <= 0, Mp > 8192,
+ * Bp <= 0, a leading dimension below its row length, num_data <= 0, the extents of K_bar and Kzx overlapping anywhere; DSVGP_EALIGN: a misaligned pointer.    */
+size_t dsvgp_collapsed_grad_workspace_bytes(int Mp);
+size_t dsvgp_collapsed_grad_chunk_bytes(int Mp, int Bp);
+int dsvgp_collapsed_grad_prepare(dsvgp_ctx* ctx, const void* state, int Mp, const float* m, const float* LS, int64_t ldls,
+                                 const double* inverse, const float* hyp, double num_data, double* alpha, double* Q, int64_t ldq,
+                                 double* Kzz_bar, int64_t ldkb, double* adj, int* info, void* workspace);
+int dsvgp_collapsed_grad_chunk(dsvgp_ctx* ctx, int Mp, int Bp, const float* Kzx, int64_t ldk, const float* y, const float* constant,
+                               const double* Q, int64_t ldq, const double* alpha, const double* adj, float* K_bar, int64_t ldkb,
+                               float* diag_bar, double* rho_sum, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
