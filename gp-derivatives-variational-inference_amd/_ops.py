@@ -1474,6 +1474,27 @@ def likelihood_terms(ctx, mu, var, y, p, hyp, mll_type, global_rows, mu_bar, var
                                      _ptr(scalars)), "dsvgp_likelihood_terms")
 
 
+def likelihood_terms_masked_workspace(device):
+    """scratch of ``likelihood_terms_masked`` (per-workgroup counts and partial sums; a fixed size)"""
+    return torch.empty(int(lib.dsvgp_likelihood_terms_masked_workspace_bytes()), dtype=torch.uint8, device=device)
+
+
+def likelihood_terms_masked(ctx, mu, var, y, p, hyp, mll_type, mu_bar, var_bar, varn, scalars, n_present, workspace):
+    """``likelihood_terms`` over the rows whose target is not NaN (csrc/missing.hip): exact zeros on the missing rows, scalars normalised
+    by the device-side count (``step_epilogue`` then takes rows = 1), the count itself in ``n_present`` (int32 [1]).  No host read."""
+    for t, name in ((mu, "mu"), (var, "var"), (mu_bar, "mu_bar"), (var_bar, "var_bar"), (varn, "varn")):
+        _req(t, f32, name, 1)
+        if t.numel() != y.numel():
+            raise ValueError("%s must have B' = %d entries, got %d" % (name, y.numel(), t.numel()))
+    if scalars.dtype != f32 or scalars.numel() < 8 or n_present.dtype != torch.int32 or n_present.numel() < 1:
+        raise ValueError("scalars must be 8 float32 values and n_present one int32")
+    if workspace is None or workspace.numel() * workspace.element_size() < int(lib.dsvgp_likelihood_terms_masked_workspace_bytes()):
+        raise ValueError("likelihood_terms_masked needs the workspace of likelihood_terms_masked_workspace()")
+    check(lib.dsvgp_likelihood_terms_masked(ctx.h, _ptr(mu), _ptr(var), _ptr(_req(y, f32, "y", 1)), y.numel(), int(p), _ptr(hyp),
+                                            int(mll_type), _ptr(mu_bar), _ptr(var_bar), _ptr(varn), _ptr(scalars), _ptr(n_present),
+                                            _ptr(workspace)), "dsvgp_likelihood_terms_masked")
+
+
 def abar(ctx, A, U, m, mu_bar, var_bar, out):
     Mp, nc = A.shape
     check(lib.dsvgp_abar(ctx.h, _ptr(A), _ld(A), _ptr(U), _ld(U), Mp, nc, _ptr(m), _ptr(mu_bar), _ptr(var_bar),
@@ -1996,6 +2017,22 @@ def collapsed_accumulate_(ctx, state, Mp, A64, Bp, y, constant, prior_diag):
                                          _ptr(prior_diag)), "dsvgp_collapsed_accumulate")
 
 
+def collapsed_accumulate_masked_(ctx, state, Mp, A64, Bp, pd, y, constant, prior_diag):
+    """``collapsed_accumulate_`` over the rows whose target is not NaN (csrc/missing.hip): the missing columns of A64 are zeroed, r = 0
+    there, and the prior-diagonal sum, R (state[1]) and the count of present value rows (state[2]) take present rows only"""
+    _req_collapsed_state(state, Mp)
+    _req(A64, f64, "A64", 2)
+    if A64.shape[0] != Mp + 1 or A64.shape[1] < Bp:
+        raise ValueError("A64 must be [M' + 1, >= B'] = [%d, >= %d], got %s" % (Mp + 1, Bp, tuple(A64.shape)))
+    for t, name in ((y, "y"), (prior_diag, "prior_diag")):
+        _req(t, f32, name, 1)
+        if t.numel() != Bp:
+            raise ValueError("%s must have B' = %d entries, got %d" % (name, Bp, t.numel()))
+    _req(constant, f32, "constant", 1)
+    check(lib.dsvgp_collapsed_accumulate_masked(ctx.h, _ptr(state), int(Mp), _ptr(A64), _ld(A64), int(Bp), int(pd), _ptr(y),
+                                                _ptr(constant), _ptr(prior_diag)), "dsvgp_collapsed_accumulate_masked")
+
+
 def collapsed_solve(ctx, state, Mp, hyp, num_data, workspace, want_natural=True):
     """(m*, L_S*, natural_vec, natural_mat, scalars[8] float64, info int32[1]) -- all on the device, nothing read"""
     _req_collapsed_state(state, Mp)
@@ -2090,3 +2127,34 @@ def collapsed_grad_chunk(ctx, Mp, Kzx, y, constant, Q, alpha, adj, K_bar, diag_b
     check(lib.dsvgp_collapsed_grad_chunk(ctx.h, int(Mp), int(Bp), _ptr(Kzx), _ld(Kzx), _ptr(y), _ptr(constant), _ptr(Q), _ld(Q), _ptr(alpha),
                                          _ptr(adj), _ptr(K_bar), _ld(K_bar), _ptr(diag_bar), _ptr(rho_sum), _ptr(workspace)),
           "dsvgp_collapsed_grad_chunk")
+
+
+def collapsed_grad_chunk_masked_bytes(Mp, Bp):
+    """bytes of ``collapsed_grad_chunk_masked``'s workspace (pure host arithmetic); 0 for refused arguments"""
+    return int(lib.dsvgp_collapsed_grad_chunk_masked_bytes(int(Mp), int(Bp)))
+
+
+def collapsed_grad_chunk_masked(ctx, Mp, Kzx, y, constant, Q, alpha, adj, K_bar, diag_bar, rho_sum, workspace):
+    """``collapsed_grad_chunk`` with K_bar's columns, diag_bar and the share of rho_sum exactly 0 on the rows whose target is NaN
+    (csrc/missing.hip).  The missing columns of ``Kzx`` are zeroed in place."""
+    _req(Kzx, f32, "Kzx", 2)
+    _req(K_bar, f32, "K_bar", 2)
+    Bp = Kzx.shape[1]
+    if Kzx.shape[0] != Mp or K_bar.shape != Kzx.shape:
+        raise ValueError("Kzx and K_bar must both be [M', B'] = [%d, B'], got %s and %s" % (Mp, tuple(Kzx.shape), tuple(K_bar.shape)))
+    _req(y, f32, "y", 1)
+    if y.numel() != Bp or (diag_bar is not None and (diag_bar.numel() != Bp or diag_bar.dtype != f32)):
+        raise ValueError("y and diag_bar must have B' = %d float32 entries" % Bp)
+    _req(constant, f32, "constant", 1)
+    _req(Q, f64, "Q", 2)
+    if Q.shape != (Mp, Mp):
+        raise ValueError("Q must be [M', M'] = [%d, %d], got %s" % (Mp, Mp, tuple(Q.shape)))
+    for t, name, numel in ((alpha, "alpha", Mp), (adj, "adj", 8), (rho_sum, "rho_sum", 1)):
+        if t.dtype != f64 or t.numel() != numel or not t.is_contiguous():
+            raise ValueError("%s must be %d contiguous float64 values" % (name, numel))
+    nbytes = collapsed_grad_chunk_masked_bytes(Mp, Bp)
+    if nbytes == 0 or workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+        raise ValueError("collapsed_grad_chunk_masked needs a workspace of collapsed_grad_chunk_masked_bytes(M', B') = %d bytes" % nbytes)
+    check(lib.dsvgp_collapsed_grad_chunk_masked(ctx.h, int(Mp), int(Bp), _ptr(Kzx), _ld(Kzx), _ptr(y), _ptr(constant), _ptr(Q), _ld(Q),
+                                                _ptr(alpha), _ptr(adj), _ptr(K_bar), _ld(K_bar), _ptr(diag_bar), _ptr(rho_sum),
+                                                _ptr(workspace)), "dsvgp_collapsed_grad_chunk_masked")

@@ -607,6 +607,11 @@ class CollapsedAccumulator:
         self._solve_ws = None
         self._solved = self._bwd = None              # (num_data, rows) of the last solve; the state of a running backward pass
         self._raw = self._shapes = None              # raw hyper-parameters and gradient shapes (set by ``collapsed_accumulator``)
+        # the engine's ``missing_targets`` when the accumulator was made: NaN targets are rows that do not exist (csrc/missing.hip).  R
+        # (state[1]) and the count of present value rows (state[2]) then live on the device; ``rows`` stays the host count of the rows
+        # that were HANDED to ``add``, present or not -- what the second pass must cover
+        self._missing = bool(getattr(engine, "missing_targets", False))
+        self._present = None                         # R as the last solve's host read carried it
 
     # ---- chunking -------------------------------------------------------------------------------
     def row_bytes(self, pd, backward=False):
@@ -703,7 +708,10 @@ class CollapsedAccumulator:
             Kzx = fwd(ctx, self._packZ, self.M, self.p, packX, nb_, pd, self.d, self._hyp, out=self._get("Kzx", Mp * Bp, f32).view(Mp, Bp))
             A64 = self._get("A64", (Mp + 1) * Bp, f64).view(Mp + 1, Bp)
             _ops.trsm(ctx, self._L, Kzx, False, A64[:Mp], None, self._nb, ws, reuse_inverse=True)
-            _ops.collapsed_accumulate_(ctx, self._state, Mp, A64, Bp, y[r0 * q:(r0 + nb_) * q], self._constant, diag)
+            if self._missing:
+                _ops.collapsed_accumulate_masked_(ctx, self._state, Mp, A64, Bp, pd, y[r0 * q:(r0 + nb_) * q], self._constant, diag)
+            else:
+                _ops.collapsed_accumulate_(ctx, self._state, Mp, A64, Bp, y[r0 * q:(r0 + nb_) * q], self._constant, diag)
         self._rows += B * q
         return self
 
@@ -717,6 +725,10 @@ class CollapsedAccumulator:
     def _num_data(self, num_data):
         if self._rows == 0:
             raise ValueError("the collapsed statistics are empty (R = 0): add data before solve / evaluate")
+        if num_data is None and self._missing:
+            num_data = float(self._state[1].item())      # R, the present rows, is counted on the device: the default costs this read
+            if not num_data > 0.0:
+                raise ValueError("the collapsed statistics hold no present row (R = 0: every target added so far is NaN)")
         num_data = float(self._rows if num_data is None else num_data)
         if not num_data > 0.0:
             raise ValueError("num_data must be positive, got %r" % (num_data,))
@@ -745,6 +757,7 @@ class CollapsedAccumulator:
         if code != 0:
             raise ValueError("collapsed solve: a statistic is not finite (a NaN or Inf in y, x or the directions that were added)")
         self._solved = (num_data, self._rows)
+        self._present = int(host[5])
         return CollapsedResult(m, LS, nv, nm, self._terms(host[:8]), num_data)
 
     @torch.no_grad()
@@ -770,7 +783,7 @@ class CollapsedAccumulator:
         if solved is None or solved[1] != self._rows:
             raise ValueError("begin_backward needs the result of a solve() of the current statistics (R = %d): call solve() after the "
                              "last add()" % self._rows)
-        if float(result.num_data) != solved[0] or int(result.terms["rows"]) != self._rows:
+        if float(result.num_data) != solved[0] or int(result.terms["rows"]) != (self._present if self._missing else self._rows):
             raise ValueError("begin_backward: the result was solved for num_data = %r on %d rows, the accumulator's last solve for "
                              "num_data = %r on %d rows -- the gradients hold only at the optimum of the same statistics"
                              % (result.num_data, int(result.terms["rows"]), solved[0], self._rows))
@@ -824,7 +837,9 @@ class CollapsedAccumulator:
         y = y.contiguous()
         nmax = min(rows, B)
         kws = self._get("kbwd_ws", self._kernel_bwd_bytes(nmax, pd, False), torch.uint8)
-        cws = self._get("cgrad_ws", _ops.collapsed_grad_chunk_bytes(Mp, nmax * q) // 8, f64)
+        chunk_bytes = _ops.collapsed_grad_chunk_masked_bytes if self._missing else _ops.collapsed_grad_chunk_bytes
+        chunk = _ops.collapsed_grad_chunk_masked if self._missing else _ops.collapsed_grad_chunk     # (masked: exact zeros on NaN rows)
+        cws = self._get("cgrad_ws", (chunk_bytes(Mp, nmax * q) + 7) // 8, f64)
         for r0 in range(0, B, rows):
             nb_ = min(rows, B - r0)
             Bp = nb_ * q
@@ -840,8 +855,7 @@ class CollapsedAccumulator:
             ld = (Bp + 3) // 4 * 4                   # rows 16-byte addressable: the product's float operand takes the vector-load kernels
             Kzx = fwd(ctx, self._packZ, M, p, packX, nb_, pd, d, self._hyp, out=self._get("Kzx", Mp * ld, f32).view(Mp, ld)[:, :Bp])
             Kbar = self._get("Kbar", Mp * ld, f32).view(Mp, ld)[:, :Bp]
-            _ops.collapsed_grad_chunk(ctx, Mp, Kzx, y[r0 * q:(r0 + nb_) * q], self._constant, st["Q"], st["alpha"], st["adj"], Kbar, dbar,
-                                      st["rho_sum"], cws)
+            chunk(ctx, Mp, Kzx, y[r0 * q:(r0 + nb_) * q], self._constant, st["Q"], st["alpha"], st["adj"], Kbar, dbar, st["rho_sum"], cws)
             if self._ell is not None:
                 bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
                 bwd(ctx, Kbar, self._packZ, M, p, packX, nb_, pd, d, self._ell, self._hyp, False, dZ, dV if p > 0 else None, d_ell, d_hyp, kws)
@@ -876,9 +890,11 @@ class CollapsedAccumulator:
         else:
             _ops.kernel_bwd(ctx, st["Kzz_bar"], self._packZ, M, self._packZ, M, d, p, self._hyp, True, dZ, dV, d_hyp, kws)
             # the scalar RBF prior diagonal s [1, 1 / ell^2, ...]: dg-bar = w on every entry, in closed form
-            ell, s, n_der = self._hyp[0].to(f64), self._hyp[1].to(f64), float(st["rows"] - st["points"])
+            ell, s, n_der, n_val = self._hyp[0].to(f64), self._hyp[1].to(f64), float(st["rows"] - st["points"]), float(st["points"])
+            if self._missing:                            # present value / derivative rows: device counts of the first pass
+                n_val, n_der = self._state[2], self._state[1] - self._state[2]
             d_hyp[0] += (adj[2] * s * n_der * (-2.0) / (ell * ell * ell)).to(f32)
-            d_hyp[1] += (adj[2] * (float(st["points"]) + n_der / (ell * ell))).to(f32)
+            d_hyp[1] += (adj[2] * (n_val + n_der / (ell * ell))).to(f32)
         d_hyp[2] += adj[1].to(f32)
         rl, rs, rn = self._raw
         g_l, g_s, g_n = torch.zeros_like(rl), torch.zeros_like(rs), torch.zeros_like(rn)
@@ -1025,6 +1041,12 @@ class ElboEngine:
         # the rectangular TRAINING step (loss_and_grads with pd != p directions per data point, csrc/assemble_rect.hip): pd while such a
         # step is being queued, None otherwise -- the data side's direction count wherever the piecewise path reads ``_pd``
         self._train_pd = None
+        # OPT-IN (csrc/missing.hip): True = a NaN entry of y is an observation that does not exist.  The step takes
+        # the piecewise per-output path with dsvgp_likelihood_terms_masked in the place of dsvgp_likelihood_terms: the loss is normalised
+        # by the present rows of the batch, counted on the device (``present_rows``, int32 [1], of the last such step; never read here),
+        # and everything downstream sees exact zeros on the missing rows.  ``collapsed_accumulator`` reads the switch when it is called.
+        self.missing_targets = False
+        self.present_rows = None
         # ARD lengthscales (raw_lengthscale [1, d], csrc/assemble_ard.hip): set by the entries built for them (predict, predict_joint,
         # loss_and_grads) while such a call is being queued.  The packs then carry the per-dimension scaling, hyp[0] = 1, K_ZZ comes
         # from the wide forward, K_ZX from the rectangular one, both backwards from dsvgp_kernel_bwd_ard; ``_ard_ell`` is the
@@ -1190,6 +1212,32 @@ class ElboEngine:
                 raise no("the deterministic mode")
             if fast:
                 raise no("the Gram fast path (fast=True)")
+
+    def _missing_refusals(self, params, x, fast=None, training=True):
+        """what ``missing_targets`` is not built for, refused on the parameters and switches alone, before any device work"""
+        no = lambda what: ValueError("missing_targets is not built for %s (NaN targets are skipped on the piecewise per-output path and "
+                                     "in the collapsed statistics of a float32, Cholesky-whitened, per-point model on one rank)" % what)
+        if type(self) is not ElboEngine or params["inducing_points"].dtype != f32 or (x is not None and x.dtype != f32):
+            raise no("float64 engines and inputs")
+        if self.whitening == "ciq":
+            raise no("CIQ whitening")
+        if "natural_vec" in params:
+            raise no("natural parameters")
+        if self.shared_directions:
+            raise no("shared directions (shared_directions)")
+        if self.data_outputs == "values":
+            raise no("the derivative-free strategy (data_outputs == 'values')")
+        coll = self.collective
+        if coll is not None and coll.world > 1:
+            raise no("a collective with world = %d" % coll.world)
+        if training:
+            if self.capture_mode:
+                raise no("graph capture (capture_mode)")
+            if self.deterministic:
+                raise no("the deterministic mode (deterministic)")
+            if fast:
+                raise no("the Gram fast path (fast=True): it needs per-type present counts, zeroed K_ZX columns and a masked "
+                         "residual pass -- a follow-up")
 
     def _is_matern(self):
         """whether the engine's kernel is Matern-5/2; any value but "rbf" / "matern52" is refused"""
@@ -1684,7 +1732,10 @@ class ElboEngine:
         """``CollapsedAccumulator`` of the current hyper-parameters, inducing points and directions: K_ZZ is factored once through
         ``_factor`` (jitter ladder included) with the kernel in use -- RBF, ARD (raw_lengthscale [1, d]) or Matern-5/2 -- and the factor,
         its inverse and the packs are copied out of the engine's buffers.  q(u) itself is not read: the accumulator computes it.  The
-        factorisation runs in the engine's factor buffers, so the evaluation cache of ``predict`` is dropped."""
+        factorisation runs in the engine's factor buffers, so the evaluation cache of ``predict`` is dropped.  With ``missing_targets`` set
+        the accumulator skips NaN targets (it keeps the switch it was made with)."""
+        if self.missing_targets:
+            self._missing_refusals(params, None, training=False)
         if self.whitening == "ciq":
             raise ValueError("the closed-form optimal q(u) is not built for CIQ whitening: its whitened basis is K^{-1/2}, not L^-1, and "
                              "the statistics G = A A^T would need the msMINRES solves of every data column")
@@ -1981,7 +2032,11 @@ class ElboEngine:
         """Returns (loss, grads dict, mu, varn).  ``global_rows`` = B'(global) for data-parallel ranks;
         ``include_kl=False`` leaves the (replicated) KL term out so exactly one rank adds it.
         ``fast`` (default ``self.elbo_fast``): in ELBO mode use the Gram-matrix formulation, which does not
-        produce per-output variances (``varn`` is then an empty tensor; ``predict`` gives them on demand)."""
+        produce per-output variances (``varn`` is then an empty tensor; ``predict`` gives them on demand).
+        ``missing_targets`` (attribute): NaN entries of ``y`` are skipped; always the per-output path (``fast=True`` is refused)."""
+        if self.missing_targets:
+            self._missing_refusals(params, x, fast=fast)
+            fast = False
         if self._is_matern():
             return self._loss_and_grads_matern(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
         if self._is_ard(params):
@@ -2533,7 +2588,7 @@ class ElboEngine:
         one rank, Cholesky whitening, every data point with its derivatives, explicit-inverse regime"""
         if not (self.c_step and not sync and not self.capture_mode and self.whitening == "cholesky" and self.data_outputs == "all"
                 and not self.shared_directions and not self._no_middle and self.potrf_algo == 1 and self.fused_inverse
-                and self._trsm_nb is None and not self.lib_dense_gemm and not self.deterministic):
+                and self._trsm_nb is None and not self.lib_dense_gemm and not self.deterministic and not self.missing_targets):
             return False
         coll = self.collective
         if coll is not None and coll.world > 1:
@@ -2780,8 +2835,16 @@ class ElboEngine:
             mu_bar = torch.empty(Bp, dtype=f32, device=dev)
             var_bar = torch.empty(Bp, dtype=f32, device=dev)
             varn = torch.empty(Bp, dtype=f32, device=dev)
-            _ops.likelihood_terms(ctx, mu, var, y, pd, hyp, 0 if mll_type == "ELBO" else 1, rows, mu_bar, var_bar,
-                                  varn, scal)
+            if self.missing_targets:
+                # NaN targets do not exist: zeros on their rows, the scalars normalised by the device-side present count -- the epilogue
+                # below then takes rows = 1.  Nothing downstream changes: it sees the zeros.
+                self.present_rows = torch.empty(1, dtype=torch.int32, device=dev)
+                _ops.likelihood_terms_masked(ctx, mu, var, y, pd, hyp, 0 if mll_type == "ELBO" else 1, mu_bar, var_bar, varn, scal,
+                                             self.present_rows, self._bytes("missing_ws", _lib.lib.dsvgp_likelihood_terms_masked_workspace_bytes()))
+                rows = 1.0
+            else:
+                _ops.likelihood_terms(ctx, mu, var, y, pd, hyp, 0 if mll_type == "ELBO" else 1, rows, mu_bar, var_bar,
+                                      varn, scal)
             # ---- variational parameters ----
             Abar = self._get("Abar", (Mp, Bp), f32)
             if self._no_middle:

@@ -433,6 +433,8 @@ class ElboEngine64(ElboEngine):
     def loss_and_grads(self, params, x, y, D, num_data, mll_type="ELBO", global_rows=None, include_kl=True, fast=None):
         """(loss, grads dict, mu, varn), all fp64; see ``ElboEngine.loss_and_grads`` for the arguments.  With natural parameters
         (``natural_vec``, ``natural_mat``) the gradients of those two slots are the expectation-parameter gradients NGD steps along."""
+        if self.missing_targets:
+            self._missing_refusals(params, x, fast=fast)             # (a float64 engine: always refused)
         self._no_matern("a float64 engine")
         self._no_ard(params, "a float64 engine")
         if self.data_outputs != "values":

@@ -250,11 +250,15 @@ extern "C" int dsvgp_collapsed_accumulate(dsvgp_ctx* ctx, void* state, int Mp, d
     hipLaunchKernelGGL(collapsed_rows_kernel, dim3(blocks), dim3(1024), 0, ctx->stream, st, A64 + (int64_t)Mp * lda, Bp, y, constant,
                        prior_diag);
     DSVGP_LAUNCH_CHECK();
-    // T += tril([A ; r^T][A ; r^T]^T) in place (beta = 1, Cin == C): one pass below the launcher's split-K threshold, its fp64 atomics
-    // onto the live state above it
+    return collapsed_gram_update(ctx, st + CS_HEAD, Mp, A64, lda, Bp);
+}
+
+// T += tril([A ; r^T][A ; r^T]^T) in place (beta = 1, Cin == C): one pass below the launcher's split-K threshold, its fp64 atomics
+// onto the live state above it (shared with dsvgp_collapsed_accumulate_masked, missing.hip)
+int collapsed_gram_update(dsvgp_ctx* ctx, double* T, int Mp, const double* A64, int64_t lda, int Bp) {
     GemmArgs g{};
     g.M = Mp + 1; g.N = Mp + 1; g.K = Bp;
-    g.A = A64; g.B = A64; g.Cin = st + CS_HEAD; g.C = st + CS_HEAD;
+    g.A = A64; g.B = A64; g.Cin = T; g.C = T;
     g.lda = lda; g.ldb = lda; g.ldcin = Mp + 1; g.ldc = Mp + 1;
     g.alpha = 1.0; g.beta = 1.0; g.flags = DSVGP_GEMM_TRANS_B | DSVGP_GEMM_OUT_LOWER | DSVGP_GEMM_KEEP_UPPER;
     g.batch = 1; g.splitk = 1;

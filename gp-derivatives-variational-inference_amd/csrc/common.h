@@ -91,6 +91,8 @@ void launch_cvt_f64_f32(hipStream_t st, const double* C, int64_t ldc, float* C32
 void launch_widen_f32_f64(hipStream_t st, const float* src, int64_t ld, double* dst, int64_t ldd, int M, int N);      // gemm64.hip
 int launch_gemm64(hipStream_t st, const GemmArgs& g);     // gemm64.hip: 1 = taken, 0 = not eligible, > 1 = error
 int launch_gemm32(hipStream_t st, const GemmArgs& g);     // gemm32.hip (fp32, 32x32x2 MFMA): same convention
+// T += tril([A ; r^T][A ; r^T]^T) on the collapsed statistics' (Mp + 1) x (Mp + 1) matrix T, A64 = [A ; r^T] (Mp + 1) x Bp -- collapsed.hip
+int collapsed_gram_update(dsvgp_ctx* ctx, double* T, int Mp, const double* A64, int64_t lda, int Bp);
 
 // ---------------------------------------------------------------------------------------------
 // Deterministic float64 model mode (det64.hip): what the fp64 kernels add through atomics by default goes, with ctx->det_slab set, to

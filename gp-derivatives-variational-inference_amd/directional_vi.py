@@ -64,6 +64,9 @@ class GPModel(ApproximateGP):
         self._engine = None
         self.data_parallel = None
         self.data_directions = None             # int: the data carry that many directions per point, not num_directions (ApproximateGP)
+        # ``missing_targets`` (through **kwargs; False by default): NaN targets are observations that do not exist -- the engine's masked
+        # per-output step and collapsed statistics (``ElboEngine.missing_targets``)
+        self.missing_targets = bool(kwargs.get("missing_targets", False))
         self.mean_module = ConstantMean()
         if ard_num_dims is not None and int(ard_num_dims) != int(dim):
             raise ValueError("ard_num_dims must equal the input dimension (%d), got %s" % (dim, ard_num_dims))
@@ -88,6 +91,7 @@ class GPModel(ApproximateGP):
         eng.data_outputs = "all"
         eng.shared_directions = False
         eng.kernel = "matern52" if isinstance(self.covar_module.base_kernel, Matern52KernelDirectionalGrad) else "rbf"
+        eng.missing_targets = bool(getattr(self, "missing_targets", False))
         return eng
 
     # --- parameter plumbing for the HIP engine (order = _step.PARAM_NAMES) ---
@@ -494,6 +498,13 @@ class TrainLoop:
             prm.grad = None
         return result
 
+    def set_missing_targets(self):
+        """NaN entries of the resident targets are observations that do not exist from here on (``GPModel.missing_targets``; the engine's
+        masked per-output step and collapsed statistics): Cholesky-whitened per-point model, float32, one rank -- anything else is refused.
+        ``num_data`` of the objective becomes its value times the present fraction of Y, taken once here (one reduction, one host read)."""
+        _enable_missing_targets(self)
+        return self
+
     def finish(self):
         """drain the replay pipeline (the status of the last replayed / deferred step is checked here)"""
         self._graph_check_previous()
@@ -531,6 +542,7 @@ def setup_training(train_dataset, num_inducing=128, num_directions=1, minibatch_
                    dfree=False, shared=False, variational_initialization=None, data_directions=None, kernel="rbf",
                    ard_num_dims=None):
     """Everything ``train_gp`` does before its loop (directional_vi.py:130-219); returns a TrainLoop.
+    NaN targets: ``TrainLoop.set_missing_targets()`` on the loop this returns (``train_gp(..., missing_targets=True)`` does that).
     ``inducing_data_initialization``: True (the first M data rows), False (uniform draws), or "kmeans" -- k-means centroids and gradient
     directions from the training tensors (``_kmeans_start``; one rank; ``fixed_inducing_locations`` wins over it).
     ``kernel`` ("rbf", the default, or "matern52"): the covariance family -- Matern-5/2 (scalar lengthscale, or ARD with
@@ -711,16 +723,25 @@ def train_gp(train_dataset, num_inducing=128,
       ``max_steps`` (int): stop after this many optimisation steps;
       ``ard_num_dims`` (int, the input dimension): one lengthscale per input dimension (``setup_training``);
       ``kernel`` ("rbf" or "matern52"): the covariance family (``setup_training``);
-      ``variational_initialization`` (None or "optimal"): start q(u) at its closed-form optimum (``setup_training``).
+      ``variational_initialization`` (None or "optimal"): start q(u) at its closed-form optimum (``setup_training``);
+      ``missing_targets`` (bool): NaN entries of the targets are observations that do not exist (``TrainLoop.set_missing_targets``).
     """
     assert num_directions == minibatch_dim
+    missing = bool(args.get("missing_targets", False))
+    if missing and args.get("variational_initialization") not in (None, "optimal"):
+        raise ValueError("variational_initialization must be None or 'optimal', got %r" % (args.get("variational_initialization"),))
     loop = setup_training(train_dataset, num_inducing, num_directions, minibatch_size, minibatch_dim, num_epochs,
                           learning_rate_hypers, inducing_data_initialization, lr_sched, mll_type, gamma,
                           fixed_inducing_locations, seed=args.get("seed"), use_ngd=use_ngd,
                           learning_rate_ngd=learning_rate_ngd, use_ciq=use_ciq,
                           num_contour_quadrature=num_contour_quadrature, model_class=args.get("_model_class"),
                           shared=bool(args.get("_shared")), data_directions=data_directions, kernel=args.get("kernel", "rbf"),
-                          ard_num_dims=args.get("ard_num_dims"), variational_initialization=args.get("variational_initialization"))
+                          ard_num_dims=args.get("ard_num_dims"),
+                          variational_initialization=None if missing else args.get("variational_initialization"))
+    if missing:                                              # (before any pass over the targets: the optimal start included)
+        loop.set_missing_targets()
+        if args.get("variational_initialization") == "optimal":
+            loop.refit_variational(data_directions=data_directions, seed=args.get("seed"))
     n_samples = loop.X.shape[0]
     stride = (num_directions if loop.data_directions is None else loop.data_directions) + 1      # outputs per minibatch point
     max_steps = args.get("max_steps")
@@ -734,7 +755,11 @@ def train_gp(train_dataset, num_inducing=128,
             if report:
                 means = output.mean[::stride]
                 stds = output.value_variance.sqrt()          # = output.variance.sqrt()[::num_directions + 1]
-                nll = -torch.distributions.Normal(means, stds).log_prob(y_batch[::stride]).mean()
+                values = y_batch[::stride]
+                if missing:                                  # the present function values only
+                    ok = ~torch.isnan(values)
+                    means, stds, values = means[ok], stds[ok], values[ok]
+                nll = -torch.distributions.Normal(means, stds).log_prob(values).mean()
                 print(f"Epoch: {i}; total_step: {total_step}, loss: {loss.item()}, nll: {nll}")
                 sys.stdout.flush()
             total_step += 1
@@ -748,6 +773,42 @@ def train_gp(train_dataset, num_inducing=128,
         print(f"Done! loss: {loss.item()}")
         print("\nDone Training!")
     return loop.model, loop.likelihood
+
+
+def _enable_missing_targets(loop):
+    """``TrainLoop.set_missing_targets``: the refusals on the loop's switches alone, then the model's switch and the scaled ``num_data``"""
+    model = loop.model
+    no = lambda what: ValueError("missing_targets is built for the Cholesky-whitened per-point DSVGP model in float32 on one rank, not "
+                                 "for %s" % what)
+    if not isinstance(model, GPModel) or loop.dfree or getattr(loop, "plain", False) or loop.full_gradient:
+        raise no("the dfree / shared / full-gradient / plain harnesses")
+    eng = model.engine
+    if eng.whitening != "cholesky" or eng.shared_directions or eng.data_outputs != "all":
+        raise no("CIQ whitening, shared directions or derivative-free data")
+    if isinstance(model.variational_strategy._variational_distribution, NaturalVariationalDistribution):
+        raise no("natural parameters (NGD)")
+    if loop.dp is not None:
+        raise no("a collective with world > 1")
+    if loop.X.dtype != torch.float32:
+        raise no("a float64 dataset")
+    if getattr(model, "missing_targets", False):
+        return                                               # (already on: num_data was scaled then)
+    model.missing_targets = True
+    loop.mll.num_data = _present_num_data(loop.mll.num_data, loop.Y)
+
+
+def _present_num_data(num_data, Y):
+    """``num_data`` times the present (not NaN) fraction of the targets Y: one reduction, one host read"""
+    return float(num_data) * float((~torch.isnan(Y)).sum().item()) / float(max(Y.numel(), 1))
+
+
+def _default_num_data(model, X, Y, num_data):
+    """the harness's own ``num_data``, (dim + 1) n_samples -- times the present fraction of Y for a model with ``missing_targets``"""
+    if num_data is not None:
+        return num_data
+    n_samples, dim = X.shape
+    num_data = (dim + 1) * n_samples
+    return _present_num_data(num_data, Y) if getattr(model, "missing_targets", False) else num_data
 
 
 def fit_variational(model, likelihood, dataset_or_tensors, minibatch_size=4096, data_directions=None, num_data=None, seed=None,
@@ -765,7 +826,7 @@ def fit_variational(model, likelihood, dataset_or_tensors, minibatch_size=4096, 
     n_samples, dim = X.shape
     for x_batch, y_batch, D in _collapsed_chunks(X, Y, pd, minibatch_size, _collapsed_columns(n_samples, dim, pd, minibatch_size, seed)):
         acc.add(x_batch, y_batch, D)
-    result = acc.solve((dim + 1) * n_samples if num_data is None else num_data)
+    result = acc.solve(_default_num_data(model, X, Y, num_data))
     _write_variational(model, result)
     return result
 
@@ -844,7 +905,7 @@ def collapsed_loss_and_grads(model, likelihood, dataset_or_tensors, minibatch_si
     columns = _collapsed_columns(n_samples, dim, pd, minibatch_size, seed)
     for x_batch, y_batch, D in _collapsed_chunks(X, Y, pd, minibatch_size, columns):
         acc.add(x_batch, y_batch, D)
-    result = acc.solve((dim + 1) * n_samples if num_data is None else num_data)
+    result = acc.solve(_default_num_data(model, X, Y, num_data))
     acc.begin_backward(result)
     for x_batch, y_batch, D in _collapsed_chunks(X, Y, pd, minibatch_size, columns):
         acc.add_backward(x_batch, y_batch, D)
@@ -860,11 +921,12 @@ def collapsed_loss_and_grads(model, likelihood, dataset_or_tensors, minibatch_si
 
 def train_collapsed(train_dataset, num_inducing=128, num_directions=1, num_iterations=50, learning_rate_hypers=0.01, minibatch_size=4096,
                     data_directions=None, inducing_data_initialization=True, fixed_inducing_locations=None, kernel="rbf",
-                    ard_num_dims=None, seed=None, num_data=None, workspace_budget=1 << 30, verbose=True, tensors=None):
+                    ard_num_dims=None, seed=None, num_data=None, workspace_budget=1 << 30, verbose=True, tensors=None,
+                    missing_targets=False):
     """Train a derivative GP on its hyper-parameters, inducing points and inducing directions alone, with q(u) exact at every iterate
     (Titsias' SGPR for the directional-derivative model; RBF, ARD and Matern-5/2).  The model is built the way ``setup_training``
     builds it (``kernel``, ``ard_num_dims``, ``inducing_data_initialization``, ``fixed_inducing_locations``, ``seed`` and ``verbose``
-    as ``train_gp`` understands them); each of the ``num_iterations`` iterations is one ``collapsed_loss_and_grads`` over the whole data
+    as ``train_gp`` understands them; ``missing_targets``: NaN targets do not exist); each of the ``num_iterations`` iterations is one ``collapsed_loss_and_grads`` over the whole data
     set -- chunks of ``minibatch_size`` points, derivative columns drawn once per iteration -- and one Adam step at
     ``learning_rate_hypers``; a final ``fit_variational`` leaves q(u) at the optimum of the final hyper-parameters.
     Returns (model, likelihood)."""
@@ -872,6 +934,10 @@ def train_collapsed(train_dataset, num_inducing=128, num_directions=1, num_itera
                           inducing_data_initialization, None, "ELBO", 0.1, fixed_inducing_locations, seed=seed, tensors=tensors,
                           data_directions=data_directions, kernel=kernel, ard_num_dims=ard_num_dims)
     model, likelihood = loop.model, loop.likelihood
+    if missing_targets:
+        loop.set_missing_targets()
+        if num_data is None:
+            num_data = loop.mll.num_data                 # the present fraction was taken once, there
     optimizer = loop.hyperparameter_optimizer
     rng = random.Random(seed) if seed is not None else random
     pass_seed = lambda: rng.randrange(2 ** 31)

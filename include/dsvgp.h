@@ -1077,6 +1077,37 @@ int dsvgp_collapsed_grad_chunk(dsvgp_ctx* ctx, int Mp, int Bp, const float* Kzx,
                                const double* Q, int64_t ldq, const double* alpha, const double* adj, float* K_bar, int64_t ldkb,
                                float* diag_bar, double* rho_sum, void* workspace);
 
+/* ---- missing observations (csrc/missing.hip): a NaN entry of y is an observation that does not exist.  The present
+ * mask is derived from y inside the kernels, the present rows are counted on the device, and the unchanged kernels behind these entries see
+ * exact zeros on the missing rows.  Inf is not a mask value: it propagates as before.  Fixed-order sums (per-workgroup partials joined in
+ * workgroup order), no floating-point atomics, no host read, no allocation: two identical calls give bitwise equal results.
+ *   dsvgp_likelihood_terms_masked      dsvgp_likelihood_terms over the present rows with global_rows = n, their count: mu_bar, var_bar and
+ *                                      varn_out are exactly 0 on a missing row; out_scalars[1..4] carry the 1 / n of the loss as before and
+ *                                      out_scalars[0] = sum ll / n is ALREADY normalised, so dsvgp_step_epilogue takes rows = 1.  n = 0: every
+ *                                      output is 0 (the loss is then KL / num_data).  *n_present (device int) = n.  workspace:
+ *                                      dsvgp_likelihood_terms_masked_workspace_bytes() bytes, 16-byte aligned.  ncols = 0: out_scalars and
+ *                                      *n_present are cleared, no launch.
+ *   dsvgp_collapsed_accumulate_masked  dsvgp_collapsed_accumulate with: the columns of A64 whose target is missing set to exactly 0 before the
+ *                                      (unchanged) fp64 MFMA product, r = 0 there, [0] += the PRESENT entries of prior_diag, [1] += the present
+ *                                      count and the reserved word [2] += the present count of value rows (j % (pd + 1) == 0; the scalar RBF
+ *                                      prior diagonal's backward needs it).  Bp must be a multiple of pd + 1.
+ *   dsvgp_collapsed_grad_chunk_masked  dsvgp_collapsed_grad_chunk with K_bar's columns, diag_bar and the contribution to rho_sum exactly 0 on the
+ *                                      missing rows: the missing columns of Kzx are zeroed IN PLACE and y is copied with the constant in the
+ *                                      missing entries (residual exactly 0), the unchanged chunk call runs on them, and dg-bar is cleared on
+ *                                      the missing rows.  workspace: dsvgp_collapsed_grad_chunk_masked_bytes(Mp, Bp) bytes, 8-byte aligned.
+ * DSVGP_EINVAL: a null pointer (diag_bar excepted), a negative size, mll_type outside {0, 1}, Bp not a multiple of pd + 1, whatever the
+ * unmasked sibling refuses; DSVGP_EALIGN: a misaligned pointer.  Size 0 returns 0 without a launch where the sibling does.                    */
+size_t dsvgp_likelihood_terms_masked_workspace_bytes(void);
+int dsvgp_likelihood_terms_masked(dsvgp_ctx* ctx, const float* mu, const float* var, const float* y, int ncols, int p, const float* hyp,
+                                  int mll_type, float* mu_bar, float* var_bar, float* varn_out, float* out_scalars, int* n_present,
+                                  void* workspace);
+int dsvgp_collapsed_accumulate_masked(dsvgp_ctx* ctx, void* state, int Mp, double* A64, int64_t lda, int Bp, int pd, const float* y,
+                                      const float* constant, const float* prior_diag);
+size_t dsvgp_collapsed_grad_chunk_masked_bytes(int Mp, int Bp);
+int dsvgp_collapsed_grad_chunk_masked(dsvgp_ctx* ctx, int Mp, int Bp, float* Kzx, int64_t ldk, const float* y, const float* constant,
+                                      const double* Q, int64_t ldq, const double* alpha, const double* adj, float* K_bar, int64_t ldkb,
+                                      float* diag_bar, double* rho_sum, void* workspace);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
