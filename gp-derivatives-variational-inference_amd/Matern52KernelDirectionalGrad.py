@@ -9,51 +9,7 @@ ScaleKernel factor), float32 only.  A scalar lengthscale runs as d equal ARD len
 import torch
 
 from . import _ops
-
-
-class _Matern52KernelFn(torch.autograd.Function):
-    """K(x1, x2; v1, v2) on ``dsvgp_pack_points_ard`` packs, ``ell`` [d]: ``dsvgp_kernel_fwd_matern52`` and two calls of
-    ``dsvgp_kernel_bwd_matern52``.  The first returns side 1's gradients and the whole lengthscale gradient (both sides' packed rows depend
-    on ell); the second, on G^T with the sides swapped, only side 2's points and directions -- d_ell is not asked for again."""
-
-    @staticmethod
-    def _packs(x1, x2, v1, v2, ell):
-        if x1.dtype == torch.float64:
-            raise ValueError("float64 inputs are not supported by the Matern-5/2 kernel")
-        ctx = _ops.Context.get(x1.device)
-        n1, d = x1.shape
-        n2 = x2.shape[0]
-        p1 = v1.shape[0] // n1 if n1 else 0
-        p2 = v2.shape[0] // n2 if n2 else 0
-        hyp = torch.tensor([1.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=x1.device)
-        ellc = ell.detach().float().reshape(-1).contiguous()
-        x1c = x1.detach().float().contiguous()
-        center = _ops.column_mean(ctx, x1c)
-        pk1 = _ops.pack_points_ard(ctx, x1c, v1.detach().float().contiguous(), p1, ellc, center)
-        pk2 = _ops.pack_points_ard(ctx, x2.detach().float().contiguous(), v2.detach().float().contiguous(), p2, ellc, center)
-        return ctx, hyp, ellc, pk1, pk2, n1, n2, d, p1, p2
-
-    @staticmethod
-    def forward(actx, x1, x2, v1, v2, ell):
-        ctx, hyp, _, pk1, pk2, n1, n2, d, p1, p2 = _Matern52KernelFn._packs(x1, x2, v1, v2, ell)
-        actx.save_for_backward(x1, x2, v1, v2, ell)
-        return _ops.kernel_fwd_matern52(ctx, pk1, n1, p1, pk2, n2, p2, d, hyp)
-
-    @staticmethod
-    def backward(actx, G):
-        x1, x2, v1, v2, ell = actx.saved_tensors
-        ctx, hyp, ellc, pk1, pk2, n1, n2, d, p1, p2 = _Matern52KernelFn._packs(x1, x2, v1, v2, ell)
-        need = actx.needs_input_grad
-        G = G.float().contiguous()
-        z = lambda t: torch.zeros(t.shape, dtype=torch.float32, device=t.device)
-        d_x1, d_v1, d_ell, d_hyp = z(x1), z(v1), torch.zeros_like(ellc), torch.zeros(4, dtype=torch.float32, device=x1.device)
-        _ops.kernel_bwd_matern52(ctx, G, pk1, n1, p1, pk2, n2, p2, d, ellc, hyp, False, d_x1, d_v1, d_ell, d_hyp)
-        d_x2 = d_v2 = None
-        if need[1] or need[3]:
-            d_x2, d_v2, scratch = z(x2), z(v2), torch.zeros(4, dtype=torch.float32, device=x1.device)
-            _ops.kernel_bwd_matern52(ctx, G.t().contiguous(), pk2, n2, p2, pk1, n1, p1, d, ellc, hyp, False, d_x2, d_v2, None, scratch)
-        cast = lambda g, t: None if g is None else g.to(t.dtype)
-        return cast(d_x1, x1), cast(d_x2, x2), cast(d_v1, v1), cast(d_v2, v2), d_ell.to(ell.dtype).reshape(ell.shape)
+from ._family import MATERN52, PackKernelFn
 
 
 class Matern52KernelDirectionalGrad(torch.nn.Module):
@@ -92,7 +48,7 @@ class Matern52KernelDirectionalGrad(torch.nn.Module):
         # d lengthscales for the pack (a scalar: d equal ones; autograd sums the vector's gradient back into the scalar)
         ell = self.lengthscale.reshape(-1).to(x1.device).expand(d)
         if not diag:    # an autograd participant: gradients reach x1, x2, v1, v2 and the lengthscale through dsvgp_kernel_bwd_matern52
-            return _Matern52KernelFn.apply(x1, x2, v1, v2, ell)
+            return PackKernelFn.apply(MATERN52, x1, x2, v1, v2, ell)
         if not (n1 == n2 and torch.eq(x1, x2).all() and torch.eq(v1, v2).all()):
             raise RuntimeError("diag=True only works when x1 == x2 and v1 == v2")
         with torch.no_grad():

@@ -16,6 +16,7 @@ repeated (A_t == A); everything else keeps the reference's arithmetic precision:
 Cholesky / triangular solves.
 """
 import collections
+import contextlib
 import math
 import os
 import time
@@ -23,6 +24,7 @@ import time
 import torch
 
 from . import _lib, _ops
+from ._family import MATERN52, RBF, RBF_ARD
 from ._lib import A_LOWER, A_UPPER, B_LOWER, OUT_LOWER, TRANS_A, TRANS_B
 
 KZZ_JITTER = 1e-3     # LazyTensor.add_jitter() default (DGVS.py:144)
@@ -593,11 +595,11 @@ class CollapsedAccumulator:
     Repeats are NOT bitwise equal: the fp64 Gram product's split-K slices meet in atomics on the live statistics (run-order rounding of
     G, b and yy, ~1e-16 relative); the two scalar sums and everything in ``solve`` / ``evaluate`` have fixed orders."""
 
-    def __init__(self, engine, hyp, packZ, L, dims, inverse_ws, center, constant, ell, matern, workspace_budget):
+    def __init__(self, engine, hyp, packZ, L, dims, inverse_ws, center, constant, ell, family, workspace_budget):
         self.device = engine.device
         self.M, self.d, self.p, self.Mp = dims
         self._hyp, self._packZ, self._L, self._center, self._constant = hyp, packZ, L, center, constant
-        self._ell, self._matern = ell, matern
+        self._ell, self._family = ell, family     # constrained lengthscales [d] (None: RBF) and the ``_family`` entry it was made with
         self._nb = engine.trsm_nb
         self._inv = inverse_ws                                   # L^-1 | L^-T (2 M'^2 doubles): the head of every solve's workspace
         self.workspace_budget = int(workspace_budget)
@@ -692,20 +694,16 @@ class CollapsedAccumulator:
             ws = torch.empty(int(ws_bytes), dtype=torch.uint8, device=self.device)
             ws[:self._inv.numel()].copy_(self._inv)
             self._buf["trsm_ws"] = ws
-        fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
+        fam = self._family
         y = y.contiguous()
         for r0 in range(0, B, rows):
             nb_ = min(rows, B - r0)
             Bp = nb_ * q
             xc = x[r0:r0 + nb_].contiguous()
             Dc = D[r0 * pd:(r0 + nb_) * pd].contiguous() if pd else None
-            if self._ell is not None:
-                packX = _ops.pack_points_ard(ctx, xc, Dc, pd, self._ell, self._center)
-                diag = (_ops.kernel_diag_matern52 if self._matern else _ops.kernel_diag_ard)(ctx, packX, nb_, pd, self.d, self._hyp)
-            else:
-                packX = _ops.pack_points(ctx, xc, Dc, pd, self._hyp, self._center)
-                diag = _ops.kernel_diag(ctx, nb_, pd, self._hyp)
-            Kzx = fwd(ctx, self._packZ, self.M, self.p, packX, nb_, pd, self.d, self._hyp, out=self._get("Kzx", Mp * Bp, f32).view(Mp, Bp))
+            packX = fam.pack(ctx, xc, Dc, pd, self._ell, self._hyp, self._center)
+            diag = fam.diag(ctx, packX, nb_, pd, self.d, self._hyp)
+            Kzx = fam.fwd_rect(ctx, self._packZ, self.M, self.p, packX, nb_, pd, self.d, self._hyp, out=self._get("Kzx", Mp * Bp, f32).view(Mp, Bp))
             A64 = self._get("A64", (Mp + 1) * Bp, f64).view(Mp + 1, Bp)
             _ops.trsm(ctx, self._L, Kzx, False, A64[:Mp], None, self._nb, ws, reuse_inverse=True)
             if self._missing:
@@ -804,18 +802,8 @@ class CollapsedAccumulator:
                      "rho_sum": torch.zeros(1, dtype=f64, device=dev),
                      "dZ": torch.zeros(M, d, dtype=f32, device=dev), "dV": torch.zeros(M * p, d, dtype=f32, device=dev),
                      "d_hyp": torch.zeros(4, dtype=f32, device=dev),
-                     "d_ell": torch.zeros(d, dtype=f32, device=dev) if self._ell is not None else None}
+                     "d_ell": torch.zeros(d, dtype=f32, device=dev) if self._family.packs_carry_ell else None}
         return self
-
-    def _kernel_bwd_bytes(self, n2, p2, symmetric):
-        M, d, p = self.M, self.d, self.p
-        if self._matern:
-            return _ops.kernel_bwd_matern52_workspace_bytes(M, p, n2, p2, d)
-        if self._ell is not None:
-            return _ops.kernel_bwd_ard_workspace_bytes(M, p, n2, p2, d)
-        if symmetric:
-            return int(_lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, n2, d, p))
-        return _ops.kernel_bwd_rect_workspace_bytes(M, p, n2, p2, d)
 
     @torch.no_grad()
     def add_backward(self, x, y, D=None):
@@ -832,11 +820,11 @@ class CollapsedAccumulator:
         ctx = _ops.Context.get(self.device)
         M, d, p, Mp, q = self.M, self.d, self.p, self.Mp, pd + 1
         rows = self.chunk_rows(pd, backward=True)
-        fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
+        fam = self._family
         dZ, dV, d_hyp, d_ell = st["dZ"], st["dV"], st["d_hyp"], st["d_ell"]
         y = y.contiguous()
         nmax = min(rows, B)
-        kws = self._get("kbwd_ws", self._kernel_bwd_bytes(nmax, pd, False), torch.uint8)
+        kws = self._get("kbwd_ws", fam.bwd_bytes(M, p, nmax, pd, d, False), torch.uint8)
         chunk_bytes = _ops.collapsed_grad_chunk_masked_bytes if self._missing else _ops.collapsed_grad_chunk_bytes
         chunk = _ops.collapsed_grad_chunk_masked if self._missing else _ops.collapsed_grad_chunk     # (masked: exact zeros on NaN rows)
         cws = self._get("cgrad_ws", (chunk_bytes(Mp, nmax * q) + 7) // 8, f64)
@@ -846,23 +834,17 @@ class CollapsedAccumulator:
             xc = x[r0:r0 + nb_].contiguous()
             Dc = D[r0 * pd:(r0 + nb_) * pd].contiguous() if pd else None
             diag = dbar = None
-            if self._ell is not None:
-                packX = _ops.pack_points_ard(ctx, xc, Dc, pd, self._ell, self._center)
-                diag = (_ops.kernel_diag_matern52 if self._matern else _ops.kernel_diag_ard)(ctx, packX, nb_, pd, d, self._hyp)
+            packX = fam.pack(ctx, xc, Dc, pd, self._ell, self._hyp, self._center)
+            if fam.diag_bwd is not None:             # (else the prior diagonal's backward is ``finish_backward``'s closed form)
+                diag = fam.diag(ctx, packX, nb_, pd, d, self._hyp)
                 dbar = self._get("diag_bar", Bp, f32)
-            else:
-                packX = _ops.pack_points(ctx, xc, Dc, pd, self._hyp, self._center)
             ld = (Bp + 3) // 4 * 4                   # rows 16-byte addressable: the product's float operand takes the vector-load kernels
-            Kzx = fwd(ctx, self._packZ, M, p, packX, nb_, pd, d, self._hyp, out=self._get("Kzx", Mp * ld, f32).view(Mp, ld)[:, :Bp])
+            Kzx = fam.fwd_rect(ctx, self._packZ, M, p, packX, nb_, pd, d, self._hyp, out=self._get("Kzx", Mp * ld, f32).view(Mp, ld)[:, :Bp])
             Kbar = self._get("Kbar", Mp * ld, f32).view(Mp, ld)[:, :Bp]
             chunk(ctx, Mp, Kzx, y[r0 * q:(r0 + nb_) * q], self._constant, st["Q"], st["alpha"], st["adj"], Kbar, dbar, st["rho_sum"], cws)
-            if self._ell is not None:
-                bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
-                bwd(ctx, Kbar, self._packZ, M, p, packX, nb_, pd, d, self._ell, self._hyp, False, dZ, dV if p > 0 else None, d_ell, d_hyp, kws)
-                diag_bwd = _ops.kernel_diag_matern52_bwd if self._matern else _ops.kernel_diag_ard_bwd
-                diag_bwd(ctx, packX, nb_, pd, d, self._ell, self._hyp, diag, dbar, d_ell, d_hyp)
-            else:
-                _ops.kernel_bwd_rect(ctx, Kbar, self._packZ, M, p, packX, nb_, pd, d, self._hyp, dZ, dV, d_hyp, kws)
+            fam.bwd(ctx, Kbar, self._packZ, M, p, packX, nb_, pd, d, self._ell, self._hyp, False, dZ, dV, d_ell, d_hyp, kws)
+            if fam.diag_bwd is not None:
+                fam.diag_bwd(ctx, packX, nb_, pd, d, self._ell, self._hyp, diag, dbar, d_ell, d_hyp)
         st["rows"] += B * q
         st["points"] += B
         return self
@@ -882,13 +864,10 @@ class CollapsedAccumulator:
         ctx = _ops.Context.get(self.device)
         dev, M, d, p = self.device, self.M, self.d, self.p
         dZ, dV, d_hyp, d_ell, adj = st["dZ"], st["dV"], st["d_hyp"], st["d_ell"], st["adj"]
-        kws = self._get("kbwd_ws", self._kernel_bwd_bytes(M, p, True), torch.uint8)
-        if self._ell is not None:
-            bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
-            bwd(ctx, st["Kzz_bar"], self._packZ, M, p, self._packZ, M, p, d, self._ell, self._hyp, True, dZ, dV if p > 0 else None, d_ell,
-                d_hyp, kws)
-        else:
-            _ops.kernel_bwd(ctx, st["Kzz_bar"], self._packZ, M, self._packZ, M, d, p, self._hyp, True, dZ, dV, d_hyp, kws)
+        fam = self._family
+        kws = self._get("kbwd_ws", fam.bwd_bytes(M, p, M, p, d, True), torch.uint8)
+        fam.bwd(ctx, st["Kzz_bar"], self._packZ, M, p, self._packZ, M, p, d, self._ell, self._hyp, True, dZ, dV, d_ell, d_hyp, kws)
+        if fam.diag_bwd is None:
             # the scalar RBF prior diagonal s [1, 1 / ell^2, ...]: dg-bar = w on every entry, in closed form
             ell, s, n_der, n_val = self._hyp[0].to(f64), self._hyp[1].to(f64), float(st["rows"] - st["points"]), float(st["points"])
             if self._missing:                            # present value / derivative rows: device counts of the first pass
@@ -898,10 +877,7 @@ class CollapsedAccumulator:
         d_hyp[2] += adj[1].to(f32)
         rl, rs, rn = self._raw
         g_l, g_s, g_n = torch.zeros_like(rl), torch.zeros_like(rs), torch.zeros_like(rn)
-        if self._ell is not None:
-            _ops.hyp_backward_ard(ctx, rl, rs, rn, d_ell, d_hyp, g_l, g_s, g_n)
-        else:
-            _ops.hyp_backward(ctx, rl, rs, rn, d_hyp, g_l, g_s, g_n)
+        fam.hyp_backward(ctx, rl, rs, rn, d_ell, d_hyp, g_l, g_s, g_n)
         host = torch.cat([adj, st["rho_sum"], st["info"].to(f64)]).tolist()            # the one host read
         self._bwd = None
         if int(host[9]) != 0 or not all(math.isfinite(v) for v in host[:9]):
@@ -916,6 +892,53 @@ class CollapsedAccumulator:
                  "inducing_points": dZ.reshape(shapes["inducing_points"]),
                  "inducing_directions": dV.reshape(shapes["inducing_directions"])}
         return host[3], grads
+
+
+class _Call:
+    """What an entry of the engine keeps while it is being queued (``ElboEngine._call``, None outside ``_in_call``): the ``_family`` entry,
+    the data side's direction count of a rectangular training step (``train_pd``, else None), the constrained lengthscales [d] of the
+    factor in use (``ell``, set by ``_factor`` or from the evaluation cache), their gradient (``d_ell``), the prior diagonal of the data in
+    flight (``diag``, set by ``_interp``) and the caller's parameters where the evaluation cache is keyed on them (``key_params``)."""
+    __slots__ = ("family", "train_pd", "ell", "d_ell", "diag", "key_params")
+
+    def __init__(self, family, train_pd, d_ell, key_params):
+        self.family, self.train_pd, self.d_ell, self.key_params = family, train_pd, d_ell, key_params
+        self.ell = self.diag = None
+
+
+# The switches an entry may not be built for: name -> predicate(engine, params, x, fast).  A refusal list (below) walks them in ITS order
+# with ITS wording: rows of (switch, training steps only, what the message names).
+_SWITCHES = {
+    "float64": lambda e, P, x, fast: P["inducing_points"].dtype != f32 or (x is not None and x.dtype != f32),
+    "float64_engine": lambda e, P, x, fast: type(e) is not ElboEngine or _SWITCHES["float64"](e, P, x, fast),
+    "ciq": lambda e, P, x, fast: e.whitening == "ciq",
+    "natural": lambda e, P, x, fast: "natural_vec" in P,
+    "shared": lambda e, P, x, fast: e.shared_directions,
+    "values": lambda e, P, x, fast: e.data_outputs == "values",
+    "world": lambda e, P, x, fast: e.collective is not None and e.collective.world > 1,
+    "capture": lambda e, P, x, fast: e.capture_mode,
+    "deterministic": lambda e, P, x, fast: e.deterministic,
+    "fast": lambda e, P, x, fast: fast,
+}
+_ARD_REFUSALS = ("%s is not built for ARD lengthscales (a follow-up; the scalar-lengthscale model has it)", (
+    ("float64", False, "a float64 engine"), ("ciq", False, "CIQ whitening"), ("natural", False, "the natural parameterisation"),
+    ("shared", False, "the shared-directions strategy"), ("values", False, "the derivative-free strategy"),
+    ("world", False, "a collective with world = %d"), ("capture", False, "graph capture (capture_mode)"),
+    ("deterministic", True, "the deterministic mode"), ("fast", True, "the Gram fast path (fast=True)")))
+_MATERN_REFUSALS = ("%s is not built for the Matern-5/2 kernel (kernel = 'matern52')", (
+    ("natural", False, "the natural parameterisation"),     # (first: before the lengthscale count is looked at)
+    ("float64_engine", False, "a float64 engine"), ("ciq", False, "CIQ whitening"), ("shared", False, "the shared-directions strategy"),
+    ("values", False, "the derivative-free strategy"), ("world", False, "a collective with world = %d"),
+    ("capture", False, "graph capture (capture_mode)"), ("deterministic", True, "the deterministic mode"),
+    ("fast", True, "the Gram fast path (fast=True)")))
+_MISSING_REFUSALS = ("missing_targets is not built for %s (NaN targets are skipped on the piecewise per-output path and "
+                     "in the collapsed statistics of a float32, Cholesky-whitened, per-point model on one rank)", (
+    ("float64_engine", False, "float64 engines and inputs"), ("ciq", False, "CIQ whitening"), ("natural", False, "natural parameters"),
+    ("shared", False, "shared directions (shared_directions)"), ("values", False, "the derivative-free strategy (data_outputs == 'values')"),
+    ("world", False, "a collective with world = %d"), ("capture", True, "graph capture (capture_mode)"),
+    ("deterministic", True, "the deterministic mode (deterministic)"),
+    ("fast", True, "the Gram fast path (fast=True): it needs per-type present counts, zeroed K_ZX columns and a masked "
+                   "residual pass -- a follow-up")))
 
 
 class ElboEngine:
@@ -1038,31 +1061,18 @@ class ElboEngine:
         # (deferred_check): the ~100 us the host waited per step at M' = 600 leave its critical path
         self.defer_status = False
         self._deferred = None                   # (plan, workspace) of a step whose status has not been read yet
-        # the rectangular TRAINING step (loss_and_grads with pd != p directions per data point, csrc/assemble_rect.hip): pd while such a
-        # step is being queued, None otherwise -- the data side's direction count wherever the piecewise path reads ``_pd``
-        self._train_pd = None
+        # the ``_Call`` of the entry being queued -- a rectangular training step (pd != p directions per data point), ARD lengthscales
+        # (raw_lengthscale [1, d]) or kernel = "matern52" -- set by ``_in_call`` alone; None otherwise, and on the scalar RBF step throughout
+        self._call = None
         # OPT-IN (csrc/missing.hip): True = a NaN entry of y is an observation that does not exist.  The step takes
         # the piecewise per-output path with dsvgp_likelihood_terms_masked in the place of dsvgp_likelihood_terms: the loss is normalised
         # by the present rows of the batch, counted on the device (``present_rows``, int32 [1], of the last such step; never read here),
         # and everything downstream sees exact zeros on the missing rows.  ``collapsed_accumulator`` reads the switch when it is called.
         self.missing_targets = False
         self.present_rows = None
-        # ARD lengthscales (raw_lengthscale [1, d], csrc/assemble_ard.hip): set by the entries built for them (predict, predict_joint,
-        # loss_and_grads) while such a call is being queued.  The packs then carry the per-dimension scaling, hyp[0] = 1, K_ZZ comes
-        # from the wide forward, K_ZX from the rectangular one, both backwards from dsvgp_kernel_bwd_ard; ``_ard_ell`` is the
-        # constrained lengthscale vector of the factor in use and ``_ard_diag`` the prior diagonal s [1, |v~|^2] of the data in flight
-        self._ard = False
-        self._ard_ell = None
-        self._ard_diag = None
-        self._ard_d_ell = None
-        self._eval_cache_ell = None
-        # the covariance family: "rbf" (everything above) or "matern52" (csrc/assemble_matern.hip).  Matern-5/2 runs the ARD path --
-        # ARD packs, hyp[0] = 1, piecewise per-output -- with the Matern tile kernels and prior diagonal in place of the RBF ones; a
-        # scalar raw_lengthscale [1, 1] is expanded to d equal entries for the pack and its gradient summed back.  ``_matern`` is set
-        # (with ``_ard``) while such a call is being queued; with kernel == "rbf" nothing below is reached
+        # the covariance family: "rbf" (scalar or ARD lengthscales, by the shape of raw_lengthscale) or "matern52"; ``_family.py`` has
+        # what each runs on
         self.kernel = "rbf"
-        self._matern = False
-        self._cache_key_params = None
         self._zx_dirs = None                    # (idx, base) of the batch in flight when its directions were stated one-hot (_ops.state_directions)
         self.c_step_used = False        # whether the last step ran through the one-call path
         self.c_step_timed = []          # plans of the steps queued with record_events on, in order
@@ -1077,6 +1087,20 @@ class ElboEngine:
     @trsm_nb.setter
     def trsm_nb(self, value):
         self._trsm_nb = None if value is None else int(value)
+
+    @contextlib.contextmanager
+    def _in_call(self, family, train_pd=None, d_ell=None, key_params=None):
+        """``self._call`` for the length of one entry; None again on every way out"""
+        self._call = call = _Call(family, train_pd, d_ell, key_params)
+        try:
+            yield call
+        finally:
+            self._call = None
+
+    # read-only views of ``_call`` (tests and diagnostics; the engine reads ``_call`` itself)
+    _ard = property(lambda self: self._call is not None and self._call.family.packs_carry_ell)
+    _matern = property(lambda self: self._call is not None and self._call.family is MATERN52)
+    _train_pd = property(lambda self: None if self._call is None else self._call.train_pd)
 
     def _problem_size(self, Mp):
         """resolve the automatic solve regime for an M' x M' inducing system"""
@@ -1119,19 +1143,18 @@ class ElboEngine:
         p = V.shape[0] // M if M else 0
         Mp = M * (p + 1)
         self._problem_size(Mp)
-        if self._is_ard(params) and not self._ard:
+        call = self._call
+        fam = RBF if call is None else call.family
+        if self._is_ard(params) and not fam.packs_carry_ell:
             raise ValueError("this entry is not built for ARD lengthscales (raw_lengthscale with %d entries): predict, predict_joint "
                              "and loss_and_grads are" % params["raw_lengthscale"].numel())
-        if self._ard:
-            self._ard_ell, hyp = _ops.hyp_forward_ard(ctx, params["raw_lengthscale"], params["raw_outputscale"], params["raw_noise"])
-        else:
-            hyp = _ops.hyp_forward(ctx, params["raw_lengthscale"], params["raw_outputscale"], params["raw_noise"])
+        ell, hyp = fam.hyp_forward(ctx, params["raw_lengthscale"], params["raw_outputscale"], params["raw_noise"])
+        if call is not None:
+            call.ell = ell
         # common shift of Z and x (gpytorch covar_dist centres on x1.mean): keeps the fp32 quadratic expansion accurate
         self.center = _ops.column_mean(ctx, Z.contiguous())
-        if self._ard:
-            packZ = _ops.pack_points_ard(ctx, Z.contiguous(), V.contiguous() if p > 0 else None, p, self._ard_ell, self.center)
-        else:
-            packZ = _ops.pack_points(ctx, Z.contiguous(), V.contiguous(), p, hyp, self.center)
+        # (the scalar pack is handed V even when it is empty; the ARD pack None)
+        packZ = fam.pack(ctx, Z.contiguous(), V.contiguous() if p > 0 or not fam.packs_carry_ell else None, p, ell, hyp, self.center)
         self._pending_packZ = packZ
         if side_job is not None:
             main = torch.cuda.current_stream(self.device)
@@ -1170,11 +1193,8 @@ class ElboEngine:
     def _kzz_fwd(self, ctx, packZ, M, d, p, hyp, L):
         """L <- s K_ZZ + jitter I (float64 storage).  ARD: the wide forward whatever d -- the narrow specialised kernels behind
         ``kernel_fwd`` are not used on ARD packs"""
-        if self._matern:
-            _ops.kernel_fwd_matern52(ctx, packZ, M, p, packZ, M, p, d, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
-            return
-        fwd = _ops.kernel_fwd_wide if self._ard else _ops.kernel_fwd
-        fwd(ctx, packZ, M, packZ, M, d, p, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
+        fam = RBF if self._call is None else self._call.family
+        fam.fwd_square(ctx, packZ, M, packZ, M, d, p, hyp, jitter=self.kzz_jitter, out=L, dtype=f64)
 
     @staticmethod
     def _is_ard(params):
@@ -1191,53 +1211,18 @@ class ElboEngine:
         if params["raw_lengthscale"].numel() != d:
             raise ValueError("ARD lengthscales: raw_lengthscale must have one entry per input dimension (%d), got %d"
                              % (d, params["raw_lengthscale"].numel()))
-        no = lambda what: ValueError("%s is not built for ARD lengthscales (a follow-up; the scalar-lengthscale model has it)" % what)
-        if params["inducing_points"].dtype != f32 or x.dtype != f32:
-            raise no("a float64 engine")
-        if self.whitening == "ciq":
-            raise no("CIQ whitening")
-        if "natural_vec" in params:
-            raise no("the natural parameterisation")
-        if self.shared_directions:
-            raise no("the shared-directions strategy")
-        if self.data_outputs == "values":
-            raise no("the derivative-free strategy")
-        coll = self.collective
-        if coll is not None and coll.world > 1:
-            raise no("a collective with world = %d" % coll.world)
-        if self.capture_mode:
-            raise no("graph capture (capture_mode)")
-        if training:
-            if self.deterministic:
-                raise no("the deterministic mode")
-            if fast:
-                raise no("the Gram fast path (fast=True)")
+        self._refuse(_ARD_REFUSALS, params, x, fast, training)
+
+    def _refuse(self, refusals, params, x, fast, training):
+        """walk one refusal list: the first switch that is set (``training``: the training-only rows too) raises with the list's wording"""
+        message, rows = refusals
+        for switch, training_only, what in rows:
+            if (training or not training_only) and _SWITCHES[switch](self, params, x, fast):
+                raise ValueError(message % (what % self.collective.world if switch == "world" else what))
 
     def _missing_refusals(self, params, x, fast=None, training=True):
         """what ``missing_targets`` is not built for, refused on the parameters and switches alone, before any device work"""
-        no = lambda what: ValueError("missing_targets is not built for %s (NaN targets are skipped on the piecewise per-output path and "
-                                     "in the collapsed statistics of a float32, Cholesky-whitened, per-point model on one rank)" % what)
-        if type(self) is not ElboEngine or params["inducing_points"].dtype != f32 or (x is not None and x.dtype != f32):
-            raise no("float64 engines and inputs")
-        if self.whitening == "ciq":
-            raise no("CIQ whitening")
-        if "natural_vec" in params:
-            raise no("natural parameters")
-        if self.shared_directions:
-            raise no("shared directions (shared_directions)")
-        if self.data_outputs == "values":
-            raise no("the derivative-free strategy (data_outputs == 'values')")
-        coll = self.collective
-        if coll is not None and coll.world > 1:
-            raise no("a collective with world = %d" % coll.world)
-        if training:
-            if self.capture_mode:
-                raise no("graph capture (capture_mode)")
-            if self.deterministic:
-                raise no("the deterministic mode (deterministic)")
-            if fast:
-                raise no("the Gram fast path (fast=True): it needs per-type present counts, zeroed K_ZX columns and a masked "
-                         "residual pass -- a follow-up")
+        self._refuse(_MISSING_REFUSALS, params, x, fast, training)
 
     def _is_matern(self):
         """whether the engine's kernel is Matern-5/2; any value but "rbf" / "matern52" is refused"""
@@ -1254,31 +1239,13 @@ class ElboEngine:
     def _matern_params(self, params, x, fast=None, training=False):
         """what the Matern-5/2 entries are not built for, refused on the parameters and switches alone, before any device work; returns
         the parameters with raw_lengthscale as [1, d] (a scalar lengthscale: d equal entries)"""
-        no = lambda what: ValueError("%s is not built for the Matern-5/2 kernel (kernel = 'matern52')" % what)
-        if "natural_vec" in params:
-            raise no("the natural parameterisation")
+        message, rows = _MATERN_REFUSALS
+        self._refuse((message, rows[:1]), params, x, fast, training)
         d = params["inducing_points"].shape[1]
         rl = params["raw_lengthscale"]
         if rl.numel() not in (1, d):
             raise ValueError("Matern-5/2: raw_lengthscale must have 1 entry or one per input dimension (%d), got %d" % (d, rl.numel()))
-        if params["inducing_points"].dtype != f32 or x.dtype != f32 or type(self) is not ElboEngine:
-            raise no("a float64 engine")
-        if self.whitening == "ciq":
-            raise no("CIQ whitening")
-        if self.shared_directions:
-            raise no("the shared-directions strategy")
-        if self.data_outputs == "values":
-            raise no("the derivative-free strategy")
-        coll = self.collective
-        if coll is not None and coll.world > 1:
-            raise no("a collective with world = %d" % coll.world)
-        if self.capture_mode:
-            raise no("graph capture (capture_mode)")
-        if training:
-            if self.deterministic:
-                raise no("the deterministic mode")
-            if fast:
-                raise no("the Gram fast path (fast=True)")
+        self._refuse((message, rows[1:]), params, x, fast, training)
         if rl.numel() == d and rl.dim() == 2:
             return params
         return dict(params, raw_lengthscale=rl.reshape(1, -1).expand(1, d).contiguous())
@@ -1356,8 +1323,9 @@ class ElboEngine:
 
     def _pd(self, p):
         """directional derivatives per DATA point"""
-        if self._train_pd is not None:
-            return self._train_pd
+        call = self._call
+        if call is not None and call.train_pd is not None:
+            return call.train_pd
         return 0 if self.data_outputs == "values" else p
 
     def _train_rect_pd(self, params, x, D):
@@ -1387,11 +1355,11 @@ class ElboEngine:
 
     def _assemble_kzx(self, ctx, packZ, M, packX, B, d, p, hyp, Mp):
         """K_ZX [M', B(pd+1)].  Derivative-free data: the value columns (every (p+1)-th) of the full block matrix."""
-        if self._train_pd is not None:                   # rectangular training step: (p + 1) x (pd + 1) micro-blocks, one launch
-            pd = self._train_pd
+        call = self._call
+        if call is not None and call.train_pd is not None:   # rectangular training step: (p + 1) x (pd + 1) micro-blocks, one launch
+            pd = call.train_pd
             ev = self._event_pair()
-            fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
-            Kzx = fwd(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, B * (pd + 1)), f32))
+            Kzx = call.family.fwd_rect(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, B * (pd + 1)), f32))
             self._event_done("assemble_fwd", ev)
             return Kzx
         if self.data_outputs == "values" and p > 0:
@@ -1436,23 +1404,17 @@ class ElboEngine:
 
     def _kernel_bwd_zx_bytes(self, M, B, d, p):
         """workspace bytes of ``_kernel_bwd_zx``"""
-        if self._matern:
-            return _ops.kernel_bwd_matern52_workspace_bytes(M, p, B, self._train_pd, d)
-        if self._ard:
-            return _ops.kernel_bwd_ard_workspace_bytes(M, p, B, self._train_pd, d)
-        if self._train_pd is not None:
-            return _ops.kernel_bwd_rect_workspace_bytes(M, p, B, self._train_pd, d)
+        call = self._call
+        if call is not None and call.train_pd is not None:
+            return call.family.bwd_bytes(M, p, B, call.train_pd, d, False)
         return _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, B, d, p)
 
     def _kernel_bwd_zx(self, ctx, Kb32, packZ, M, packX, B, d, p, hyp, dZ, dV, d_hyp, kws):
-        if self._train_pd is not None:                   # rectangular training step: the upstream [M', B(pd+1)] as it is
+        call = self._call
+        if call is not None and call.train_pd is not None:   # rectangular training step: the upstream [M', B(pd+1)] as it is
             ev = self._event_pair()
-            if self._ard:                                # d_ell through both sides' packed rows; the data side gets no point gradient
-                bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
-                bwd(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, self._ard_ell, hyp, False, dZ, dV if p > 0 else None,
-                    self._ard_d_ell, d_hyp, kws)
-            else:
-                _ops.kernel_bwd_rect(ctx, Kb32, packZ, M, p, packX, B, self._train_pd, d, hyp, dZ, dV, d_hyp, kws)
+            # (ARD packs: d_ell through both sides' packed rows; the data side gets no point gradient)
+            call.family.bwd(ctx, Kb32, packZ, M, p, packX, B, call.train_pd, d, call.ell, hyp, False, dZ, dV, call.d_ell, d_hyp, kws)
             self._event_done("assemble_bwd", ev)
             return
         if self.data_outputs == "values" and p > 0:
@@ -1475,18 +1437,17 @@ class ElboEngine:
         B = x.shape[0]
         pd = self._pd(p) if rect_pd is None else rect_pd
         Bp = B * (pd + 1)
+        call = self._call
+        fam = RBF if call is None else call.family
         if rect_pd is None:
             packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if p > 0 else None, p, hyp, self.center)
             self._zx_dirs = _ops.stated_directions(D, d, p) if p > 0 else None
             Kzx = self._assemble_kzx(ctx, packZ, M, packX, B, d, p, hyp, Mp)
         else:
-            if self._ard:
-                packX = _ops.pack_points_ard(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, self._ard_ell, self.center)
-            else:
-                packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, hyp, self.center)
+            packX = fam.pack(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, call.ell if call is not None else None, hyp,
+                             self.center)
             self._zx_dirs = None
-            fwd = _ops.kernel_fwd_matern52 if self._matern else _ops.kernel_fwd_rect
-            Kzx = fwd(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, Bp), f32))
+            Kzx = fam.fwd_rect(ctx, packZ, M, p, packX, B, pd, d, hyp, out=self._get("Kzx", (Mp, Bp), f32))
         A64 = self._get("A64", (Mp, Bp), f64)
         A32 = self._get("A32", (Mp, Bp), f32)
         need = _lib.lib.dsvgp_trsm_workspace_bytes(Mp, max(Bp, Mp), self.trsm_nb)
@@ -1511,13 +1472,13 @@ class ElboEngine:
         sws = self._bytes("stats_ws", _lib.lib.dsvgp_stats_workspace_bytes(Mp, Bp))
         _ops.predictive_stats(ctx, A32, W, pd, params["variational_mean"], params["constant"].reshape(-1), hyp, mu, var,
                               sws)
-        if self._ard:
+        if fam.packs_carry_ell:
             # predictive_stats priced the prior diagonal as s [1, 1 / ell^2] with ell = hyp[0] = 1: s on every column.  The ARD
             # kernel's is s [1, |v~_jb|^2] (dsvgp_kernel_diag_ard): add s (|v~_jb|^2 - 1) on the derivative columns (exactly 0 on the
             # value columns, where the diagonal is s itself)
             # (Matern-5/2: s [1, (5/3) |v~_jb|^2], dsvgp_kernel_diag_matern52)
-            self._ard_diag = (_ops.kernel_diag_matern52 if self._matern else _ops.kernel_diag_ard)(ctx, packX, B, pd, d, hyp)
-            var.add_(self._ard_diag - hyp[1])
+            call.diag = fam.diag(ctx, packX, B, pd, d, hyp)
+            var.add_(call.diag - hyp[1])
         return packX, A64, A32, W, mu, var
 
     # ---- public API -----------------------------------------------------------------------------
@@ -1526,10 +1487,8 @@ class ElboEngine:
         """q(f) mean / variance plus likelihood noise: what ``likelihood(model(x)).mean/.variance`` returns.
         ``cache=True`` (eval mode) keeps the Cholesky factor and its inverted blocks across calls while the
         parameters are unchanged, like the reference's ``@cached`` ``_cholesky_factor`` (DGVS.py:72)."""
-        if self._is_matern():
-            return self._predict_matern(params, x, D, cache, False)
-        if self._is_ard(params):
-            return self._predict_ard(params, x, D, cache, False)
+        if self._is_matern() or self._is_ard(params):
+            return self._predict_family(params, x, D, cache, False)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
             self._rect_pd(params, x, D)                 # (refuses a direction count other than the model's)
@@ -1587,10 +1546,8 @@ class ElboEngine:
         MultivariateNormal behind ``likelihood(model(x, derivative_directions=D))`` (reference DGVS.py:199-208), which the
         BO drivers sample jointly (experiments/GNN_bo/gcn_turbo.py:238-239).
         Sigma = s K_XX + 1e-4 I + W^T W - A^T A + noise I: one symmetric kernel assembly and two MFMA Gram products."""
-        if self._is_matern():
-            return self._predict_matern(params, x, D, cache, True)
-        if self._is_ard(params):
-            return self._predict_ard(params, x, D, cache, True)
+        if self._is_matern() or self._is_ard(params):
+            return self._predict_family(params, x, D, cache, True)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
             # NGD-CIQ: the reference's q(f) carries a DIAGONAL covariance, DiagLazyTensor(predictive_var) (CiqDGVS.py:264-267);
@@ -1760,12 +1717,10 @@ class ElboEngine:
         sub["raw_lengthscale"] = rl.reshape(1, -1).expand(1, d).contiguous() if ard else rl
         ctx = _ops.Context.get(self.device)
         self._eval_cache = None
-        self._ard, self._matern = ard, matern
-        try:
+        fam = MATERN52 if matern else RBF_ARD if ard else RBF
+        with self._in_call(fam) as call:
             hyp, packZ, L, dims = self._factor(ctx, sub, sync=True)
-            ell = self._ard_ell.detach().clone() if ard else None
-        finally:
-            self._ard = self._matern = False
+            ell = call.ell.detach().clone() if ard else None
         Mp = dims[3]
         if Mp > _ops.COLLAPSED_MAX_MP:
             raise ValueError("the closed-form optimal q(u) takes M' <= %d (explicit-inverse regime of the Cholesky), got %d"
@@ -1773,7 +1728,7 @@ class ElboEngine:
         keep = lambda t: t.detach().clone().contiguous()
         inverse = self._inverse_ws[:16 * Mp * Mp].clone()
         acc = CollapsedAccumulator(self, keep(hyp), tuple(keep(t) for t in packZ), keep(L), dims, inverse, keep(self.center),
-                                   keep(params["constant"]).reshape(-1)[:1], ell, matern, workspace_budget)
+                                   keep(params["constant"]).reshape(-1)[:1], ell, fam, workspace_budget)
         # what the backward pass maps its gradients to: the raw hyper-parameters (ARD / Matern: the [d] lengthscales that went in) and
         # the shapes ``loss_and_grads`` returns
         acc._raw = tuple(keep(sub[k]).reshape(-1) for k in ("raw_lengthscale", "raw_outputscale", "raw_noise"))
@@ -1952,38 +1907,34 @@ class ElboEngine:
         of y[b] under N(mu[b], roots[b] roots[b]^T) at every point."""
         return _ops.blocks_logpdf(_ops.Context.get(self.device) if roots.is_cuda else None, roots, logdet, mu, y)
 
-    def _predict_ard(self, params, x, D, cache, joint):
-        """predict / predict_joint of a model with ARD lengthscales: the per-output path on ARD packs (csrc/assemble_ard.hip)"""
-        self._ard_refusals(params, x)
-        ctx = _ops.Context.get(self.device)
-        self._ard = True
-        try:
-            return self._predict_chol(ctx, params, x, D, cache, joint=joint)
-        finally:
-            self._ard = False
+    def _family_params(self, params, x, fast=None, training=False):
+        """(family, parameters as the family's kernels take them) of a model with ARD lengthscales or kernel = "matern52", after the
+        family's refusals; ``MATERN52`` expands a scalar lengthscale to d equal entries"""
+        if self._is_matern():
+            return MATERN52, self._matern_params(params, x, fast=fast, training=training)
+        self._ard_refusals(params, x, fast=fast, training=training)
+        return RBF_ARD, params
 
-    def _predict_matern(self, params, x, D, cache, joint):
-        """predict / predict_joint with kernel = "matern52": ``_predict_ard``'s path on the Matern kernels (csrc/assemble_matern.hip).
-        The evaluation cache is keyed on the caller's parameters (a scalar lengthscale is expanded per call) and on the kernel."""
-        expanded = self._matern_params(params, x)
+    def _predict_family(self, params, x, D, cache, joint):
+        """predict / predict_joint of a model with ARD lengthscales or kernel = "matern52": the per-output path on ARD packs
+        (csrc/assemble_ard.hip, csrc/assemble_matern.hip).  Matern-5/2: the evaluation cache is keyed on the caller's parameters (a scalar
+        lengthscale is expanded per call) and on the kernel."""
+        fam, expanded = self._family_params(params, x)
         ctx = _ops.Context.get(self.device)
-        self._ard = self._matern = True
-        self._cache_key_params = params
-        try:
+        with self._in_call(fam, key_params=params if fam.expands_scalar_ell else None):
             return self._predict_chol(ctx, expanded, x, D, cache, joint=joint)
-        finally:
-            self._ard = self._matern = False
-            self._cache_key_params = None
 
     def _predict_chol(self, ctx, params, x, D, cache, joint=False, blocks=False):
         # (the parameters arrive expanded; the evaluation cache below is keyed on them alone: calls with different direction
         #  counts on an unchanged model share the factor)
         rect_pd = self._rect_pd(params, x, D)
-        if self._ard and rect_pd is None:               # ARD: always the rectangular assembly, equal counts included
+        call = self._call
+        fam = RBF if call is None else call.family
+        if fam.packs_carry_ell and rect_pd is None:     # ARD packs: always the rectangular assembly, equal counts included
             rect_pd = self._direction_counts(params, x, D)[1]
         key = tuple((t.data_ptr(), t._version) for t in params.values()) if cache else None
-        if cache and self._matern:
-            key = ("matern52",) + tuple((t.data_ptr(), t._version) for t in self._cache_key_params.values())
+        if cache and call is not None and call.key_params is not None:
+            key = (fam.name,) + tuple((t.data_ptr(), t._version) for t in call.key_params.values())
         hit = cache and self._eval_cache is not None and self._eval_cache[0] == key
         if "natural_vec" in params:
             if hit:
@@ -1993,14 +1944,14 @@ class ElboEngine:
                 params = {k: v for k, v in params.items() if not k.startswith("natural_")}
                 params["variational_mean"], params["chol_variational_covar"] = m32, LS32
         if hit:
-            _, hyp, packZ, L, dims, _ = self._eval_cache
-            self._ard_ell = self._eval_cache_ell
+            _, hyp, packZ, L, dims, _, ell = self._eval_cache
+            if call is not None:
+                call.ell = ell
         else:
             Mz = params["inducing_points"].shape[0]
             pz = params["inducing_directions"].shape[0] // Mz if Mz else 0
             hyp, packZ, L, dims = self._factor(ctx, params, nrhs=x.shape[0] * ((self._pd(pz) if rect_pd is None else rect_pd) + 1))
-            self._eval_cache = (key, hyp, packZ, L, dims, params) if cache else None
-            self._eval_cache_ell = self._ard_ell if self._ard else None
+            self._eval_cache = (key, hyp, packZ, L, dims, params, call.ell if call is not None else None) if cache else None
         packX, _, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=hit, rect_pd=rect_pd)
         if blocks:                                                                 # (predict_blocks: no K_XX, nothing B' x B')
             pd = self._pd(dims[2]) if rect_pd is None else rect_pd
@@ -2010,12 +1961,7 @@ class ElboEngine:
             B = x.shape[0]
             if rect_pd is not None:
                 p = rect_pd                                                        # (the data pack was made with it)
-            if self._matern:
-                Sigma = _ops.kernel_fwd_matern52(ctx, packX, B, p, packX, B, p, d, hyp)
-            elif self._ard:                                                        # (its diagonal is s [1, |v~|^2] by itself)
-                Sigma = _ops.kernel_fwd_wide(ctx, packX, B, packX, B, d, p, hyp)
-            else:
-                Sigma = _ops.kernel_fwd(ctx, packX, B, packX, B, d, p, hyp)        # s K(X, X; D, D), all (p+1)^2 blocks
+            Sigma = fam.fwd_square(ctx, packX, B, packX, B, d, p, hyp)             # s K(X, X; D, D), all (p+1)^2 blocks
             if rect_pd is None and self.data_outputs == "values" and p > 0:
                 Sigma = Sigma[::p + 1, ::p + 1].contiguous()
             if not self._no_middle:
@@ -2037,47 +1983,24 @@ class ElboEngine:
         if self.missing_targets:
             self._missing_refusals(params, x, fast=fast)
             fast = False
-        if self._is_matern():
-            return self._loss_and_grads_matern(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
-        if self._is_ard(params):
-            return self._loss_and_grads_ard(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
+        if self._is_matern() or self._is_ard(params):
+            return self._loss_and_grads_family(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
         train_pd = self._train_rect_pd(params, x, D)       # (refusals first: shapes only, no device work)
         if train_pd is None:
             return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
         B = x.shape[0]
         if y.shape != (B * (train_pd + 1),):
             raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % (B * (train_pd + 1)))
-        self._train_pd = train_pd
-        try:
+        with self._in_call(RBF, train_pd):
             return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, fast)
-        finally:
-            self._train_pd = None
 
-    def _loss_and_grads_ard(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
-        """The step of a model with ARD lengthscales (raw_lengthscale [1, d]): ELBO or PLL on the piecewise per-output path, any number
-        of data directions, with ARD packs, hyp[0] = 1, the wide / rectangular forward and dsvgp_kernel_bwd_ard for K_ZX-bar and
-        K_ZZ-bar (csrc/assemble_ard.hip).  ``fast=None`` takes this path; the Gram fast path (``fast=True``) is refused."""
-        self._ard_refusals(params, x, fast=fast, training=True)
-        if mll_type not in ("ELBO", "PLL"):
-            raise ValueError(mll_type)
-        p, pd = self._direction_counts(params, x, D)
-        if pd > 95:
-            raise ValueError("at most 95 derivative directions per data point, got %d" % pd)
-        B = x.shape[0]
-        if y.shape != (B * (pd + 1),):
-            raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % (B * (pd + 1)))
-        self._ard, self._train_pd = True, pd
-        self._ard_d_ell = torch.zeros(x.shape[1], dtype=f32, device=self.device)
-        try:
-            return self._loss_and_grads_checked(params, x, y, D, num_data, mll_type, global_rows, include_kl, False)
-        finally:
-            self._ard, self._train_pd, self._ard_d_ell, self._ard_diag = False, None, None, None
-
-    def _loss_and_grads_matern(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
-        """The step with kernel = "matern52": ``_loss_and_grads_ard``'s path (ELBO or PLL, piecewise per-output, any number of data
-        directions) with the Matern forward for K_ZZ / K_ZX, dsvgp_kernel_bwd_matern52 for K_ZX-bar / K_ZZ-bar and the Matern prior
-        diagonal.  A scalar raw_lengthscale [1, 1]: its gradient is the sum of the [1, d] gradient (one fixed-shape reduction)."""
-        expanded = self._matern_params(params, x, fast=fast, training=True)
+    def _loss_and_grads_family(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
+        """The step of a model with ARD lengthscales (raw_lengthscale [1, d]) or kernel = "matern52": ELBO or PLL on the piecewise
+        per-output path, any number of data directions, with ARD packs, hyp[0] = 1 and the family's forward, kernel backward (K_ZX-bar and
+        K_ZZ-bar) and prior diagonal (csrc/assemble_ard.hip, csrc/assemble_matern.hip).  ``fast=None`` takes this path; the Gram fast path
+        (``fast=True``) is refused.  Matern-5/2 with a scalar raw_lengthscale [1, 1]: its gradient is the sum of the [1, d] gradient (one
+        fixed-shape reduction)."""
+        fam, expanded = self._family_params(params, x, fast=fast, training=True)
         if mll_type not in ("ELBO", "PLL"):
             raise ValueError(mll_type)
         p, pd = self._direction_counts(expanded, x, D)
@@ -2086,17 +2009,14 @@ class ElboEngine:
         B = x.shape[0]
         if y.shape != (B * (pd + 1),):
             raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % (B * (pd + 1)))
-        self._ard, self._matern, self._train_pd = True, True, pd
-        self._ard_d_ell = torch.zeros(x.shape[1], dtype=f32, device=self.device)
-        try:
-            loss, grads, mu, varn = self._loss_and_grads_checked(expanded, x, y, D, num_data, mll_type, global_rows, include_kl, False)
-        finally:
-            self._ard, self._matern, self._train_pd, self._ard_d_ell, self._ard_diag = False, False, None, None, None
-        g, rl = grads["raw_lengthscale"], params["raw_lengthscale"]
-        if rl.numel() != g.numel():                      # scalar lengthscale: d equal entries went in
-            g = g.sum(dim=-1, keepdim=True)
-        grads["raw_lengthscale"] = g.reshape(rl.shape)
-        return loss, grads, mu, varn
+        with self._in_call(fam, pd, d_ell=torch.zeros(x.shape[1], dtype=f32, device=self.device)):
+            out = self._loss_and_grads_checked(expanded, x, y, D, num_data, mll_type, global_rows, include_kl, False)
+        if fam.expands_scalar_ell:
+            g, rl = out[1]["raw_lengthscale"], params["raw_lengthscale"]
+            if rl.numel() != g.numel():                  # scalar lengthscale: d equal entries went in
+                g = g.sum(dim=-1, keepdim=True)
+            out[1]["raw_lengthscale"] = g.reshape(rl.shape)
+        return out
 
     def _loss_and_grads_checked(self, params, x, y, D, num_data, mll_type, global_rows, include_kl, fast):
         ctx = _ops.Context.get(self.device)
@@ -2771,7 +2691,8 @@ class ElboEngine:
         self._ctx = ctx
         self.c_step_used = False
         self._last_fast = None
-        rect = self._train_pd is not None                  # (never a one-call step: K_ZX and its backward are the rectangular kernels)
+        call = self._call
+        rect = call is not None and call.train_pd is not None      # (never a one-call step: K_ZX and its backward are the rectangular kernels)
         if not rect and self._c_step_eligible(params, x, use_fast, sync):
             pz = params["inducing_directions"].shape[0] // params["inducing_points"].shape[0]
             Bq = x.shape[0] * (pz + 1)
@@ -2786,6 +2707,8 @@ class ElboEngine:
                 raise ValueError("y must be the interleaved target vector of length B*(p+1)=%d" % Bq)
             return self._c_step(ctx, params, x, y.contiguous(), D, num_data, float(Bq if global_rows is None else global_rows),
                                 include_kl, per_output=mll_type)
+        fam = RBF if call is None else call.family
+        train_pd = call.train_pd if rect else None
         Mz = params["inducing_points"].shape[0]
         p = params["inducing_directions"].shape[0] // Mz if Mz else 0
         B = x.shape[0]
@@ -2831,7 +2754,7 @@ class ElboEngine:
                                         scal, kl_buf, dm, dLS, Kb32, Lbar, side)
             varn = torch.empty(0, dtype=f32, device=dev)
         else:
-            packX, A64, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, rect_pd=self._train_pd)
+            packX, A64, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, rect_pd=train_pd)
             mu_bar = torch.empty(Bp, dtype=f32, device=dev)
             var_bar = torch.empty(Bp, dtype=f32, device=dev)
             varn = torch.empty(Bp, dtype=f32, device=dev)
@@ -2865,10 +2788,7 @@ class ElboEngine:
             _ops.gemm(ctx, TRANS_B | OUT_LOWER, Kb64, A64, Lbar, alpha=-1.0)    # L-bar = -tril(K_ZX-bar A^T)
 
         dZ, dV = grads["inducing_points"], grads["inducing_directions"]
-        kws = self._bytes("kbwd_ws", max(self._kernel_bwd_zx_bytes(M, B, d, p),
-                                         _ops.kernel_bwd_matern52_workspace_bytes(M, p, M, p, d) if self._matern
-                                         else _ops.kernel_bwd_ard_workspace_bytes(M, p, M, p, d) if self._ard
-                                         else _lib.lib.dsvgp_kernel_bwd_workspace_bytes(M, M, d, p)))
+        kws = self._bytes("kbwd_ws", max(self._kernel_bwd_zx_bytes(M, B, d, p), fam.bwd_bytes(M, p, M, p, d, True)))
         # K_ZX-bar's kernel backward (HBM-bound read of 4 M' B' bytes) next to the fp64 products of L-bar and the Cholesky backward
         # (matrix-pipe bound): on the side stream from the moment the dense product is done, joined before the K_ZZ kernel backward
         # (both accumulate into Z-bar, V-bar and the hyper-parameter slots)
@@ -2906,22 +2826,19 @@ class ElboEngine:
             Kzzbar = self._chol_backward(ctx, L, Lbar, self._buf["trsm_ws"], Mp, phi_arg=use_fast)
             if zx_done is not None:
                 torch.cuda.current_stream(self.device).wait_event(zx_done)
-            if self._ard:
-                bwd = _ops.kernel_bwd_matern52 if self._matern else _ops.kernel_bwd_ard
-                bwd(ctx, Kzzbar, packZ, M, p, packZ, M, p, d, self._ard_ell, hyp, True, dZ, dV if p > 0 else None, self._ard_d_ell, d_hyp,
-                    kws)
+            if fam.packs_carry_ell:
+                fam.bwd(ctx, Kzzbar, packZ, M, p, packZ, M, p, d, call.ell, hyp, True, dZ, dV, call.d_ell, d_hyp, kws)
             else:
                 _ops.kernel_bwd(ctx, Kzzbar, packZ, M, packZ, M, d, p, hyp, True, dZ, dV, d_hyp, kws)
 
-        if self._ard:
+        if fam.packs_carry_ell:
             # the prior diagonal of the data: likelihood_terms priced it as s [1, 1 / ell^2] at ell = hyp[0] = 1 (scal[3] = sum of
             # var_bar, scal[4] the scalar lengthscale's share).  Both are replaced by the ARD diagonal's own backward -- d_hyp[1] +=
             # sum var_bar diag / s, d_ell[k] += -(2 s / ell_k) sum var_bar v~_k^2 -- and the scalar lengthscale slot stays empty
-            diag_bwd = _ops.kernel_diag_matern52_bwd if self._matern else _ops.kernel_diag_ard_bwd
-            diag_bwd(ctx, packX, B, pd, d, self._ard_ell, hyp, self._ard_diag, var_bar, self._ard_d_ell, d_hyp)
+            fam.diag_bwd(ctx, packX, B, pd, d, call.ell, hyp, call.diag, var_bar, call.d_ell, d_hyp)
             scal[3:5].zero_()
-            _ops.hyp_backward_ard(ctx, params["raw_lengthscale"].reshape(-1), params["raw_outputscale"].reshape(-1),
-                                  params["raw_noise"].reshape(-1), self._ard_d_ell, torch.zeros(4, dtype=f32, device=dev),
+            fam.hyp_backward(ctx, params["raw_lengthscale"].reshape(-1), params["raw_outputscale"].reshape(-1),
+                             params["raw_noise"].reshape(-1), call.d_ell, torch.zeros(4, dtype=f32, device=dev),
                                   grads["raw_lengthscale"].reshape(-1), grads["raw_outputscale"].reshape(-1),
                                   grads["raw_noise"].reshape(-1))     # (outputscale and noise: the epilogue below, from d_hyp)
         if self._dev_scale:
@@ -2945,11 +2862,11 @@ class ElboEngine:
         m = params["variational_mean"]
         LS = params["chol_variational_covar"]
         packZ = self._pending_packZ
-        if self._train_pd is None:
+        pd = None if self._call is None else self._call.train_pd
+        if pd is None:
             packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if p > 0 else None, p, hyp, self.center)
             self._zx_dirs = _ops.stated_directions(D, d, p) if p > 0 else None
         else:                                            # rectangular training step: the data pack with ITS count, same centre
-            pd = self._train_pd
             packX = _ops.pack_points(ctx, x.contiguous(), D.contiguous() if pd > 0 else None, pd, hyp, self.center)
             self._zx_dirs = None
         Kzx = self._assemble_kzx(ctx, packZ, M, packX, B, d, p, hyp, Mp)

@@ -60,7 +60,7 @@ def probe(dsvgp, dev, d, M, p, B, warmup, reps):
     var_new = pred.variance(x, with_noise=True)
     # the alternative for the gradient, on the cached factor of eng2
     ctx = ops.Context.get(dev)
-    _, hyp, packZ, L, _, _ = eng2._eval_cache
+    _, hyp, packZ, L = eng2._eval_cache[:4]
     packX = ops.pack_points(ctx, x, None, 0, hyp, eng2.center)
     rhs = torch.randn(Mp, B, dtype=f64, device=dev)
     sol = torch.empty(Mp, B, dtype=f32, device=dev)
