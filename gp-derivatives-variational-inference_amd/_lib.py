@@ -250,6 +250,9 @@ SIGNATURES = {
     "dsvgp_collapsed_accumulate_masked": (_i, [_p, _p, _i, _p, _l, _i, _i, _p, _p, _p]),
     "dsvgp_collapsed_grad_chunk_masked_bytes": (_z, [_i, _i]),
     "dsvgp_collapsed_grad_chunk_masked": (_i, [_p, _i, _i, _p, _l, _p, _p, _p, _l, _p, _p, _p, _l, _p, _p, _p]),
+    "dsvgp_likelihood_terms_classes_workspace_bytes": (_z, []),
+    "dsvgp_likelihood_terms_classes": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _d, _p, _p, _p, _p, _p]),
+    "dsvgp_collapsed_accumulate_classes": (_i, [_p, _p, _i, _p, _l, _i, _i, _p, _p, _p, _p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

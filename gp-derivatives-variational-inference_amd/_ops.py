@@ -1495,6 +1495,28 @@ def likelihood_terms_masked(ctx, mu, var, y, p, hyp, mll_type, mu_bar, var_bar, 
                                             _ptr(workspace)), "dsvgp_likelihood_terms_masked")
 
 
+def likelihood_terms_classes_workspace(device):
+    """scratch of ``likelihood_terms_classes`` (per-workgroup partial sums; a fixed size)"""
+    return torch.empty(int(lib.dsvgp_likelihood_terms_classes_workspace_bytes()), dtype=torch.uint8, device=device)
+
+
+def likelihood_terms_classes(ctx, mu, var, y, p, hyp, mll_type, global_rows, mu_bar, var_bar, varn, scalars, workspace):
+    """``likelihood_terms`` with one noise per output class (csrc/noise_classes.hip): hyp[2] on the value rows (j % (p + 1) == 0), hyp[3]
+    on the derivative rows.  scalars[1] = d loss / d hyp[2] (value rows), scalars[5] = d loss / d hyp[3] (derivative rows); fixed-order
+    sums, no host read."""
+    for t, name in ((mu, "mu"), (var, "var"), (mu_bar, "mu_bar"), (var_bar, "var_bar"), (varn, "varn")):
+        _req(t, f32, name, 1)
+        if t.numel() != y.numel():
+            raise ValueError("%s must have B' = %d entries, got %d" % (name, y.numel(), t.numel()))
+    if scalars.dtype != f32 or scalars.numel() < 8 or hyp.dtype != f32 or hyp.numel() < 4:
+        raise ValueError("scalars must be 8 float32 values and hyp 4")
+    if workspace is None or workspace.numel() * workspace.element_size() < int(lib.dsvgp_likelihood_terms_classes_workspace_bytes()):
+        raise ValueError("likelihood_terms_classes needs the workspace of likelihood_terms_classes_workspace()")
+    check(lib.dsvgp_likelihood_terms_classes(ctx.h, _ptr(mu), _ptr(var), _ptr(_req(y, f32, "y", 1)), y.numel(), int(p), _ptr(hyp),
+                                             int(mll_type), float(global_rows), _ptr(mu_bar), _ptr(var_bar), _ptr(varn), _ptr(scalars),
+                                             _ptr(workspace)), "dsvgp_likelihood_terms_classes")
+
+
 def abar(ctx, A, U, m, mu_bar, var_bar, out):
     Mp, nc = A.shape
     check(lib.dsvgp_abar(ctx.h, _ptr(A), _ld(A), _ptr(U), _ld(U), Mp, nc, _ptr(m), _ptr(mu_bar), _ptr(var_bar),
@@ -2031,6 +2053,25 @@ def collapsed_accumulate_masked_(ctx, state, Mp, A64, Bp, pd, y, constant, prior
     _req(constant, f32, "constant", 1)
     check(lib.dsvgp_collapsed_accumulate_masked(ctx.h, _ptr(state), int(Mp), _ptr(A64), _ld(A64), int(Bp), int(pd), _ptr(y),
                                                 _ptr(constant), _ptr(prior_diag)), "dsvgp_collapsed_accumulate_masked")
+
+
+def collapsed_accumulate_classes_(ctx, state, Mp, A64, Bp, pd, y, constant, prior_diag, hyp):
+    """``collapsed_accumulate_`` with row weights 1 on value rows and rho = hyp[2] / hyp[3] on derivative rows (csrc/noise_classes.hip): the
+    derivative columns of A64 and of r are scaled by sqrt(rho) in place; state[2] counts the value rows"""
+    _req_collapsed_state(state, Mp)
+    _req(A64, f64, "A64", 2)
+    if A64.shape[0] != Mp + 1 or A64.shape[1] < Bp:
+        raise ValueError("A64 must be [M' + 1, >= B'] = [%d, >= %d], got %s" % (Mp + 1, Bp, tuple(A64.shape)))
+    for t, name in ((y, "y"), (prior_diag, "prior_diag")):
+        _req(t, f32, name, 1)
+        if t.numel() != Bp:
+            raise ValueError("%s must have B' = %d entries, got %d" % (name, Bp, t.numel()))
+    _req(constant, f32, "constant", 1)
+    _req(hyp, f32, "hyp", 1)
+    if hyp.numel() < 4:
+        raise ValueError("hyp must have 4 entries, got %d" % hyp.numel())
+    check(lib.dsvgp_collapsed_accumulate_classes(ctx.h, _ptr(state), int(Mp), _ptr(A64), _ld(A64), int(Bp), int(pd), _ptr(y),
+                                                 _ptr(constant), _ptr(prior_diag), _ptr(hyp)), "dsvgp_collapsed_accumulate_classes")
 
 
 def collapsed_solve(ctx, state, Mp, hyp, num_data, workspace, want_natural=True):

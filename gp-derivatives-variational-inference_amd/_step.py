@@ -614,6 +614,10 @@ class CollapsedAccumulator:
         # that were HANDED to ``add``, present or not -- what the second pass must cover
         self._missing = bool(getattr(engine, "missing_targets", False))
         self._present = None                         # R as the last solve's host read carried it
+        # two noise classes (set by ``collapsed_accumulator`` when the parameters carry ``raw_derivative_noise``; hyp[3] = n_g): row weights
+        # 1 and rho = n_f / n_g in the statistics (csrc/noise_classes.hip), rho fixed here like every other hyper-parameter; solve and
+        # evaluate run unchanged with hyp[2] = n_f and their log-noise term is corrected on the host from the state's counts
+        self._classes = False
 
     # ---- chunking -------------------------------------------------------------------------------
     def row_bytes(self, pd, backward=False):
@@ -706,7 +710,10 @@ class CollapsedAccumulator:
             Kzx = fam.fwd_rect(ctx, self._packZ, self.M, self.p, packX, nb_, pd, self.d, self._hyp, out=self._get("Kzx", Mp * Bp, f32).view(Mp, Bp))
             A64 = self._get("A64", (Mp + 1) * Bp, f64).view(Mp + 1, Bp)
             _ops.trsm(ctx, self._L, Kzx, False, A64[:Mp], None, self._nb, ws, reuse_inverse=True)
-            if self._missing:
+            if self._classes:
+                _ops.collapsed_accumulate_classes_(ctx, self._state, Mp, A64, Bp, pd, y[r0 * q:(r0 + nb_) * q], self._constant, diag,
+                                                   self._hyp)
+            elif self._missing:
                 _ops.collapsed_accumulate_masked_(ctx, self._state, Mp, A64, Bp, pd, y[r0 * q:(r0 + nb_) * q], self._constant, diag)
             else:
                 _ops.collapsed_accumulate_(ctx, self._state, Mp, A64, Bp, y[r0 * q:(r0 + nb_) * q], self._constant, diag)
@@ -741,6 +748,20 @@ class CollapsedAccumulator:
     def _terms(host):
         return dict(zip(_COLLAPSED_TERMS, host))
 
+    def _host_scalars(self, scal, *more):
+        """the one host read of solve / evaluate: the scalars, ``more`` and -- two noise classes -- the value-row count and both noises,
+        with the log-noise correction applied: the entries wrote R log n_f where the rows carry R_f log n_f + R_g log n_g"""
+        if not self._classes:
+            return torch.cat([scal] + list(more)).tolist()
+        host = torch.cat([scal] + list(more) + [self._state[2:3], self._hyp[2:4].to(f64)]).tolist()
+        (values, n_f, n_g), host = host[-3:], host[:-3]
+        R = host[5]
+        if R > 0.0 and n_f > 0.0 and n_g > 0.0:
+            shift = 0.5 * (R - values) * math.log(n_f / n_g)         # (R_g / 2) log rho
+            host[1] += shift
+            host[0] -= shift / R
+        return host
+
     @torch.no_grad()
     def solve(self, num_data=None):
         """``CollapsedResult``: the maximiser of the ELBO over q(u) for ``num_data`` (default R: the plain full-data ELBO).  One host read."""
@@ -748,7 +769,7 @@ class CollapsedAccumulator:
         num_data = self._num_data(num_data)
         ctx = _ops.Context.get(self.device)
         m, LS, nv, nm, scal, info = _ops.collapsed_solve(ctx, self._state, self.Mp, self._hyp, num_data, self._workspace())
-        host = torch.cat([scal, info.to(f64)]).tolist()                    # the one host read
+        host = self._host_scalars(scal, info.to(f64))                      # the one host read
         code = int(host[8])
         if code > 0:
             raise NotPSDError("collapsed solve: I + kappa G is not positive definite at leading minor %d (kappa = %.3e)" % (code, host[6]))
@@ -765,7 +786,7 @@ class CollapsedAccumulator:
         ctx = _ops.Context.get(self.device)
         scal = _ops.collapsed_evaluate(ctx, self._state, self.Mp, variational_mean.contiguous(), chol_variational_covar.contiguous(),
                                        self._hyp, num_data, self._workspace())
-        terms = self._terms(scal.tolist())
+        terms = self._terms(self._host_scalars(scal))
         return CollapsedValue(terms["loss"], terms)
 
     # ---- gradients of the collapsed bound -------------------------------------
@@ -775,6 +796,9 @@ class CollapsedAccumulator:
         hyper-parameters, inducing points and directions.  ``result`` must be what ``solve`` last returned for THESE statistics: by the
         envelope theorem the total derivative equals the partial one at the fixed whitened optimum, which holds at no other q(u).
         Queues alpha = L^-T m, Q = L^-T (S - I) L^-1, K~-bar and the scalar adjoints (dsvgp_collapsed_grad_prepare); no host read."""
+        if self._classes:
+            raise ValueError(_DERIVATIVE_NOISE_REFUSALS[0] % "the collapsed backward pass (begin_backward): d loss / d rho needs a "
+                             "per-class sum in the chunk pass -- a follow-up")
         if not isinstance(result, CollapsedResult):
             raise TypeError("begin_backward takes the CollapsedResult of solve(), got %s" % type(result).__name__)
         solved = self._solved
@@ -919,6 +943,7 @@ _SWITCHES = {
     "capture": lambda e, P, x, fast: e.capture_mode,
     "deterministic": lambda e, P, x, fast: e.deterministic,
     "fast": lambda e, P, x, fast: fast,
+    "missing": lambda e, P, x, fast: e.missing_targets,
 }
 _ARD_REFUSALS = ("%s is not built for ARD lengthscales (a follow-up; the scalar-lengthscale model has it)", (
     ("float64", False, "a float64 engine"), ("ciq", False, "CIQ whitening"), ("natural", False, "the natural parameterisation"),
@@ -931,6 +956,8 @@ _MATERN_REFUSALS = ("%s is not built for the Matern-5/2 kernel (kernel = 'matern
     ("values", False, "the derivative-free strategy"), ("world", False, "a collective with world = %d"),
     ("capture", False, "graph capture (capture_mode)"), ("deterministic", True, "the deterministic mode"),
     ("fast", True, "the Gram fast path (fast=True)")))
+# the parameter whose PRESENCE selects the second likelihood noise (csrc/noise_classes.hip), like ``natural_vec``
+DERIVATIVE_NOISE = "raw_derivative_noise"
 _MISSING_REFUSALS = ("missing_targets is not built for %s (NaN targets are skipped on the piecewise per-output path and "
                      "in the collapsed statistics of a float32, Cholesky-whitened, per-point model on one rank)", (
     ("float64_engine", False, "float64 engines and inputs"), ("ciq", False, "CIQ whitening"), ("natural", False, "natural parameters"),
@@ -939,6 +966,15 @@ _MISSING_REFUSALS = ("missing_targets is not built for %s (NaN targets are skipp
     ("deterministic", True, "the deterministic mode (deterministic)"),
     ("fast", True, "the Gram fast path (fast=True): it needs per-type present counts, zeroed K_ZX columns and a masked "
                    "residual pass -- a follow-up")))
+_DERIVATIVE_NOISE_REFUSALS = ("a separate derivative noise (raw_derivative_noise) is not built for %s (two noise classes run on the "
+                              "piecewise per-output path, in the predictions and in the collapsed statistics of a float32, "
+                              "Cholesky-whitened, per-point model on one rank)", (
+    ("float64_engine", False, "float64 engines and parameters"), ("ciq", False, "CIQ whitening"), ("natural", False, "natural parameters"),
+    ("shared", False, "shared directions (shared_directions)"), ("values", False, "the derivative-free strategy (data_outputs == 'values')"),
+    ("world", False, "a collective with world = %d"),
+    ("missing", False, "missing_targets: one kernel carrying both the mask and the classes is a follow-up"),
+    ("capture", True, "graph capture (capture_mode)"), ("deterministic", True, "the deterministic mode (deterministic)"),
+    ("fast", True, "the Gram fast path (fast=True): it assumes one noise")))
 
 
 class ElboEngine:
@@ -1149,6 +1185,8 @@ class ElboEngine:
             raise ValueError("this entry is not built for ARD lengthscales (raw_lengthscale with %d entries): predict, predict_joint "
                              "and loss_and_grads are" % params["raw_lengthscale"].numel())
         ell, hyp = fam.hyp_forward(ctx, params["raw_lengthscale"], params["raw_outputscale"], params["raw_noise"])
+        if DERIVATIVE_NOISE in params:                  # n_g behind the family's forward (which leaves 0 there); device ops, no read
+            hyp[3:4].copy_(torch.nn.functional.softplus(params[DERIVATIVE_NOISE].reshape(-1)[:1]) + 1e-4)
         if call is not None:
             call.ell = ell
         # common shift of Z and x (gpytorch covar_dist centres on x1.mean): keeps the fp32 quadratic expansion accurate
@@ -1219,6 +1257,14 @@ class ElboEngine:
         for switch, training_only, what in rows:
             if (training or not training_only) and _SWITCHES[switch](self, params, x, fast):
                 raise ValueError(message % (what % self.collective.world if switch == "world" else what))
+
+    def _derivative_noise_refusals(self, params, x, fast=None, training=True):
+        """what a second likelihood noise is not built for, refused on the parameters and switches alone, before any device work"""
+        rdn = params[DERIVATIVE_NOISE]
+        if rdn.dtype != f32 or rdn.numel() != 1:
+            raise ValueError(_DERIVATIVE_NOISE_REFUSALS[0] % ("a raw_derivative_noise of %s with %d entries (float32 [1] is)"
+                                                              % (rdn.dtype, rdn.numel())))
+        self._refuse(_DERIVATIVE_NOISE_REFUSALS, params, x, fast, training)
 
     def _missing_refusals(self, params, x, fast=None, training=True):
         """what ``missing_targets`` is not built for, refused on the parameters and switches alone, before any device work"""
@@ -1487,6 +1533,8 @@ class ElboEngine:
         """q(f) mean / variance plus likelihood noise: what ``likelihood(model(x)).mean/.variance`` returns.
         ``cache=True`` (eval mode) keeps the Cholesky factor and its inverted blocks across calls while the
         parameters are unchanged, like the reference's ``@cached`` ``_cholesky_factor`` (DGVS.py:72)."""
+        if DERIVATIVE_NOISE in params:                  # (value rows carry n_f, derivative rows n_g: ``_predict_chol``)
+            self._derivative_noise_refusals(params, x, training=False)
         if self._is_matern() or self._is_ard(params):
             return self._predict_family(params, x, D, cache, False)
         ctx = _ops.Context.get(self.device)
@@ -1546,6 +1594,8 @@ class ElboEngine:
         MultivariateNormal behind ``likelihood(model(x, derivative_directions=D))`` (reference DGVS.py:199-208), which the
         BO drivers sample jointly (experiments/GNN_bo/gcn_turbo.py:238-239).
         Sigma = s K_XX + 1e-4 I + W^T W - A^T A + noise I: one symmetric kernel assembly and two MFMA Gram products."""
+        if DERIVATIVE_NOISE in params:                  # (value rows carry n_f, derivative rows n_g: ``_predict_chol``)
+            self._derivative_noise_refusals(params, x, training=False)
         if self._is_matern() or self._is_ard(params):
             return self._predict_family(params, x, D, cache, True)
         ctx = _ops.Context.get(self.device)
@@ -1575,6 +1625,8 @@ class ElboEngine:
         point -- the diagonal blocks of ``predict_joint``'s Sigma without K_XX, the two Gram products or anything of size B' x B'
         (csrc/predict_blocks.hip).  Everything up to A = L^-1 K_ZX and W = L_S^T A is ``predict``'s, evaluation cache included, so any
         direction count per data point goes (``D`` None: [B, 1, 1], the variances)."""
+        if DERIVATIVE_NOISE in params:                  # (value rows carry n_f, derivative rows n_g: ``_predict_chol``)
+            self._derivative_noise_refusals(params, x, training=False)
         self._no_matern("predict_blocks (and the block roots built on it)")
         self._no_ard(params, "predict_blocks (and the block roots built on it)")
         ctx = _ops.Context.get(self.device)
@@ -1691,6 +1743,8 @@ class ElboEngine:
         its inverse and the packs are copied out of the engine's buffers.  q(u) itself is not read: the accumulator computes it.  The
         factorisation runs in the engine's factor buffers, so the evaluation cache of ``predict`` is dropped.  With ``missing_targets`` set
         the accumulator skips NaN targets (it keeps the switch it was made with)."""
+        if DERIVATIVE_NOISE in params:
+            self._derivative_noise_refusals(params, None, training=False)
         if self.missing_targets:
             self._missing_refusals(params, None, training=False)
         if self.whitening == "ciq":
@@ -1715,6 +1769,8 @@ class ElboEngine:
                                                                           "one entry per input dimension", d, rl.numel()))
         sub = {k: params[k] for k in ("inducing_points", "inducing_directions", "raw_outputscale", "raw_noise")}
         sub["raw_lengthscale"] = rl.reshape(1, -1).expand(1, d).contiguous() if ard else rl
+        if DERIVATIVE_NOISE in params:
+            sub[DERIVATIVE_NOISE] = params[DERIVATIVE_NOISE]
         ctx = _ops.Context.get(self.device)
         self._eval_cache = None
         fam = MATERN52 if matern else RBF_ARD if ard else RBF
@@ -1733,6 +1789,7 @@ class ElboEngine:
         # the shapes ``loss_and_grads`` returns
         acc._raw = tuple(keep(sub[k]).reshape(-1) for k in ("raw_lengthscale", "raw_outputscale", "raw_noise"))
         acc._shapes = {k: tuple(params[k].shape) for k in COLLAPSED_GRAD_NAMES}
+        acc._classes = DERIVATIVE_NOISE in params
         return acc
 
     @torch.no_grad()
@@ -1925,6 +1982,7 @@ class ElboEngine:
             return self._predict_chol(ctx, expanded, x, D, cache, joint=joint)
 
     def _predict_chol(self, ctx, params, x, D, cache, joint=False, blocks=False):
+        two = DERIVATIVE_NOISE in params                # value rows carry hyp[2], derivative rows hyp[3] (strided device adds)
         # (the parameters arrive expanded; the evaluation cache below is keyed on them alone: calls with different direction
         #  counts on an unchanged model share the factor)
         rect_pd = self._rect_pd(params, x, D)
@@ -1955,7 +2013,10 @@ class ElboEngine:
         packX, _, A32, W, mu, var = self._interp(ctx, params, hyp, packZ, L, dims, x, D, reuse_inverse=hit, rect_pd=rect_pd)
         if blocks:                                                                 # (predict_blocks: no K_XX, nothing B' x B')
             pd = self._pd(dims[2]) if rect_pd is None else rect_pd
-            return mu, _ops.predictive_blocks(ctx, A32, None if self._no_middle else W, pd, packX if pd > 0 else None, dims[1], hyp, True)
+            out = _ops.predictive_blocks(ctx, A32, None if self._no_middle else W, pd, packX if pd > 0 else None, dims[1], hyp, True)
+            if two and pd > 0:
+                out.diagonal(dim1=1, dim2=2)[:, 1:].add_(hyp[3] - hyp[2])
+            return mu, out
         if joint:
             M, d, p, Mp = dims
             B = x.shape[0]
@@ -1968,7 +2029,14 @@ class ElboEngine:
                 _ops.gemm(ctx, TRANS_A, W, W, Sigma, beta=1.0, Cin=Sigma)          # + W^T W
                 _ops.gemm(ctx, TRANS_A, A32, A32, Sigma, alpha=-1.0, beta=1.0, Cin=Sigma)   # - A^T A
             Sigma.diagonal().add_(hyp[2] + 1e-4)                                   # add_jitter(1e-4) + likelihood noise
+            if two and p > 0:
+                Sigma.diagonal().view(B, p + 1)[:, 1:].add_(hyp[3] - hyp[2])
             return mu, Sigma
+        if two:
+            q = var.numel() // max(x.shape[0], 1)
+            noise = hyp[2:3].repeat(q)
+            noise[1:] = hyp[3]
+            return mu, (var.view(-1, q) + noise).reshape(-1).clamp_min_(1e-6)
         varn = (var + hyp[2]).clamp_min_(1e-6)
         return mu, varn
 
@@ -1980,6 +2048,9 @@ class ElboEngine:
         ``fast`` (default ``self.elbo_fast``): in ELBO mode use the Gram-matrix formulation, which does not
         produce per-output variances (``varn`` is then an empty tensor; ``predict`` gives them on demand).
         ``missing_targets`` (attribute): NaN entries of ``y`` are skipped; always the per-output path (``fast=True`` is refused)."""
+        if DERIVATIVE_NOISE in params:                  # two noise classes: always the piecewise per-output path
+            self._derivative_noise_refusals(params, x, fast=fast)
+            fast = False
         if self.missing_targets:
             self._missing_refusals(params, x, fast=fast)
             fast = False
@@ -2476,7 +2547,7 @@ class ElboEngine:
     def _c_step_eligible(self, params, x, use_fast, sync):
         if not (self.c_step and use_fast and not sync and not self.capture_mode and self.whitening == "cholesky"
                 and self.data_outputs == "all" and not self.shared_directions and not self._no_middle and self.potrf_algo == 1
-                and self.fused_inverse and self._trsm_nb is None and not self.lib_dense_gemm):
+                and self.fused_inverse and self._trsm_nb is None and not self.lib_dense_gemm and DERIVATIVE_NOISE not in params):
             return False
         Z, V = params["inducing_points"], params["inducing_directions"]
         M, d = Z.shape
@@ -2508,7 +2579,8 @@ class ElboEngine:
         one rank, Cholesky whitening, every data point with its derivatives, explicit-inverse regime"""
         if not (self.c_step and not sync and not self.capture_mode and self.whitening == "cholesky" and self.data_outputs == "all"
                 and not self.shared_directions and not self._no_middle and self.potrf_algo == 1 and self.fused_inverse
-                and self._trsm_nb is None and not self.lib_dense_gemm and not self.deterministic and not self.missing_targets):
+                and self._trsm_nb is None and not self.lib_dense_gemm and not self.deterministic and not self.missing_targets
+                and DERIVATIVE_NOISE not in params):
             return False
         coll = self.collective
         if coll is not None and coll.world > 1:
@@ -2734,6 +2806,9 @@ class ElboEngine:
         LS = params["chol_variational_covar"]
         dev = self.device
         grads, loss_out, d_hyp = self._alloc_grads(params, PARAM_NAMES)
+        two = DERIVATIVE_NOISE in params
+        if two:                                          # (its own slot: one rank, nothing reduces it)
+            grads[DERIVATIVE_NOISE] = torch.zeros_like(params[DERIVATIVE_NOISE])
         dLS, dm = grads["chol_variational_covar"], grads["variational_mean"]
         scal = torch.empty(8, dtype=f32, device=dev)
         kl_buf = torch.zeros(2 * Mp + 1, dtype=f32, device=dev)      # [KL | per-row KL partials | per-row trace partials]
@@ -2758,7 +2833,11 @@ class ElboEngine:
             mu_bar = torch.empty(Bp, dtype=f32, device=dev)
             var_bar = torch.empty(Bp, dtype=f32, device=dev)
             varn = torch.empty(Bp, dtype=f32, device=dev)
-            if self.missing_targets:
+            if two:
+                # one noise per output class: scal[1] is the value rows' share, scal[5] the derivative rows'.  Nothing downstream changes.
+                _ops.likelihood_terms_classes(ctx, mu, var, y, pd, hyp, 0 if mll_type == "ELBO" else 1, rows, mu_bar, var_bar, varn, scal,
+                                              self._bytes("classes_ws", _lib.lib.dsvgp_likelihood_terms_classes_workspace_bytes()))
+            elif self.missing_targets:
                 # NaN targets do not exist: zeros on their rows, the scalars normalised by the device-side present count -- the epilogue
                 # below then takes rows = 1.  Nothing downstream changes: it sees the zeros.
                 self.present_rows = torch.empty(1, dtype=torch.int32, device=dev)
@@ -2849,6 +2928,8 @@ class ElboEngine:
                            params["raw_outputscale"].reshape(-1), params["raw_noise"].reshape(-1), d_hyp,
                            grads["raw_lengthscale"].reshape(-1), grads["raw_outputscale"].reshape(-1),
                            grads["raw_noise"].reshape(-1), grads["constant"].reshape(-1), loss_out)
+        if two:                                          # softplus chain rule of the second noise, behind the step (device ops)
+            grads[DERIVATIVE_NOISE].reshape(-1).add_(scal[5] * torch.sigmoid(params[DERIVATIVE_NOISE].reshape(-1)))
         loss = loss_out[0]
         return loss, grads, mu, varn
 

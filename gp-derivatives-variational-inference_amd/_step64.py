@@ -369,6 +369,8 @@ class ElboEngine64(ElboEngine):
 
     @torch.no_grad()
     def predict(self, params, x, D, cache=False):
+        if "raw_derivative_noise" in params:
+            self._derivative_noise_refusals(params, x, training=False)     # (a float64 engine: always refused)
         self._refuse_rect(params, x, D)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
@@ -399,6 +401,8 @@ class ElboEngine64(ElboEngine):
     def predict_joint(self, params, x, D, cache=False):
         """Mean [B'] and the full predictive covariance [B', B'] (fp64, likelihood noise on the diagonal):
         Sigma = s K_XX + 1e-4 I + W^T W - A^T A + noise I  (DGVS.py:199-208 + likelihood)"""
+        if "raw_derivative_noise" in params:
+            self._derivative_noise_refusals(params, x, training=False)     # (a float64 engine: always refused)
         self._refuse_rect(params, x, D)
         ctx = _ops.Context.get(self.device)
         if self.whitening == "ciq":
@@ -433,6 +437,8 @@ class ElboEngine64(ElboEngine):
     def loss_and_grads(self, params, x, y, D, num_data, mll_type="ELBO", global_rows=None, include_kl=True, fast=None):
         """(loss, grads dict, mu, varn), all fp64; see ``ElboEngine.loss_and_grads`` for the arguments.  With natural parameters
         (``natural_vec``, ``natural_mat``) the gradients of those two slots are the expectation-parameter gradients NGD steps along."""
+        if "raw_derivative_noise" in params:
+            self._derivative_noise_refusals(params, x, fast=fast)    # (a float64 engine: always refused)
         if self.missing_targets:
             self._missing_refusals(params, x, fast=fast)             # (a float64 engine: always refused)
         self._no_matern("a float64 engine")

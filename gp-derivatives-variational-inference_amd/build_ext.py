@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(HERE, "..", "include")
 LIB = os.path.join(HERE, "libdsvgp_hip.so")
-SOURCES = ["gemm.hip", "gemm64.hip", "gemm32.hip", "gemm3b.hip", "assemble.hip", "assemble_wide.hip", "assemble_ard.hip", "assemble_matern.hip", "assemble64.hip", "assemble64_tiled.hip", "det64.hip", "elbo.hip", "potrf.hip", "ciq.hip", "step.hip", "step64.hip", "predict_mean.hip", "predict_variance.hip", "predict_blocks.hip", "block_roots.hip", "paths.hip", "kmeans.hip", "collapsed.hip", "missing.hip", "api.hip"]
+SOURCES = ["gemm.hip", "gemm64.hip", "gemm32.hip", "gemm3b.hip", "assemble.hip", "assemble_wide.hip", "assemble_ard.hip", "assemble_matern.hip", "assemble64.hip", "assemble64_tiled.hip", "det64.hip", "elbo.hip", "potrf.hip", "ciq.hip", "step.hip", "step64.hip", "predict_mean.hip", "predict_variance.hip", "predict_blocks.hip", "block_roots.hip", "paths.hip", "kmeans.hip", "collapsed.hip", "missing.hip", "noise_classes.hip", "api.hip"]
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-result"]
 

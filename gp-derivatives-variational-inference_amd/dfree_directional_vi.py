@@ -49,6 +49,8 @@ def train_gp(train_dataset, num_inducing=128,
              **args):
     """Train a derivative GP on function values only (argument meaning identical to the reference,
     dfree_directional_vi.py:66-123; ``seed`` / ``max_steps`` as in ``directional_vi.train_gp``)."""
+    if args.get("derivative_noise"):
+        raise ValueError("derivative_noise is built for the per-point DSVGP harness (directional_vi.train_gp), not for the derivative-free harness: its data carry no derivative rows")
     assert num_directions == minibatch_dim
     if use_ciq:
         raise NotImplementedError("derivative-free data with the CIQ strategy: the reference pairs B (p + 1) CIQ outputs with B "

@@ -104,15 +104,18 @@ class GPModel(ApproximateGP):
              else [vd.variational_mean, vd.chol_variational_covar])
         return [vs.inducing_points, vs.inducing_directions] + q + [
             self.mean_module.constant, self.covar_module.raw_outputscale,
-            self.covar_module.base_kernel.raw_lengthscale, raw_noise]
+            self.covar_module.base_kernel.raw_lengthscale, raw_noise] + (
+                [likelihood.noise_covar.raw_derivative_noise] if getattr(likelihood, "has_derivative_noise", False) else [])
 
-    def _param_names(self):
-        from ._step import NGD_PARAM_NAMES, PARAM_NAMES
+    def _param_names(self, likelihood=None):
+        from ._step import DERIVATIVE_NOISE, NGD_PARAM_NAMES, PARAM_NAMES
         ngd = isinstance(self.variational_strategy._variational_distribution, NaturalVariationalDistribution)
-        return NGD_PARAM_NAMES if ngd else PARAM_NAMES
+        names = NGD_PARAM_NAMES if ngd else PARAM_NAMES
+        # (a likelihood with a second noise: its parameter rides behind the fixed names -- the engine's switch is its presence)
+        return names + (DERIVATIVE_NOISE,) if getattr(likelihood, "has_derivative_noise", False) else names
 
     def _param_dict(self, likelihood=None):
-        return {k: _ops.detach_keep(v) for k, v in zip(self._param_names(), self._param_list(likelihood))}
+        return {k: _ops.detach_keep(v) for k, v in zip(self._param_names(likelihood), self._param_list(likelihood))}
 
 
 def select_cols_of_y(y_batch, minibatch_dim, dim):
@@ -505,6 +508,14 @@ class TrainLoop:
         _enable_missing_targets(self)
         return self
 
+    def set_derivative_noise(self):
+        """The likelihood gets a second noise from here on (``GaussianLikelihood.add_derivative_noise``: ``raw_derivative_noise``, started
+        at the value noise), registered with the hyper-parameter optimiser: function values are observed under ``likelihood.noise``,
+        derivatives under ``likelihood.derivative_noise`` (the engine's two-class per-output step, predictions and collapsed statistics).
+        Cholesky-whitened per-point model, float32, one rank, no missing targets, no graph replay -- anything else is refused."""
+        _enable_derivative_noise(self)
+        return self
+
     def finish(self):
         """drain the replay pipeline (the status of the last replayed / deferred step is checked here)"""
         self._graph_check_previous()
@@ -724,10 +735,19 @@ def train_gp(train_dataset, num_inducing=128,
       ``ard_num_dims`` (int, the input dimension): one lengthscale per input dimension (``setup_training``);
       ``kernel`` ("rbf" or "matern52"): the covariance family (``setup_training``);
       ``variational_initialization`` (None or "optimal"): start q(u) at its closed-form optimum (``setup_training``);
-      ``missing_targets`` (bool): NaN entries of the targets are observations that do not exist (``TrainLoop.set_missing_targets``).
+      ``missing_targets`` (bool): NaN entries of the targets are observations that do not exist (``TrainLoop.set_missing_targets``);
+      ``derivative_noise`` (bool): one likelihood noise for the function values and one for the derivatives
+      (``TrainLoop.set_derivative_noise``);
+      ``loss_history`` (list): every step's loss is appended to it as a device scalar (no host read here).
     """
     assert num_directions == minibatch_dim
     missing = bool(args.get("missing_targets", False))
+    two_noises = bool(args.get("derivative_noise", False))
+    if two_noises and (missing or args.get("_shared") or args.get("_model_class") is not None):
+        raise ValueError("derivative_noise is built for the per-point DSVGP harness (directional_vi.train_gp) without missing_targets, "
+                         "not for the shared-directions harness or another model class")
+    if two_noises and args.get("variational_initialization") not in (None, "optimal"):
+        raise ValueError("variational_initialization must be None or 'optimal', got %r" % (args.get("variational_initialization"),))
     if missing and args.get("variational_initialization") not in (None, "optimal"):
         raise ValueError("variational_initialization must be None or 'optimal', got %r" % (args.get("variational_initialization"),))
     loop = setup_training(train_dataset, num_inducing, num_directions, minibatch_size, minibatch_dim, num_epochs,
@@ -737,7 +757,11 @@ def train_gp(train_dataset, num_inducing=128,
                           num_contour_quadrature=num_contour_quadrature, model_class=args.get("_model_class"),
                           shared=bool(args.get("_shared")), data_directions=data_directions, kernel=args.get("kernel", "rbf"),
                           ard_num_dims=args.get("ard_num_dims"),
-                          variational_initialization=None if missing else args.get("variational_initialization"))
+                          variational_initialization=None if missing or two_noises else args.get("variational_initialization"))
+    if two_noises:                                           # (before the optimal start: it fits under both noises)
+        loop.set_derivative_noise()
+        if args.get("variational_initialization") == "optimal":
+            loop.refit_variational(data_directions=data_directions, seed=args.get("seed"))
     if missing:                                              # (before any pass over the targets: the optimal start included)
         loop.set_missing_targets()
         if args.get("variational_initialization") == "optimal":
@@ -745,6 +769,7 @@ def train_gp(train_dataset, num_inducing=128,
     n_samples = loop.X.shape[0]
     stride = (num_directions if loop.data_directions is None else loop.data_directions) + 1      # outputs per minibatch point
     max_steps = args.get("max_steps")
+    history = args.get("loss_history")
     total_step = 0
     loss = None
     for i in range(num_epochs):
@@ -752,6 +777,8 @@ def train_gp(train_dataset, num_inducing=128,
         for start in range(0, n_samples, minibatch_size):
             report = (total_step % 50 == 0) and verbose
             loss, output, y_batch = loop.step(perm[start:start + minibatch_size], need_variance="values" if report else False)
+            if history is not None:
+                history.append(loss.detach().clone())
             if report:
                 means = output.mean[::stride]
                 stds = output.value_variance.sqrt()          # = output.variance.sqrt()[::num_directions + 1]
@@ -795,6 +822,38 @@ def _enable_missing_targets(loop):
         return                                               # (already on: num_data was scaled then)
     model.missing_targets = True
     loop.mll.num_data = _present_num_data(loop.mll.num_data, loop.Y)
+
+
+def _enable_derivative_noise(loop):
+    """``TrainLoop.set_derivative_noise``: the refusals on the loop's switches alone, then the parameter and its optimiser group"""
+    model, likelihood = loop.model, loop.likelihood
+    no = lambda what: ValueError("derivative noise is built for the Cholesky-whitened per-point DSVGP model in float32 on one rank, "
+                                 "not for %s" % what)
+    if not isinstance(model, GPModel) or loop.dfree or getattr(loop, "plain", False) or loop.full_gradient:
+        raise no("the dfree / shared / full-gradient / plain harnesses")
+    eng = model.engine
+    if eng.whitening != "cholesky" or eng.shared_directions or eng.data_outputs != "all":
+        raise no("CIQ whitening, shared directions or derivative-free data")
+    if isinstance(model.variational_strategy._variational_distribution, NaturalVariationalDistribution):
+        raise no("natural parameters (NGD)")
+    if loop.dp is not None:
+        raise no("a collective with world > 1")
+    if loop.X.dtype != torch.float32:
+        raise no("a float64 dataset")
+    if getattr(model, "missing_targets", False):
+        raise no("missing_targets (one kernel carrying both is a follow-up)")
+    if getattr(eng, "deterministic", False):
+        raise no("the deterministic mode")
+    if loop.graph is True or (loop.graph is None and os.environ.get("DSVGP_GRAPH") == "1"):
+        raise no("graph replay of the step (capture_mode)")
+    if not isinstance(likelihood, GaussianLikelihood):
+        raise no("a likelihood other than GaussianLikelihood")
+    if likelihood.has_derivative_noise:
+        return                                               # (already there, e.g. built with derivative_noise=True)
+    raw = likelihood.add_derivative_noise()
+    # into the likelihood's own group (the last one) of the hyper-parameter optimiser: the schedulers were built on the groups as they
+    # are, so the new parameter follows the learning rate of ``raw_noise``; its moments start with its first step
+    loop.hyperparameter_optimizer.param_groups[-1]["params"].append(raw)
 
 
 def _present_num_data(num_data, Y):
@@ -900,6 +959,9 @@ def collapsed_loss_and_grads(model, likelihood, dataset_or_tensors, minibatch_si
     likelihood's hyper-parameters, the inducing points and the directions (those that require a gradient; added onto an existing
     ``.grad``); the variational tensors get none -- with ``write_variational`` they are set to the optimum itself.  Returns the result
     object of the solve (``loss``: the collapsed loss these gradients belong to)."""
+    if getattr(likelihood, "has_derivative_noise", False):
+        raise ValueError("derivative noise: the collapsed backward pass (collapsed_loss_and_grads, train_collapsed) is not built for two "
+                         "noise classes -- d loss / d rho needs a per-class sum in the chunk pass (a follow-up); fit_variational is")
     acc, X, Y, pd = _collapsed_setup(model, likelihood, dataset_or_tensors, data_directions, workspace_budget, "collapsed_loss_and_grads")
     n_samples, dim = X.shape
     columns = _collapsed_columns(n_samples, dim, pd, minibatch_size, seed)

@@ -48,24 +48,63 @@ class ScaleKernel(torch.nn.Module):
 
 
 class _NoiseCovar(torch.nn.Module):
-    def __init__(self):
+    def __init__(self, derivative_noise=False):
         super().__init__()
         self.register_parameter("raw_noise", torch.nn.Parameter(torch.zeros(1)))
+        if derivative_noise:
+            self.register_parameter("raw_derivative_noise", torch.nn.Parameter(torch.zeros(1)))
 
 
 class GaussianLikelihood(torch.nn.Module):
-    """gpytorch.likelihoods.GaussianLikelihood: ``noise_covar.raw_noise`` [1], noise = softplus + 1e-4."""
+    """gpytorch.likelihoods.GaussianLikelihood: ``noise_covar.raw_noise`` [1], noise = softplus + 1e-4.
+    ``derivative_noise=True`` (not in gpytorch's class; its derivative-GP examples use one noise per output of [f, grad f]): a second
+    parameter ``noise_covar.raw_derivative_noise`` [1] under the same constraint -- the function-value rows are then observed under
+    ``noise``, the directional-derivative rows under ``derivative_noise`` (csrc/noise_classes.hip).  The default's state_dict is as before."""
 
-    def __init__(self):
+    def __init__(self, derivative_noise=False):
         super().__init__()
-        self.noise_covar = _NoiseCovar()
+        self.noise_covar = _NoiseCovar(bool(derivative_noise))
+
+    @property
+    def has_derivative_noise(self):
+        return "raw_derivative_noise" in self.noise_covar._parameters
+
+    def add_derivative_noise(self):
+        """register ``noise_covar.raw_derivative_noise`` at the current value of ``raw_noise`` (nothing if it is there); returns it"""
+        if not self.has_derivative_noise:
+            raw = self.noise_covar.raw_noise
+            self.noise_covar.register_parameter("raw_derivative_noise", torch.nn.Parameter(raw.detach().clone()))
+        return self.noise_covar.raw_derivative_noise
 
     @property
     def noise(self):
         return torch.nn.functional.softplus(self.noise_covar.raw_noise) + 1e-4
 
+    @property
+    def derivative_noise(self):
+        if not self.has_derivative_noise:
+            raise AttributeError("this likelihood has one noise: GaussianLikelihood(derivative_noise=True) has a second")
+        return torch.nn.functional.softplus(self.noise_covar.raw_derivative_noise) + 1e-4
+
     def forward(self, dist):
         return dist.with_likelihood(self)
+
+
+def _param_names(model, likelihood):
+    """the model's parameter names; a likelihood with a derivative noise is handed over (``GPModel`` appends its name)"""
+    return model._param_names(likelihood) if getattr(likelihood, "has_derivative_noise", False) else model._param_names()
+
+
+def _noise_rows(params, q):
+    """the likelihood noise of the q = pd + 1 rows of a point as the engine added it: [q] with the derivative noise on rows 1.., or a
+    0-dim tensor for a single noise (a model's ``_param_dict(None)`` carries the stand-in noise alone)"""
+    soft = torch.nn.functional.softplus
+    n_f = soft(params["raw_noise"].reshape(())) + 1e-4
+    if "raw_derivative_noise" not in params:
+        return n_f
+    out = n_f.reshape(1).repeat(q)
+    out[1:] = soft(params["raw_derivative_noise"].reshape(())) + 1e-4
+    return out
 
 
 class _VariationalDistribution(torch.nn.Module):
@@ -160,7 +199,11 @@ class PredictiveDistribution:
             mu, varn = self.model.engine.predict(params, self.x, self.D, cache=not self.model.training)
             self._mu, self._varn = mu, varn
             if lik is None:   # q(f) itself: remove the noise again
-                self._var = (varn - torch.nn.functional.softplus(params["raw_noise"].reshape(())) - 1e-4)
+                if "raw_derivative_noise" in params:
+                    q = varn.numel() // max(self.x.shape[0], 1)
+                    self._var = (varn.view(-1, q) - _noise_rows(params, q)).reshape(-1)
+                else:
+                    self._var = (varn - torch.nn.functional.softplus(params["raw_noise"].reshape(())) - 1e-4)
 
     @property
     def mean(self):
@@ -201,7 +244,11 @@ class PredictiveDistribution:
             params = self.model._param_dict(lik)
             mu, Sigma = self.model.engine.predict_joint(params, self.x, self.D, cache=not self.model.training)
             if lik is None:   # q(f) itself: remove the noise again
-                Sigma.diagonal().sub_(torch.nn.functional.softplus(params["raw_noise"].reshape(())) + 1e-4)
+                if "raw_derivative_noise" in params:
+                    q = Sigma.shape[0] // max(self.x.shape[0], 1)
+                    Sigma.diagonal().view(-1, q).sub_(_noise_rows(params, q))
+                else:
+                    Sigma.diagonal().sub_(torch.nn.functional.softplus(params["raw_noise"].reshape(())) + 1e-4)
             self._mu, self._Sigma, self._root = mu, Sigma, None
 
     @property
@@ -219,7 +266,7 @@ class PredictiveDistribution:
             params = self.model._param_dict(lik)
             mu, blocks = self.model.engine.predict_blocks(params, self.x, self.D, cache=not self.model.training)
             if lik is None:   # q(f) itself: remove the noise again
-                blocks.diagonal(dim1=1, dim2=2).sub_(torch.nn.functional.softplus(params["raw_noise"].reshape(())) + 1e-4)
+                blocks.diagonal(dim1=1, dim2=2).sub_(_noise_rows(params, blocks.shape[-1]))
             self._mu, self._blocks = mu, blocks
         return self._blocks
 
@@ -309,7 +356,7 @@ class _ApproximateMLL(torch.nn.Module):
         plist = model._param_list(self.likelihood)
         dp = getattr(model, "data_parallel", None)
         elbo, mu, varn = _ElboFunction.apply(model.engine, output.x, target, output.D, float(self.num_data),
-                                             self.mll_type, dp, model._param_names(), *plist)
+                                             self.mll_type, dp, _param_names(model, self.likelihood), *plist)
         # the ELBO fast path does not form per-output variances; they are produced on demand
         output._mu, output._varn = mu, (varn if varn.numel() else None)
         return elbo
@@ -325,7 +372,7 @@ class _ApproximateMLL(torch.nn.Module):
             raise TypeError("mll expects likelihood(model(x, derivative_directions=D)) as in directional_vi.py:245")
         model = output.model
         plist = model._param_list(self.likelihood)
-        names = model._param_names()
+        names = _param_names(model, self.likelihood)
         pd = dict(zip(names, [_ops.detach_keep(p) for p in plist]))
         dp = getattr(model, "data_parallel", None)
         if dp is not None:

@@ -169,6 +169,8 @@ def train_gp(train_dataset, dim, num_inducing=128,
              watch_model=False, gamma=0.1,
              verbose=True,
              **args):
+    if args.get("derivative_noise"):
+        raise ValueError("derivative_noise is built for the per-point DSVGP harness (directional_vi.train_gp), not for the full-gradient SVGP harness (one noise per canonical direction is a follow-up)")
     loop = setup_training(train_dataset, dim, num_inducing, minibatch_size, num_epochs, use_ngd, use_ciq,
                           learning_rate_hypers, learning_rate_ngd, lr_sched, mll_type, gamma,
                           num_contour_quadrature=num_contour_quadrature, **args)

@@ -65,6 +65,8 @@ def train_gp(train_dataset, num_inducing=128,
     if use_ciq:
         raise NotImplementedError("shared directions with the CIQ strategy: the reference's combination is shape-"
                                   "inconsistent (see the module docstring) and is not built")
+    if args.get("derivative_noise"):
+        raise ValueError("derivative_noise is built for the per-point DSVGP harness (directional_vi.train_gp), not for the shared-directions harness")
     return _dvi.train_gp(train_dataset, num_inducing, num_directions, minibatch_size, minibatch_dim, num_epochs,
                          learning_rate_hypers, learning_rate_ngd, inducing_data_initialization, use_ngd, False, lr_sched,
                          mll_type, num_contour_quadrature, watch_model, gamma, verbose, fixed_inducing_locations,

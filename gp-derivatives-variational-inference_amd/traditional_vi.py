@@ -92,6 +92,8 @@ def train_gp(train_dataset, dim, num_inducing=128,
              verbose=True,
              **args):
     """Argument meaning identical to the reference (traditional_vi.py:39-52); ``seed`` / ``max_steps`` via ``**args``."""
+    if args.get("derivative_noise"):
+        raise ValueError("derivative_noise is built for the per-point DSVGP harness (directional_vi.train_gp), not for the plain SVGP harness: its data carry no derivative rows")
     if not torch.cuda.is_available():
         raise RuntimeError("train_gp needs an MI355X (HIP) device: this path has no CPU fallback")
     device = torch.device("cuda", torch.cuda.current_device())

@@ -1108,6 +1108,30 @@ int dsvgp_collapsed_grad_chunk_masked(dsvgp_ctx* ctx, int Mp, int Bp, float* Kzx
                                       const double* Q, int64_t ldq, const double* alpha, const double* adj, float* K_bar, int64_t ldkb,
                                       float* diag_bar, double* rho_sum, void* workspace);
 
+/* ---- two likelihood noises (csrc/noise_classes.hip): the function-value rows of an interleaved batch
+ * (j % (p + 1) == 0) are observed under n_f = hyp[2], the derivative rows under n_g = hyp[3] (the caller writes hyp[3] behind
+ * dsvgp_hyp_forward / _ard, which leave 0 there).  The class is read from the row index.  Fixed-order sums (per-workgroup partials joined
+ * in workgroup order), no floating-point atomics, no host read, no allocation: two identical calls give bitwise equal results.
+ *   dsvgp_likelihood_terms_classes      dsvgp_likelihood_terms with the row's class noise in every per-row formula (ELBO and PLL, the
+ *                                       clamp at 1e-6 included).  out_scalars[0], [2..4] as there; out_scalars[1] = d loss / d n_f from the
+ *                                       value rows only, out_scalars[5] = d loss / d n_g from the derivative rows only (exactly 0 at p = 0),
+ *                                       out_scalars[6..7] = 0.  workspace: dsvgp_likelihood_terms_classes_workspace_bytes() bytes, 16-byte
+ *                                       aligned.  ncols = 0: out_scalars is cleared, no launch.
+ *   dsvgp_collapsed_accumulate_classes  dsvgp_collapsed_accumulate with row weights omega = 1 on value rows and rho = hyp[2] / hyp[3] on
+ *                                       derivative rows: the derivative columns of A64 (rows < Mp) and of the residual row are scaled by
+ *                                       sqrt(rho) (float64) IN PLACE before the unchanged fp64 MFMA product; [0] += sum omega prior_diag +
+ *                                       1e-4 sum (omega - 1), [1] += Bp, the reserved word [2] += the number of value rows.  Bp must be a
+ *                                       multiple of pd + 1.  dsvgp_collapsed_solve / _evaluate run unchanged on this state with hyp[2] = n_f;
+ *                                       their sum ll lacks (R_g / 2) log rho, R_g = [1] - [2], which the caller adds.
+ * DSVGP_EINVAL: a null pointer, a negative size, global_rows <= 0, mll_type outside {0, 1}, Bp not a multiple of pd + 1, whatever the
+ * single-noise sibling refuses; DSVGP_EALIGN: a misaligned pointer.  Size 0 returns 0 without a launch where the sibling does.         */
+size_t dsvgp_likelihood_terms_classes_workspace_bytes(void);
+int dsvgp_likelihood_terms_classes(dsvgp_ctx* ctx, const float* mu, const float* var, const float* y, int ncols, int p, const float* hyp,
+                                   int mll_type, double global_rows, float* mu_bar, float* var_bar, float* varn_out, float* out_scalars,
+                                   void* workspace);
+int dsvgp_collapsed_accumulate_classes(dsvgp_ctx* ctx, void* state, int Mp, double* A64, int64_t lda, int Bp, int pd, const float* y,
+                                       const float* constant, const float* prior_diag, const float* hyp);
+
 /* ---- measurement aid (bench.py `roofline.sustained`): the MFMA rate this card holds with no memory traffic, ~`millis` ms of
  * v_mfma_f64_16x16x4_f64 (is_double = 1) or v_mfma_f32_32x32x2_f32 (0) on every CU; synchronises the stream.
  * scratch: 2 MiB of device memory.  Not part of the reference's interface (SURVEY.md 8d asks for achieved-vs-peak; the
