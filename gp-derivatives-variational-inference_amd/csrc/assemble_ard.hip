@@ -3,11 +3,13 @@
 // Formulation.  The packed rows of assemble.hip carry the per-dimension scaling themselves,
 //     x~ = (x - c) ./ ell        v~_a = (v_a / |v_a|) ./ ell        (elementwise)
 // and the ARD kernel's micro-blocks are  k [[1, w~_b], [-u~_a, v~_a . v~_b - u~_a w~_b]]  with r = x~1 - x~2, u~_a = r . v~1_a,
-// w~_b = r . v~2_b, k = s exp(-|r|^2 / 2): the transform of kernel_fwd_tiled_kernel / kernel_bwd_tbar_kernel (assemble_wide.hip) run with
-// hyp[0] = 1 on these rows.  Those kernels see directions through T = P1 P2^T and the self terms alone and nothing in them assumes
+// w~_b = r . v~2_b, k = s exp(-|r|^2 / 2): the transform of kernel_fwd_tiled_kernel / kernel_bwd_tbar_kernel (tiled_assembly.h) with
+// RbfRadial (assemble_wide.hip) run with hyp[0] = 1 on these rows.  Those kernels see directions through T = P1 P2^T and the self terms alone and nothing in them assumes
 // |v| = 1, so the forward (dsvgp_kernel_fwd_wide / dsvgp_kernel_fwd_rect) and the Tbar and contraction launches of the backward are
 // theirs, unchanged.  New here: the hyper-parameter chain of an ell vector, the pack, the prior diagonal and its backward, and the
-// points reduction of the backward with the per-dimension lengthscale gradient of BOTH sides.
+// points reduction of the backward with the per-dimension lengthscale gradient of BOTH sides.  The backward's body serves every family
+// on these packs: kernel_bwd_ard_family takes the family's Tbar launcher (everything after the Tbar tiles sees the kernel through Tbar
+// alone).  The prior diagonal's two kernels are the family-templated ones of tiled_assembly.h.
 //
 // Lengthscale gradient.  Every packed entry scales as 1 / ell_k, so d_ell[k] = -(1 / ell_k) sum over the rows of both sides of
 // P[r, k] Pbar[r, k], Pbar the total gradient of the row.  With dP = Tbar [P2 | indicator] (the summed slabs),
@@ -19,12 +21,11 @@
 // (same pack, symmetric G) side 2's self part equals side 1's and no column sums are formed.
 // No floating-point atomics: every sum has a fixed order, two identical calls are bitwise equal.
 #include "common.h"
-
-#include <climits>
+#include "tiled_assembly.h"
 
 namespace {
 
-constexpr int ANT = 256;                // threads per workgroup
+constexpr int ANT = WNT;                // threads per workgroup (256: block_sum64 of tiled_assembly.h)
 constexpr int AQMAX = 96;               // p + 1 <= 96
 constexpr float NOISE_FLOOR = 1e-4f;    // GaussianLikelihood noise constraint GreaterThan(1e-4) (elbo.hip)
 
@@ -97,60 +98,6 @@ __global__ __launch_bounds__(ANT) void pack_points_ard_kernel(const float* __res
             self[row] = acc;
             vnorm[i * p + (a - 1)] = nrm;
         }
-    }
-}
-
-// ---- prior diagonal: out[i q] = s, out[i q + a] = s |v~_ia|^2 ------------------------------------------------
-// one wave per packed row; the lanes' strided partial sums meet in a fixed shuffle tree
-__global__ __launch_bounds__(ANT) void kernel_diag_ard_kernel(const float* __restrict__ P, int64_t nq, int q, int K4, int DP,
-                                                              const float* __restrict__ hyp, float* __restrict__ out) {
-    const int64_t row = (int64_t)blockIdx.x * (ANT / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (row >= nq) return;
-    const float s = hyp[1];
-    if (row % q == 0) {
-        if (lane == 0) out[row] = s;
-        return;
-    }
-    const float* Pr = P + row * DP;
-    float acc = 0.f;
-    for (int k = lane; k < K4; k += 64) acc = __builtin_fmaf(Pr[k], Pr[k], acc);      // (columns d..K4-1 hold zeros)
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if (lane == 0) out[row] = s * acc;
-}
-
-// fixed-order sum of 256 doubles held one per thread; the total is valid on thread 0
-__device__ __forceinline__ double block_sum64(double v, double* part) {
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (int off = ANT / 2; off > 0; off >>= 1) {
-        if (threadIdx.x < off) part[threadIdx.x] += part[threadIdx.x + off];
-        __syncthreads();
-    }
-    return part[0];
-}
-
-// backward of the diagonal.  Block k < d: d_ell[k] += -(2 s / ell_k) sum_{i, a >= 1} gbar_ia v~_iak^2; block d: d_hyp[1] += sum gbar out / s.
-// One block per output, the rows dealt to the threads in a fixed stride, fp64 partial sums, a fixed tree (column_mean_kernel's shape).
-__global__ __launch_bounds__(ANT) void kernel_diag_ard_bwd_kernel(const float* __restrict__ P, int64_t nq, int q, int d, int DP,
-                                                                  const float* __restrict__ ell, const float* __restrict__ hyp,
-                                                                  const float* __restrict__ out, const float* __restrict__ gbar,
-                                                                  float* __restrict__ d_ell, float* __restrict__ d_hyp) {
-    __shared__ double part[ANT];
-    const int k = blockIdx.x;
-    double acc = 0.0;
-    if (k < d) {
-        for (int64_t r = threadIdx.x; r < nq; r += ANT) {
-            if (r % q == 0) continue;
-            const float pv = P[r * DP + k];
-            acc += (double)gbar[r] * (double)(pv * pv);
-        }
-        const double tot = block_sum64(acc, part);
-        if (threadIdx.x == 0) d_ell[k] += (float)(-2.0 * (double)hyp[1] / (double)ell[k] * tot);
-    } else {
-        for (int64_t r = threadIdx.x; r < nq; r += ANT) acc += (double)gbar[r] * (double)out[r];
-        const double tot = block_sum64(acc, part);
-        if (threadIdx.x == 0) d_hyp[1] += (float)(tot / (double)hyp[1]);
     }
 }
 
@@ -278,10 +225,10 @@ __global__ __launch_bounds__(ANT) void ard_reduce_kernel(const float* __restrict
 }
 
 // workspace: [ the rectangular backward's (slab | partials | TB) | pad to 16 bytes | cs[n2q] | E[(n1 + n2), d] ], floats
-struct ArdBwdPlan { size_t rect_bytes, cs_off, e_off, bytes; int ns; };
+struct ArdBwdPlan { TilePlan t; size_t cs_off, e_off, bytes; };
 inline int ard_bwd_plan(int n1, int p1, int n2, int p2, int d, ArdBwdPlan& a) {
-    if (int rc = kernel_bwd_rect_tiles_plan(n1, p1, n2, p2, d, &a.rect_bytes, &a.ns)) return rc;
-    a.cs_off = (a.rect_bytes + 15) & ~(size_t)15;
+    if (int rc = rect_tile_plan(n1, p1, n2, p2, d, true, a.t)) return rc;
+    a.cs_off = (a.t.bytes + 15) & ~(size_t)15;
     a.e_off = a.cs_off + sizeof(float) * (((size_t)n2 * (p2 + 1) + 3) & ~(size_t)3);
     a.bytes = a.e_off + sizeof(float) * ((size_t)n1 + (size_t)n2) * (size_t)d;
     return 0;
@@ -319,26 +266,12 @@ extern "C" int dsvgp_pack_points_ard(dsvgp_ctx* ctx, const float* x, const float
 }
 
 extern "C" int dsvgp_kernel_diag_ard(dsvgp_ctx* ctx, const float* P, int n, int p, int d, const float* hyp, float* out) {
-    if (!ctx || !P || !hyp || !out || n < 0 || d < 1 || p < 0 || p + 1 > AQMAX) return DSVGP_EINVAL;
-    if (n == 0) return 0;
-    const int64_t rows = (int64_t)n * (p + 1);
-    if (rows > INT_MAX || d > INT_MAX - 64) return DSVGP_EINVAL;
-    const int DP = dsvgp_packed_width(d);
-    hipLaunchKernelGGL(kernel_diag_ard_kernel, dim3(cdiv(rows, ANT / 64)), dim3(ANT), 0, ctx->stream, P, rows, p + 1, DP - 4, DP, hyp, out);
-    DSVGP_LAUNCH_CHECK();
-    return 0;
+    return kernel_diag_rbf(ctx, P, n, p, d, hyp, out);
 }
 
 extern "C" int dsvgp_kernel_diag_ard_bwd(dsvgp_ctx* ctx, const float* P, int n, int p, int d, const float* ell, const float* hyp,
                                          const float* out, const float* gbar, float* d_ell, float* d_hyp) {
-    if (!ctx || !P || !ell || !hyp || !out || !gbar || !d_ell || !d_hyp || n < 0 || d < 1 || p < 0 || p + 1 > AQMAX) return DSVGP_EINVAL;
-    if (n == 0) return 0;
-    const int64_t rows = (int64_t)n * (p + 1);
-    if (rows > INT_MAX || d > INT_MAX - 64) return DSVGP_EINVAL;
-    hipLaunchKernelGGL(kernel_diag_ard_bwd_kernel, dim3(d + 1), dim3(ANT), 0, ctx->stream, P, rows, p + 1, d, dsvgp_packed_width(d), ell, hyp,
-                       out, gbar, d_ell, d_hyp);
-    DSVGP_LAUNCH_CHECK();
-    return 0;
+    return kernel_diag_bwd_rbf(ctx, P, n, p, d, ell, hyp, out, gbar, d_ell, d_hyp);
 }
 
 extern "C" size_t dsvgp_kernel_bwd_ard_workspace_bytes(int n1, int p1, int n2, int p2, int d) {
@@ -348,12 +281,12 @@ extern "C" size_t dsvgp_kernel_bwd_ard_workspace_bytes(int n1, int p1, int n2, i
 
 extern "C" int dsvgp_kernel_bwd_ard_slabs(int n1, int p1, int n2, int p2, int d) {
     ArdBwdPlan a;
-    return ard_bwd_plan(n1, p1, n2, p2, d, a) ? 0 : a.ns;
+    return ard_bwd_plan(n1, p1, n2, p2, d, a) ? 0 : a.t.ns;
 }
 
-int kernel_bwd_ard_family(dsvgp_ctx* ctx, int family, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
-                          const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
-                          const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell, float* d_hyp,
+int kernel_bwd_ard_family(dsvgp_ctx* ctx, TbarLauncher tbar, const void* G, int64_t ldg, int g_is_double, const float* P1,
+                          const float* self1, const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2,
+                          int d, const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell, float* d_hyp,
                           void* workspace) {
     if (!ctx || !G || !P1 || !self1 || !P2 || !self2 || !ell || !hyp || !d_x1 || !d_hyp || !workspace) return DSVGP_EINVAL;
     if (d_v1 && !vnorm1) return DSVGP_EINVAL;
@@ -364,15 +297,13 @@ int kernel_bwd_ard_family(dsvgp_ctx* ctx, int family, const void* G, int64_t ldg
     if (int rc = ard_bwd_plan(n1, p1, n2, p2, d, a)) return rc;
     if (((uintptr_t)P1 | (uintptr_t)P2) % 16) return DSVGP_EINVAL;         // the packed rows are read 16 bytes at a time
     if ((uintptr_t)workspace % 4 || (uintptr_t)G % (g_is_double ? 8 : 4)) return DSVGP_EINVAL;
-    const int q1 = p1 + 1, q2 = p2 + 1, n2q = n2 * q2;
-    const int DP = dsvgp_packed_width(d), K4 = DP - 4, NP = (DP + 15) & ~15;
+    const TilePlan& t = a.t;
+    if (ldg < t.n2q) return DSVGP_EINVAL;
+    const int q1 = t.q1, q2 = t.q2, n2q = t.n2q, DP = t.DP, K4 = t.K4, NP = t.NP, ns = t.ns, nparts = t.nparts;
     float *slab, *partials, *TB;
-    int ns, nparts;
-    // launches 1 and 2 of dsvgp_kernel_bwd_rect (or the Matern family's Tbar tiles in place of launch 1); the scalar lengthscale partial
-    // (partials[2 j + 1]) is not read
-    if (int rc = (family ? launch_kernel_bwd_matern52_tiles : launch_kernel_bwd_rect_tiles)(ctx->stream, G, ldg, g_is_double, P1, self1, n1, p1,
-                                                                                            P2, self2, n2, p2, d, hyp, workspace, &slab, &ns,
-                                                                                            &partials, &nparts, &TB))
+    // launches 1 and 2 of dsvgp_kernel_bwd_rect with the family's Tbar tiles; the scalar lengthscale partial (partials[2 j + 1]) is not read
+    if (int rc = launch_kernel_bwd_tiles(ctx->stream, tbar, t, G, ldg, g_is_double, P1, self1, P2, self2, hyp, workspace, &slab, &partials,
+                                         &TB))
         return rc;
     float* cs = (float*)((char*)workspace + a.cs_off);
     float* E = (float*)((char*)workspace + a.e_off);
@@ -398,6 +329,6 @@ extern "C" int dsvgp_kernel_bwd_ard(dsvgp_ctx* ctx, const void* G, int64_t ldg, 
                                     const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
                                     const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell,
                                     float* d_hyp, void* workspace) {
-    return kernel_bwd_ard_family(ctx, 0, G, ldg, g_is_double, P1, self1, vnorm1, n1, p1, P2, self2, n2, p2, d, ell, hyp, symmetric, d_x1,
-                                 d_v1, d_ell, d_hyp, workspace);
+    return kernel_bwd_ard_family(ctx, launch_kernel_bwd_tbar_rbf, G, ldg, g_is_double, P1, self1, vnorm1, n1, p1, P2, self2, n2, p2, d, ell,
+                                 hyp, symmetric, d_x1, d_v1, d_ell, d_hyp, workspace);
 }

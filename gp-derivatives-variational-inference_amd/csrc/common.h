@@ -145,30 +145,8 @@ size_t kernel_bwd_wide_workspace(int n1q, int n2q, int q, int NP);
 int launch_kernel_bwd_wide(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1q,
                            const float* P2, const float* self2, int n2q, int q, int K4, int DP, int NP, const float* hyp, void* workspace,
                            float** slab, int* ns, float** partials, int* nparts);
-// the tile and contraction launches of dsvgp_kernel_bwd_rect (assemble_wide.hip) for the ARD backward's own points reduction
-// (assemble_ard.hip): plan (workspace bytes, slab count; DSVGP_EINVAL as dsvgp_kernel_bwd_rect_workspace_bytes returns 0) and launch --
-// slab[ns][n1q][NP], partials[nparts][2] and the Tbar matrix TB[n1q][n2q], all inside `workspace`
-int kernel_bwd_rect_tiles_plan(int n1, int p1, int n2, int p2, int d, size_t* bytes, int* ns);
-int launch_kernel_bwd_rect_tiles(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1, int n1,
-                                 int p1, const float* P2, const float* self2, int n2, int p2, int d, const float* hyp, void* workspace,
-                                 float** slab, int* ns, float** partials, int* nparts, float** TB);
-// those tiles and that contraction for another kernel family's tile kernels (assemble_matern.hip).  kernel_rect_tiles_geometry: the
-// forward's tiles (backward = false) or the rectangular backward's capped tiles with its slab cut and the float counts of the workspace
-// pieces slab | partials | TB; DSVGP_EINVAL where dsvgp_kernel_fwd_rect / dsvgp_kernel_bwd_rect_workspace_bytes refuse.
-// launch_kernel_bwd_contract: launch 2 of the rectangular backward on that geometry.
-struct RectTilesGeom { int q1, q2, n1q, n2q, K4, DP, NP, Rr, Rc, gx, gy, ns, kper, nparts; size_t lds_fwd, lds_tbar, slab_f, part_f; };
-int kernel_rect_tiles_geometry(int n1, int p1, int n2, int p2, int d, bool backward, RectTilesGeom* g);
-int launch_kernel_bwd_contract(hipStream_t st, const float* TB, const RectTilesGeom& g, const float* P2, float* slab);
-// Matern-5/2 tile kernels (assemble_matern.hip) with launch_kernel_bwd_rect_tiles' contract: Tbar tiles, then the contraction above.
-// partials[2 j] holds the tile's sum(G o K) / s, partials[2 j + 1] zero (no scalar lengthscale: Matern runs on ARD packs)
-int launch_kernel_bwd_matern52_tiles(hipStream_t st, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
-                                     int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d, const float* hyp,
-                                     void* workspace, float** slab, int* ns, float** partials, int* nparts, float** TB);
-// dsvgp_kernel_bwd_ard's body (assemble_ard.hip) with the tile kernels of a family: 0 = RBF (launch_kernel_bwd_rect_tiles), 1 = Matern-5/2
-int kernel_bwd_ard_family(dsvgp_ctx* ctx, int family, const void* G, int64_t ldg, int g_is_double, const float* P1, const float* self1,
-                          const float* vnorm1, int n1, int p1, const float* P2, const float* self2, int n2, int p2, int d,
-                          const float* ell, const float* hyp, int symmetric, float* d_x1, float* d_v1, float* d_ell, float* d_hyp,
-                          void* workspace);
+// (what assemble_wide.hip, assemble_ard.hip and assemble_matern.hip share among themselves -- the tile plan, the family-templated tile
+// kernels and their launchers -- is in tiled_assembly.h)
 // the points launch of the kernel backwards (assemble.hip: finish_points) for side 1's geometry (d, p): d_x1 / d_v1 / d_hyp[0..1] +=
 int kernel_bwd_finish_points(dsvgp_ctx* ctx, int d, int p, const float* slab, int ns, const float* P1, const float* vnorm1, int n1,
                              const float* hyp, float sym, float* d_x1, float* d_v1, const float* partials, int nparts, float* d_hyp);

@@ -53,11 +53,12 @@ def test_workspace_bytes_are_the_ard_backwards_rounded_to_16(dsvgp):
 
 def test_forward_lds_stays_inside_a_workgroup_for_every_direction_count(dsvgp):
     """the forward keeps three pair values per point pair: its dynamic LDS over all q1, q2 <= 96, in a host computation.  The Tbar launch
-    adds no array to the RBF launch's (at most 117372 bytes, csrc/assemble_wide.hip)."""
+    adds no array to the RBF launch's (at most 117372 bytes, csrc/assemble_wide.hip).  The worst case is pinned: 47424 bytes at 2 x 1, the
+    RBF forward's bytes there plus two more pair arrays of Rr x Rc = 24 x 96 floats."""
     lds = dsvgp._lib.lib.dsvgp_kernel_fwd_matern52_lds_bytes
     worst = max((int(lds(p1, p2)), p1 + 1, p2 + 1) for p1 in range(96) for p2 in range(96))
     print("[parity] Matern forward LDS: at most %d bytes, at q1 x q2 = %d x %d" % worst)
-    assert 0 < worst[0] <= 65536
+    assert worst == (47424, 2, 1)
     assert lds(96, 0) == 0 and lds(0, 96) == 0 and lds(-1, 0) == 0
 
 

@@ -1,20 +1,31 @@
 #!/usr/bin/env python3
 """Compare two assembly listings of one translation unit function by function.
 
-    python tools/isa_diff.py OLD.s NEW.s [--resources OLD.txt NEW.txt]
+    python tools/isa_diff.py OLD.s NEW.s [--resources OLD.txt NEW.txt] [--rename OLDSYM=NEWSYM ...]
 
 OLD.s / NEW.s: hipcc <the flags of build_ext.py> --cuda-device-only -S (or --cuda-host-only -S).  A function is the text from
 its `.type NAME,@function` to its `.Lfunc_end`, plus its `.amdhsa_kernel NAME` block.  Prints one line per file pair and the
 names that differ or exist on one side only.  --resources: the stderr of -Rpass-analysis=kernel-resource-usage of both builds;
-the resource lines of every differing kernel are printed side by side.
+the resource lines of every differing kernel are printed side by side.  --rename: a kernel that changed its symbol (a template argument
+more, another name) is compared under its new one -- every occurrence of OLDSYM in OLD.s and OLD.txt is read as NEWSYM.
 """
 import re
 import sys
 
 
-def functions(path):
-    out, name, kern = {}, None, None
+RENAMES = []
+
+
+def lines(path):
     for line in open(path):
+        for old, new in RENAMES:
+            line = line.replace(old, new)
+        yield line
+
+
+def functions(path, renamed=False):
+    out, name, kern = {}, None, None
+    for line in (lines(path) if renamed else open(path)):
         m = re.match(r"\s*\.type\s+([^,\s]+),@function", line)
         if m:
             name = m.group(1)
@@ -38,9 +49,9 @@ def functions(path):
     return {k: norm("".join(v)) for k, v in out.items()}
 
 
-def resources(path):
+def resources(path, renamed=False):
     out, name = {}, None
-    for line in open(path):
+    for line in (lines(path) if renamed else open(path)):
         m = re.search(r"remark: Function Name: (\S+)", line)
         if m:
             name = m.group(1)
@@ -52,8 +63,12 @@ def resources(path):
 
 
 def main():
-    old, new = functions(sys.argv[1]), functions(sys.argv[2])
-    res = [resources(p) for p in sys.argv[4:6]] if "--resources" in sys.argv else None
+    while "--rename" in sys.argv:
+        i = sys.argv.index("--rename")
+        RENAMES.append(tuple(sys.argv[i + 1].split("=", 1)))
+        del sys.argv[i:i + 2]
+    old, new = functions(sys.argv[1], renamed=True), functions(sys.argv[2])
+    res = [resources(sys.argv[4], renamed=True), resources(sys.argv[5])] if "--resources" in sys.argv else None
     both = sorted(set(old) & set(new))
     differ = [k for k in both if old[k] != new[k]]
     print("%s: %d functions before, %d after, %d on both sides, %d identical, %d differ, %d removed, %d added"
