@@ -146,6 +146,7 @@ SIGNATURES = {
     "dsvgp_kernel_diag_matern52": (_i, [_p, _p, _i, _i, _i, _p, _p]),
     "dsvgp_kernel_diag_matern52_bwd": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "dsvgp_kernel_canon_supported": (_i, [_i, _i]),
+    "dsvgp_kernel_lds_bytes": (_z, [_i, _i, _i]),
     "dsvgp_kernel_canon2_supported": (_i, [_i, _i]),
     "dsvgp_kernel_fwd_canon2": (_i, [_p, _p, _i, _p, _i, _i, _i, _p, _i, _p, _f, _p, _l, _i]),
     "dsvgp_kernel_bwd_canon2": (_i, [_p, _p, _l, _i, _p, _p, _i, _p, _i, _i, _i, _p, _i, _p, _i, _p, _p, _p, _p]),

@@ -19,22 +19,12 @@
 // The "without the stores / the MFMA product / the loads" figures quoted below came from timing-ablation builds (wrong results by
 // construction: ASM_ABLATE, FWDP_ABL, BWD_ABLATE, PAIR_ABLATE, BWDS_ABL, CAN_ABL); removed in the build-variant clean-up; last present in 8a953b7.
 #include "common.h"
-#include <type_traits>
-
-// One-wave workgroups (64 threads) exchange through LDS, which serves a wave's instructions in issue order: all they need between a write
-// and another lane's read is that the COMPILER keeps the order.  __syncthreads() would add "s_waitcnt vmcnt(0)" (its fence covers global
-// memory too), i.e. drain the tile's global stores and the next tile's prefetch at every exchange (profiles/r06_c_*).
-#define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); \
-                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
-
+#include "wave_tile.h"      // the one-wave 48 x 48 scheme of the pair, split and canon kernels: WAVE_SYNC, f4, the shared parts
 
 namespace {
 
 constexpr int TMAX = 96;   // tile rows/cols of the interleaved matrix handled per workgroup
 constexpr int LDT = 100;   // LDS row stride of the T / G tiles (100 % 32 == 4 -> acc writes conflict-free per half)
-
-
-using f4 = float __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int fdiv_small(int e, float inv) { return (int)(((float)e + 0.5f) * inv); }
 
@@ -300,7 +290,6 @@ __global__ __launch_bounds__(256) void kernel_fwd_kernel(const float* __restrict
 // T'[r0, cb] = w_b, T'[ra, c0] = -u_a) goes MFMA -> LDS -> registers, every lane turns the Q x Q values of its point
 // pair(s) into the kernel micro-block with one exp and writes it straight to HBM in the interleaved layout.
 // ~15 KB of LDS per wave: 8 waves per CU overlap each other's staging, MFMA and store phases.
-constexpr int FWD_PAIR_LDT = 52;
 #ifndef FWD_PAIR_WGS_
 #define FWD_PAIR_WGS_ (256 * 16)      // probed 4 / 6 / 8 / 12 / 16 / 32 per CU: 207 / 170 / 137 / 133 / 121 / 135 us for K_ZX at C4
 #endif
@@ -327,87 +316,32 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
     constexpr int LDT2 = FWD_PAIR_LDT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LDP = K4 + 5;
-    float* P2s = smem;                  // [48][LDP]   (P1' has no image: the A fragments of the wave's 48 rows stay in registers)
-    float* TT = P2s;                    // [48][LDT2]  T' overlays the P2 image: it is written once every P2 fragment is in registers
+    const FwdPairLds L(K4);
+    float* P2s = smem + L.p2;           // [48][LDP]   (P1' has no image: the A fragments of the wave's 48 rows stay in registers)
+    float* TT = smem + L.tt;            // [48][LDT2]  T' overlays the P2 image: it is written once every P2 fragment is in registers
     const int lane = threadIdx.x, m16 = lane & 15, kg = lane >> 4;
     const int row0 = blockIdx.y * T;
     const int ncoltiles = (n2q + T - 1) / T;
     const int KS = K4 / 4 + 1;
-    const int pch = DP / 4;
     const float ell = hyp[0], s = hyp[1];
     const float il = 1.f / ell, il2 = il * il;
 
-    float areg[3][KSM];                 // A fragments: areg[i][ks] = P1'[row0 + 16 i + m16][4 ks + kg]  (KS <= KSM since DP <= 4 KSM)
+    float areg[3][KSM];
     for (int e = lane; e < 48 * LDP; e += 64) P2s[e] = 0.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int gr = row0 + i * 16 + m16;
-        const bool ok = gr < n1q;
-        const int a = (i * 16 + m16) % Q;
-        const float sf = ok ? self1[gr] : 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KSM; ++ks) {
-            float v = 0.f;
-            if (ks < K4 / 4) v = ok ? P1[(int64_t)gr * DP + ks * 4 + kg] : 0.f;
-            else if (ks == K4 / 4 && ok) v = (kg == 1) ? (a == 0 ? 1.f : 0.f) : ((kg == 2) ? (a == 0 ? 0.f : -sf) : 0.f);
-            areg[i][ks] = v;
-        }
-    }
+    load_a_fragments<Q, KSM>(areg, P1, self1, row0, n1q, K4, DP, m16, kg);
     int pr0[PPL], pc0[PPL];
     float s1r0[PPL];
     bool prow[PPL];
-#pragma unroll
-    for (int pp = 0; pp < PPL; ++pp) {
-        const int pid = lane + 64 * pp;
-        const int pi = pid / R, pj = pid - pi * R;
-        pr0[pp] = pi * Q; pc0[pp] = pj * Q;
-        prow[pp] = pid < NPAIR && row0 + pr0[pp] < n1q;
-        s1r0[pp] = prow[pp] ? self1[row0 + pr0[pp]] : 0.f;
-    }
-
-    constexpr int NPFP = (48 * KSM + 63) / 64;     // float4 per lane of one prefetched P2 tile (DP <= 4 KSM)
-    f4 pf[NPFP];
-    float pselfv = 0.f;
-    // The packed rows of a column tile are ONE contiguous piece of P2 (T rows of DP floats): float4 number e = lane + 64 u of it
-    // goes to row e / pch of the LDS image.  Per-lane constants: the element index (clamped to the tile for the lanes past its
-    // end) and the LDS offset (those lanes write to a scratch row behind the image) -- a tile that lies inside the matrix is then
-    // fetched and staged without a single predicate (the guarded form below spends ~15 instructions per float4 on masks, zero
-    // fills and 64-bit address arithmetic: PMC, profiles/r03_c_pmc_assemble_fwd_*.txt).
-    int pf_e[NPFP], pf_lds[NPFP];
-#pragma unroll
-    for (int u = 0; u < NPFP; ++u) {
-        const int e = lane + 64 * u;
-        const int ec = min(e, T * pch - 1);
-        const int r = ec / pch, k = (ec - r * pch) * 4;
-        pf_e[u] = ec;
-        pf_lds[u] = (e < T * pch ? r : 48) * LDP + k;
-    }
+    pair_geometry<Q>(pr0, pc0, prow, s1r0, self1, row0, n1q, lane);
+    Side2Stager<Q, KSM, true> stage(P2, self2, n2q, K4, DP, LDP, lane);     // the next tile's packed rows, in flight under the current tile
     const bool rows_full = row0 + T <= n1q;
-    auto prefetch = [&](int ct_) {
-        const int c0_ = ct_ * T;
-        if (c0_ + T <= n2q) {
-            const f4* src = reinterpret_cast<const f4*>(P2 + (int64_t)c0_ * DP);
-#pragma unroll
-            for (int u = 0; u < NPFP; ++u) pf[u] = src[pf_e[u]];
-            pselfv = -self2[c0_ + min(lane, T - 1)];
-            return;
-        }
-#pragma unroll
-        for (int u = 0; u < NPFP; ++u) {
-            const int e = lane + 64 * u;
-            const int r = e / pch, k = (e - r * pch) * 4;
-            pf[u] = f4{0.f, 0.f, 0.f, 0.f};
-            if (e < T * pch && c0_ + r < n2q) pf[u] = *reinterpret_cast<const f4*>(P2 + (int64_t)(c0_ + r) * DP + k);
-        }
-        pselfv = (lane < T && c0_ + lane < n2q) ? -self2[c0_ + lane] : 0.f;
-    };
     // ovec bit 3 (the one-call steps' K_ZZ: ctx->fwd_lower_only): only the column tiles that reach into the 64 x 64 blocks on or below the block
     // diagonal of this row tile's rows -- what the blocked Cholesky factorisation reads
     const int ct_end = (ovec & 8) ? min(ncoltiles, (64 * ((row0 + T - 1) / 64) + 63) / T + 1) : ncoltiles;
     // consecutive column tiles per wave: the 192-byte row pieces of neighbouring tiles complete each other's 128-byte lines in ONE L2
     const int cper = (ct_end + (int)gridDim.x - 1) / (int)gridDim.x;
     const int ct_lo = blockIdx.x * cper, ct_hi = min(ct_lo + cper, ct_end), ct_step = 1;
-    if (ct_lo < ct_hi) prefetch(ct_lo);
+    if (ct_lo < ct_hi) stage.fetch(ct_lo);
     for (int ct = ct_lo; ct < ct_hi; ct += ct_step) {
         const int col0 = ct * T;
         float s2c0[PPL];
@@ -420,67 +354,16 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
             for (int pp = 0; pp < PPL; ++pp) s2c0[pp] = (prow[pp] && col0 + pc0[pp] < n2q) ? self2[col0 + pc0[pp]] : 0.f;
         }
         WAVE_SYNC();   // single wave: orders the previous tile's LDS reads before the new stores
-#pragma unroll
-        for (int u = 0; u < NPFP; ++u) {           // (lanes past the end of the tile: the scratch row behind the image)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) P2s[pf_lds[u] + t] = pf[u][t];
-        }
+        stage.store(P2s);
         WAVE_SYNC();
-        if (lane < T) {
-            P2s[lane * LDP + K4 + 1] = pselfv;
-            P2s[lane * LDP + K4 + 2] = (col0 + lane < n2q && lane % Q == 0) ? 1.f : 0.f;
-        }
-        if (ct + ct_step < ct_hi) prefetch(ct + ct_step);      // in flight under the rest of this tile
+        stage.extend(P2s, col0);
+        if (ct + ct_step < ct_hi) stage.fetch(ct + ct_step);      // in flight under the rest of this tile
         WAVE_SYNC();
         {
             f4 t[3][3];
-            const float* pb = P2s + m16 * LDP + kg;
-            // one straight-line copy per K depth: no per-step branches, the first product starts from the inline zero
-            auto product = [&](auto ksc) {
-                constexpr int KS_ = decltype(ksc)::value;
-#pragma unroll
-                for (int ks = 0; ks < KS_; ++ks) {
-                    float bv[3];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) bv[j] = pb[j * 16 * LDP + ks * 4];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j)
-                            t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv[j], ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i][j], 0, 0, 0);
-                }
-            };
-            switch (KS) {
-                case 1: product(std::integral_constant<int, 1>{}); break;
-                case 2: product(std::integral_constant<int, 2>{}); break;
-                case 3: product(std::integral_constant<int, 3>{}); break;
-                case 4: product(std::integral_constant<int, 4>{}); break;
-                case 5: product(std::integral_constant<int, 5>{}); break;
-                case 6: product(std::integral_constant<int, 6>{}); break;
-                case 7: product(std::integral_constant<int, 7>{}); break;
-                case 8: product(std::integral_constant<int, 8>{}); break;
-                default:
-                    if constexpr (KSM > 8) {
-                        switch (KS) {
-                            case 9: product(std::integral_constant<int, 9>{}); break;
-                            case 10: product(std::integral_constant<int, 10>{}); break;
-                            case 11: product(std::integral_constant<int, 11>{}); break;
-                            case 12: product(std::integral_constant<int, 12>{}); break;
-                            case 13: product(std::integral_constant<int, 13>{}); break;
-                            case 14: product(std::integral_constant<int, 14>{}); break;
-                            case 15: product(std::integral_constant<int, 15>{}); break;
-                            default: product(std::integral_constant<int, 16>{}); break;
-                        }
-                    } else product(std::integral_constant<int, 8>{});
-                    break;
-            }
+            tprime_product<KSM, 3>(t, areg, P2s + m16 * LDP + kg, LDP, KS);
             WAVE_SYNC();          // every P2 fragment has been read: T' may overlay the image
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) TT[(i * 16 + kg * 4 + r) * LDT2 + j * 16 + m16] = t[i][j][r];
+            store_tprime<LDT2>(TT, t, m16, kg);
         }
         WAVE_SYNC();
         // Interior tile, float output, 16-byte aligned rows: the micro-blocks go back to the T' tile IN PLACE (every lane rewrites
@@ -495,20 +378,9 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
                     if (lane + 64 * pp < NPAIR) {
                         float* blk = TT + pr0[pp] * LDT2 + pc0[pp];
                         float tq[Q][Q];
-#pragma unroll
-                        for (int a = 0; a < Q; ++a) {
-                            if constexpr (Q % 2 == 0) {
-                                using F2 = float __attribute__((ext_vector_type(2)));
-#pragma unroll
-                                for (int b = 0; b < Q; b += 2) {
-                                    const F2 v = *reinterpret_cast<const F2*>(blk + a * LDT2 + b);
-                                    tq[a][b] = v[0]; tq[a][b + 1] = v[1];
-                                }
-                            } else {
-#pragma unroll
-                                for (int b = 0; b < Q; ++b) tq[a][b] = blk[a * LDT2 + b];
-                            }
-                        }
+                        read_block<Q, LDT2>(tq, blk);
+                        // (RbfPair's arithmetic, kept as text: through RbfPair this path's <float, 3, 8> instance takes 12 more
+                        //  registers and drops from two waves per SIMD to one)
                         const float nn = fmaxf(s1r0[pp] - s2c0[pp] - 2.f * tq[0][0], 0.f);
                         const float k = s * expf(-0.5f * nn);
                         const float kil = k * il, kil2 = k * il2;
@@ -524,14 +396,7 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
 #pragma unroll
                                 for (int b = 1; b < Q; ++b) v[b] = (tq[a][b] + tq[a][0] * tq[0][b]) * kil2;
                             }
-                            if constexpr (Q % 2 == 0) {
-                                using F2 = float __attribute__((ext_vector_type(2)));
-#pragma unroll
-                                for (int b = 0; b < Q; b += 2) *reinterpret_cast<F2*>(blk + a * LDT2 + b) = F2{v[b], v[b + 1]};
-                            } else {
-#pragma unroll
-                                for (int b = 0; b < Q; ++b) blk[a * LDT2 + b] = v[b];
-                            }
+                            write_strip<Q>(blk + a * LDT2, v);
                         }
                     }
                 }
@@ -553,23 +418,8 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
             //  neighbouring lanes, which must not sit inside divergent control flow)
             const float* blk = TT + pr0[pp] * LDT2 + pc0[pp];
             float tq[Q][Q];
-#pragma unroll
-            for (int a = 0; a < Q; ++a) {
-                if constexpr (Q % 2 == 0) {
-                    using F2 = float __attribute__((ext_vector_type(2)));
-#pragma unroll
-                    for (int b = 0; b < Q; b += 2) {
-                        const F2 v = *reinterpret_cast<const F2*>(blk + a * LDT2 + b);
-                        tq[a][b] = v[0]; tq[a][b + 1] = v[1];
-                    }
-                } else {
-#pragma unroll
-                    for (int b = 0; b < Q; ++b) tq[a][b] = blk[a * LDT2 + b];
-                }
-            }
-            const float nn = fmaxf(s1r0[pp] - s2c0[pp] - 2.f * tq[0][0], 0.f);     // covar_dist clamps at 0
-            const float k = s * expf(-0.5f * nn);                                  // postprocess_rbf, ScaleKernel
-            const float kil = k * il, kil2 = k * il2;
+            read_block<Q, LDT2>(tq, blk);
+            const RbfPair rb(s1r0[pp], s2c0[pp], tq[0][0], s, il, il2);
             const int64_t gr0 = (int64_t)row0 + pr0[pp], gc0 = (int64_t)col0 + pc0[pp];
             OutT* o = out + gr0 * ld + gc0;
             // Q = 6, float: lanes 2j / 2j + 1 hold horizontally adjacent micro-blocks = 12 consecutive floats per row, 48-byte
@@ -584,15 +434,7 @@ __global__ __launch_bounds__(64, FWDP_MINW) void kernel_fwd_pair_kernel(const fl
 #pragma unroll
             for (int a = 0; a < Q; ++a) {
                 float v[Q];
-                if (a == 0) {
-                    v[0] = k;
-#pragma unroll
-                    for (int b = 1; b < Q; ++b) v[b] = tq[0][b] * kil;                          // w_b k / ell
-                } else {
-                    v[0] = tq[a][0] * kil;                                                      // -u_a k / ell
-#pragma unroll
-                    for (int b = 1; b < Q; ++b) v[b] = (tq[a][b] + tq[a][0] * tq[0][b]) * kil2;  // (G_ab - u_a w_b) k / ell^2
-                }
+                rb.fwd_row(v, a == 0, tq[a], tq[0]);
                 if (jitter != 0.f && gr0 == gc0) v[a] += jitter;      // diagonal micro-block: global row == global column
                 if constexpr (Q == 6 && sizeof(OutT) == 4) {
                     const float n0 = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v[0]), 0xB1, 0xF, 0xF, false));
@@ -639,30 +481,18 @@ __global__ __launch_bounds__(64) void kernel_fwd_split_kernel(const float* __res
     static_assert(NPAIR * SPL <= 64 && SPL >= 2 && T % 4 == 0, "split mapping: R^2 pairs x SPL lanes, 16-byte rows");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LDP = K4 + 5;
-    float* P2s = smem;                  // [49][LDP]  packed side-2 rows of the tile (+ a scratch row), overlaid by ...
-    float* TT = smem;                   // [48][LDT2] ... the T' tile once every B fragment is in registers
+    const FwdPairLds L(K4);
+    float* P2s = smem + L.p2;           // [49][LDP]  packed side-2 rows of the tile (+ a scratch row), overlaid by ...
+    float* TT = smem + L.tt;            // [48][LDT2] ... the T' tile once every B fragment is in registers
     const int lane = threadIdx.x, m16 = lane & 15, kg = lane >> 4;
     const int row0 = blockIdx.y * T;
     const int ncoltiles = (n2q + T - 1) / T;
-    const int KS = K4 / 4 + 1, pch = DP / 4;
+    const int KS = K4 / 4 + 1;
     const float ell = hyp[0], s = hyp[1];
     const float il = 1.f / ell, il2 = il * il;
 
     float areg[3][KSM];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int lr = i * 16 + m16, gr = row0 + lr;
-        const bool ok = lr < T && gr < n1q;
-        const int a = lr % Q;
-        const float sf = ok ? self1[gr] : 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KSM; ++ks) {
-            float v = 0.f;
-            if (ks < K4 / 4) v = ok ? P1[(int64_t)gr * DP + ks * 4 + kg] : 0.f;
-            else if (ks == K4 / 4 && ok) v = (kg == 1) ? (a == 0 ? 1.f : 0.f) : ((kg == 2) ? (a == 0 ? 0.f : -sf) : 0.f);
-            areg[i][ks] = v;
-        }
-    }
+    load_a_fragments<Q, KSM>(areg, P1, self1, row0, n1q, K4, DP, m16, kg);
     for (int e = lane; e < 49 * LDP; e += 64) P2s[e] = 0.f;
     // this lane's share of the tile: pair (pi, pj), rows a = sub + SPL i of its micro-block
     const int pid = lane / SPL, sub = lane - pid * SPL;
@@ -677,63 +507,23 @@ __global__ __launch_bounds__(64) void kernel_fwd_split_kernel(const float* __res
     const int ct_lo = blockIdx.x * cper, ct_hi = min(ct_lo + cper, ncoltiles);
     // the packed rows of a column tile are one contiguous piece of P2 (T rows of DP floats); the NEXT tile's travel through
     // registers under the current tile's transform and stores
-    constexpr int NPF = (T * KSM + 63) / 64;       // float4 per lane (pch <= KSM)
-    f4 pf[NPF];
-    float pselfv = 0.f;
-    auto prefetch = [&](int ct_) {
-        const int c0_ = ct_ * T;
-#pragma unroll
-        for (int u = 0; u < NPF; ++u) {
-            const int e = lane + 64 * u, r = e / pch, k = (e - r * pch) * 4;
-            pf[u] = f4{0.f, 0.f, 0.f, 0.f};
-            if (e < T * pch && c0_ + r < n2q) pf[u] = *reinterpret_cast<const f4*>(P2 + (int64_t)(c0_ + r) * DP + k);
-        }
-        pselfv = (lane < T && c0_ + lane < n2q) ? -self2[c0_ + lane] : 0.f;
-    };
-    if (ct_lo < ct_hi) prefetch(ct_lo);
+    Side2Stager<Q, KSM, false> stage(P2, self2, n2q, K4, DP, LDP, lane);
+    if (ct_lo < ct_hi) stage.fetch(ct_lo);
     for (int ct = ct_lo; ct < ct_hi; ++ct) {
         const int col0 = ct * T;
         const bool colok = prow && col0 + pc0 < n2q;
         const float s2c0 = colok ? self2[col0 + pc0] : 0.f;
         WAVE_SYNC();                 // (single wave: the previous tile's LDS reads are done)
-#pragma unroll
-        for (int u = 0; u < NPF; ++u) {
-            const int e = lane + 64 * u, r = e / pch, k = (e - r * pch) * 4;
-            if (e < T * pch) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) P2s[r * LDP + k + t] = pf[u][t];
-            }
-        }
+        stage.store(P2s);
         WAVE_SYNC();
-        if (lane < T) {
-            P2s[lane * LDP + K4 + 1] = pselfv;
-            P2s[lane * LDP + K4 + 2] = (col0 + lane < n2q && lane % Q == 0) ? 1.f : 0.f;
-        }
-        if (ct + 1 < ct_hi) prefetch(ct + 1);
+        stage.extend(P2s, col0);
+        if (ct + 1 < ct_hi) stage.fetch(ct + 1);
         WAVE_SYNC();
         {
             f4 t[3][3];
-            const float* pb = P2s + m16 * LDP + kg;
-#pragma unroll
-            for (int ks = 0; ks < KSM; ++ks) {
-                if (ks < KS) {
-                    float bv[3];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) bv[j] = pb[j * 16 * LDP + ks * 4];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j)
-                            t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv[j], ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i][j], 0, 0, 0);
-                }
-            }
+            tprime_product<KSM, 3, false>(t, areg, P2s + m16 * LDP + kg, LDP, KS);
             WAVE_SYNC();             // every B fragment has been read: T' may overlay the packed rows
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) TT[(i * 16 + kg * 4 + r) * LDT2 + j * 16 + m16] = t[i][j][r];
+            store_tprime<LDT2>(TT, t, m16, kg);
         }
         WAVE_SYNC();
         // ---- micro-block transform, rows split over the SPL lanes of a pair
@@ -750,24 +540,14 @@ __global__ __launch_bounds__(64) void kernel_fwd_split_kernel(const float* __res
             }
         }
         WAVE_SYNC();                 // row 0 is rewritten by the lane with sub = 0: every lane of the pair has read it
-        const float nn = fmaxf(s1r0 - s2c0 - 2.f * t0[0], 0.f);      // covar_dist clamps at 0
-        const float k = s * expf(-0.5f * nn);                          // postprocess_rbf, ScaleKernel
-        const float kil = k * il, kil2 = k * il2;
+        const RbfPair rb(s1r0, s2c0, t0[0], s, il, il2);
         const int64_t gr0 = (int64_t)row0 + pr0, gc0 = (int64_t)col0 + pc0;
         const bool fast = sizeof(OutT) == 4 && (ovec & 2) && rows_full && col0 + T <= n2q;     // (wave-uniform)
 #pragma unroll
         for (int i = 0; i < RPL; ++i) {
             const int a = sub + SPL * i;
             float v[Q];
-            if (a == 0) {
-                v[0] = k;
-#pragma unroll
-                for (int b = 1; b < Q; ++b) v[b] = t0[b] * kil;                                  // w_b k / ell
-            } else {
-                v[0] = ta[i][0] * kil;                                                           // -u_a k / ell
-#pragma unroll
-                for (int b = 1; b < Q; ++b) v[b] = (ta[i][b] + ta[i][0] * t0[b]) * kil2;         // (G_ab - u_a w_b) k / ell^2
-            }
+            rb.fwd_row(v, a == 0, ta[i], t0);
             if (jitter != 0.f && gr0 == gc0) {
 #pragma unroll
                 for (int b = 0; b < Q; ++b) if (b == a) v[b] += jitter;                          // diagonal of the diagonal micro-block
@@ -1123,7 +903,6 @@ __global__ __launch_bounds__(BWD_NT) void kernel_bwd_kernel(const GT* __restrict
 // so the transform reads nothing but its own 36 T' values.  The A fragments of the wave's 48 side-1 rows stay in registers for
 // the whole sweep (no LDS image of P1'), the T' product is one straight-line copy per K depth: ~16 KB of LDS per wave, 8 waves
 // per CU hide each other's LDS / HBM latency (K_ZX-bar at C4, whole dsvgp_kernel_bwd: 194 -> 157 us on one box).
-constexpr int PAIR_LDT = 52;     // LDS row stride of the 48 x 48 T' / Tbar tile (even: 8-byte strips)
 #ifndef PAIR_WGS_
 #define PAIR_WGS_ (256 * 8)       // 8 waves per CU (registers: 2 per SIMD; LDS: 16 KB per wave); 7 / 8 / 9 / 10 / 12: 169 / 157 / 262 / 246 / 225 us
 #endif
@@ -1148,87 +927,29 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
     constexpr int LDT2 = PAIR_LDT;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LDP = NP + 1;
-    // (the A fragments of the wave's 48 side-1 rows stay in registers for the whole sweep: no LDS image of P1')
-    float* P2s = smem;                  // [48][LDP]   extended side-2 packs of the current tile
-    float* TT = P2s + ((49 * LDP + 3) & ~3);      // [48][LDT2]  T', then Tbar in place (16-byte aligned: its 8-byte strips); row 48 of P2s: scratch of the predicate-free staging
+    const BwdPairLds L(NP, 0);
+    float* P2s = smem + L.p2;           // [48][LDP]   extended side-2 packs of the current tile (row 48: scratch of the predicate-free staging)
+    float* TT = smem + L.tt;            // [48][LDT2]  T', then Tbar in place (16-byte aligned: its 8-byte strips)
     const int lane = threadIdx.x, m16 = lane & 15, kg = lane >> 4;
     const int row0 = blockIdx.y * T;
     const int ncoltiles = (n2q + T - 1) / T;
     const int nnp = NP / 16;            // 1 .. KSM / 4
     constexpr int NNP = KSM / 4;
     const int KS = K4 / 4 + 1;
-    const int pch = DP / 4;
     const float ell = hyp[0], s = hyp[1];
     const float il = 1.f / ell, il2 = il * il;
     const bool vec = gvec != 0;
 
     for (int e = lane; e < 48 * LDP; e += 64) P2s[e] = 0.f;
-    float areg[3][KSM];                 // areg[i][ks] = P1'[row0 + 16 i + m16][4 ks + kg]  (KS <= KSM since DP <= 4 KSM)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int gr = row0 + i * 16 + m16;
-        const bool ok = i * 16 + m16 < T && gr < n1q;
-        const int a = (i * 16 + m16) % Q;
-        const float sf = ok ? self1[gr] : 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KSM; ++ks) {
-            float v = 0.f;
-            if (ks < K4 / 4) v = ok ? P1[(int64_t)gr * DP + ks * 4 + kg] : 0.f;
-            else if (ks == K4 / 4 && ok) v = (kg == 1) ? (a == 0 ? 1.f : 0.f) : ((kg == 2) ? (a == 0 ? 0.f : -sf) : 0.f);
-            areg[i][ks] = v;
-        }
-    }
-    // the packed rows of the NEXT column tile travel through registers under the current tile's work
-    constexpr int NPFP = (48 * KSM + 63) / 64;     // float4 per lane of one P2 tile (DP <= 4 KSM)
-    // (the packed rows of a column tile are one contiguous piece of P2: see kernel_fwd_pair_kernel)
-    int pf_r[NPFP], pf_k[NPFP], pf_e[NPFP], pf_lds[NPFP];
-#pragma unroll
-    for (int u = 0; u < NPFP; ++u) {
-        const int e = lane + 64 * u;
-        const int r = e / pch;
-        pf_r[u] = (e < T * pch) ? r : -1;
-        pf_k[u] = (e - r * pch) * 4;
-        const int ec = min(e, T * pch - 1), rc = ec / pch;
-        pf_e[u] = ec;
-        pf_lds[u] = (e < T * pch ? rc : 48) * LDP + (ec - rc * pch) * 4;
-    }
-    f4 pf[NPFP];
-    float pselfv = 0.f;
-    auto prefetch = [&](int ct_) {
-        const int c0_ = ct_ * T;
-        if (c0_ + T <= n2q) {               // a tile inside the matrix: no predicates
-            const f4* src = reinterpret_cast<const f4*>(P2 + (int64_t)c0_ * DP);
-#pragma unroll
-            for (int u = 0; u < NPFP; ++u) pf[u] = src[pf_e[u]];
-            pselfv = -self2[c0_ + min(lane, T - 1)];
-            return;
-        }
-#pragma unroll
-        for (int u = 0; u < NPFP; ++u) {
-            pf[u] = f4{0.f, 0.f, 0.f, 0.f};
-            if (pf_r[u] >= 0 && c0_ + pf_r[u] < n2q) pf[u] = *reinterpret_cast<const f4*>(P2 + (int64_t)(c0_ + pf_r[u]) * DP + pf_k[u]);
-        }
-        pselfv = (lane < T && c0_ + lane < n2q) ? -self2[c0_ + lane] : 0.f;
-    };
-
-    // lane-invariant pair geometry
+    float areg[3][KSM];
+    load_a_fragments<Q, KSM>(areg, P1, self1, row0, n1q, K4, DP, m16, kg);
+    Side2Stager<Q, KSM, true> stage(P2, self2, n2q, K4, DP, LDP, lane);
     int pr0[PPL], pc0[PPL];
     float s1r0[PPL];
     bool prow[PPL];
-#pragma unroll
-    for (int pp = 0; pp < PPL; ++pp) {
-        const int pid = lane + 64 * pp;
-        const int pi = pid / R, pj = pid - pi * R;
-        pr0[pp] = pi * Q; pc0[pp] = pj * Q;
-        prow[pp] = pid < NPAIR && row0 + pr0[pp] < n1q;
-        s1r0[pp] = prow[pp] ? self1[row0 + pr0[pp]] : 0.f;
-    }
-
+    pair_geometry<Q>(pr0, pc0, prow, s1r0, self1, row0, n1q, lane);
     f4 acc[3][NNP];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < NNP; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     float sK_sum = 0.f, l_acc = 0.f;
 
     for (int ct = blockIdx.x; ct < ncoltiles; ct += gridDim.x) {
@@ -1259,68 +980,16 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
             }
         }
         WAVE_SYNC();   // (single wave: orders the previous tile's MFMA reads of P2s / TT before the new stores)
-        prefetch(ct);
-#pragma unroll
-        for (int u = 0; u < NPFP; ++u) {               // (lanes past the end of the tile: the scratch row)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) P2s[pf_lds[u] + t] = pf[u][t];
-        }
+        stage.fetch(ct);
+        stage.store(P2s);
         WAVE_SYNC();   // the extension columns go on top of the packed zeros
-        if (lane < T) {
-            P2s[lane * LDP + K4 + 1] = pselfv;
-            P2s[lane * LDP + K4 + 2] = (col0 + lane < n2q && lane % Q == 0) ? 1.f : 0.f;
-        }
+        stage.extend(P2s, col0);
         WAVE_SYNC();
 
-        // T' = P1' P2'^T : 3 x 3 tiles of 16 x 16, K = K4 + 4  (one straight-line copy per K depth: no per-step branches, the
-        // first product starts from the inline zero)
-        {
+        {   // T' = P1' P2'^T : 3 x 3 tiles of 16 x 16, K = K4 + 4
             f4 t[3][3];
-            const float* pb = P2s + m16 * LDP + kg;
-            auto product = [&](auto ksc) {
-                constexpr int KS_ = decltype(ksc)::value;
-#pragma unroll
-                for (int ks = 0; ks < KS_; ++ks) {
-                    float bv[3];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) bv[j] = pb[j * 16 * LDP + ks * 4];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j)
-                            t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv[j], ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i][j], 0, 0, 0);
-                }
-            };
-            switch (KS) {
-                case 1: product(std::integral_constant<int, 1>{}); break;
-                case 2: product(std::integral_constant<int, 2>{}); break;
-                case 3: product(std::integral_constant<int, 3>{}); break;
-                case 4: product(std::integral_constant<int, 4>{}); break;
-                case 5: product(std::integral_constant<int, 5>{}); break;
-                case 6: product(std::integral_constant<int, 6>{}); break;
-                case 7: product(std::integral_constant<int, 7>{}); break;
-                case 8: product(std::integral_constant<int, 8>{}); break;
-                default:
-                    if constexpr (KSM > 8) {
-                        switch (KS) {
-                            case 9: product(std::integral_constant<int, 9>{}); break;
-                            case 10: product(std::integral_constant<int, 10>{}); break;
-                            case 11: product(std::integral_constant<int, 11>{}); break;
-                            case 12: product(std::integral_constant<int, 12>{}); break;
-                            case 13: product(std::integral_constant<int, 13>{}); break;
-                            case 14: product(std::integral_constant<int, 14>{}); break;
-                            case 15: product(std::integral_constant<int, 15>{}); break;
-                            default: product(std::integral_constant<int, 16>{}); break;
-                        }
-                    } else product(std::integral_constant<int, 8>{});
-                    break;
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) TT[(i * 16 + kg * 4 + r) * LDT2 + j * 16 + m16] = t[i][j][r];
+            tprime_product<KSM, 3>(t, areg, P2s + m16 * LDP + kg, LDP, KS);
+            store_tprime<LDT2>(TT, t, m16, kg);
         }
         WAVE_SYNC();
 
@@ -1330,20 +999,9 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
             if (lane + 64 * pp < NPAIR) {
                 float* blk = TT + pr0[pp] * LDT2 + pc0[pp];
                 float tq[Q][Q];
-#pragma unroll
-                for (int a = 0; a < Q; ++a) {
-                    if constexpr (Q % 2 == 0) {
-                        using F2 = float __attribute__((ext_vector_type(2)));
-#pragma unroll
-                        for (int b = 0; b < Q; b += 2) {
-                            const F2 v = *reinterpret_cast<const F2*>(blk + a * LDT2 + b);
-                            tq[a][b] = v[0]; tq[a][b + 1] = v[1];
-                        }
-                    } else {
-#pragma unroll
-                        for (int b = 0; b < Q; ++b) tq[a][b] = blk[a * LDT2 + b];
-                    }
-                }
+                read_block<Q, LDT2>(tq, blk);
+                // (RbfPair's arithmetic, kept as text: through RbfPair the compiler contracts the Q = 6 transform below into other
+                //  fused multiply-adds and dx, dv change in the last bits)
                 const float nn = fmaxf(s1r0[pp] - s2c0[pp] - 2.f * tq[0][0], 0.f);
                 const float k = s * expf(-0.5f * nn);
                 const float kil = k * il, kil2 = k * il2;
@@ -1400,49 +1058,11 @@ __global__ __launch_bounds__(64, KSM > 8 ? 1 : BWDP_MINW) void kernel_bwd_pair_k
         }
         WAVE_SYNC();
 
-        {   // dP1[48, NP] += Tbar[48, 48] . P2ext[48, NP]
-            const float* pa = TT + m16 * LDT2 + kg;
-            const float* pb = P2s + kg * LDP + m16;
-#pragma unroll
-            for (int kk = 0; kk < 48; kk += 4) {
-                float av[3], bv[NNP];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) av[i] = pa[i * 16 * LDT2 + kk];
-#pragma unroll
-                for (int j = 0; j < NNP; ++j) bv[j] = (j < nnp) ? pb[kk * LDP + 16 * j] : 0.f;
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-#pragma unroll
-                    for (int j = 0; j < NNP; ++j)
-                        if (j < nnp) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-                }
-            }
-        }
+        dp1_product(acc, TT, P2s, LDP, nnp, m16, kg);
     }
 
-    float* myslab = slab + ((int64_t)blockIdx.x * n1q) * NP;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < NNP; ++j)
-            if (j < nnp) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int rr = i * 16 + kg * 4 + r;
-                    const int64_t gr = row0 + rr;
-                    if (rr < T && gr < n1q) myslab[gr * NP + j * 16 + m16] = acc[i][j][r];
-                }
-            }
-    float l_sum = -il * l_acc;
-    for (int off = 32; off > 0; off >>= 1) {
-        sK_sum += __shfl_down(sK_sum, off);
-        l_sum += __shfl_down(l_sum, off);
-    }
-    if (lane == 0) {
-        const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-        partials[bid * 2] = sK_sum;
-        partials[bid * 2 + 1] = l_sum;
-    }
+    flush_slab<T>(acc, slab, row0, n1q, NP, nnp, m16, kg);
+    flush_partials(sK_sum, l_acc, il, partials, lane);
 }
 
 // ---- backward, "split" variant for wide micro-blocks (round 5; q = 11: BASELINE config 3) -----------------------------------------
@@ -1471,49 +1091,35 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
     static_assert(NPAIR * SPL == 64 && SPL == 4 && T % 4 == 0, "split mapping: R^2 pairs x 4 lanes (quad shuffles), 16-byte rows");
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LDP = NP + 1;
-    float* P2s = smem;                                   // [49][LDP]  extended side-2 packs of the tile
-    float* TT = P2s + ((49 * LDP + 3) & ~3);             // [48][LDT2] T', then Tbar in place
-    float* GG = TT + 48 * LDT2;                          // [T][LDG]   upstream tile
+    const BwdPairLds L(NP, T);
+    float* P2s = smem + L.p2;                            // [49][LDP]  extended side-2 packs of the tile
+    float* TT = smem + L.tt;                             // [48][LDT2] T', then Tbar in place
+    float* GG = smem + L.gg;                             // [T][LDG]   upstream tile
     const int lane = threadIdx.x, m16 = lane & 15, kg = lane >> 4;
     const int row0 = blockIdx.y * T;
     const int ncoltiles = (n2q + T - 1) / T;
-    const int nnp = NP / 16, KS = K4 / 4 + 1, pch = DP / 4;
+    const int nnp = NP / 16, KS = K4 / 4 + 1;
     const float ell = hyp[0], s = hyp[1];
     const float il = 1.f / ell, il2 = il * il;
 
     for (int e = lane; e < 49 * LDP; e += 64) P2s[e] = 0.f;
     for (int e = lane; e < 48 * LDT2; e += 64) TT[e] = 0.f;
     float areg[3][KSM];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int lr = i * 16 + m16, gr = row0 + lr;
-        const bool ok = lr < T && gr < n1q;
-        const int a = lr % Q;
-        const float sf = ok ? self1[gr] : 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KSM; ++ks) {
-            float v = 0.f;
-            if (ks < K4 / 4) v = ok ? P1[(int64_t)gr * DP + ks * 4 + kg] : 0.f;
-            else if (ks == K4 / 4 && ok) v = (kg == 1) ? (a == 0 ? 1.f : 0.f) : ((kg == 2) ? (a == 0 ? 0.f : -sf) : 0.f);
-            areg[i][ks] = v;
-        }
-    }
+    load_a_fragments<Q, KSM>(areg, P1, self1, row0, n1q, K4, DP, m16, kg);
     const int pid = lane / SPL, sub = lane - pid * SPL;
     const int pi = pid / R, pj = pid - pi * R;
     const int pr0 = pi * Q, pc0 = pj * Q;
     const bool prow = row0 + pr0 < n1q;
     const float s1r0 = prow ? self1[row0 + pr0] : 0.f;
     f4 acc[3][NNP];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < NNP; ++j) acc[i][j] = f4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     float sK_sum = 0.f, l_acc = 0.f;
     constexpr int C4 = T / 4;                              // 16-byte pieces per upstream tile row
 
     // the NEXT tile's upstream rows and packed side-2 rows travel through registers under the current tile's work
-    constexpr int NGF = (T * C4 + 63) / 64, NPF = (T * KSM + 63) / 64;
-    f4 gf[NGF], pf[NPF];
+    constexpr int NGF = (T * C4 + 63) / 64;
+    f4 gf[NGF];
+    Side2Stager<Q, KSM, false> stage(P2, self2, n2q, K4, DP, LDP, lane);
     auto prefetch = [&](int ct_) {
         const int c0_ = ct_ * T;
         const bool interior = row0 + T <= n1q && c0_ + T <= n2q;
@@ -1539,12 +1145,7 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
             }
             gf[u] = v;
         }
-#pragma unroll
-        for (int u = 0; u < NPF; ++u) {
-            const int e = lane + 64 * u, r = e / pch, k = (e - r * pch) * 4;
-            pf[u] = f4{0.f, 0.f, 0.f, 0.f};
-            if (e < T * pch && c0_ + r < n2q) pf[u] = *reinterpret_cast<const f4*>(P2 + (int64_t)(c0_ + r) * DP + k);
-        }
+        stage.fetch(ct_);
     };
     for (int ct = blockIdx.x; ct < ncoltiles; ct += gridDim.x) {
         const int col0 = ct * T;
@@ -1557,43 +1158,14 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
             const int id = lane + 64 * u, r = id / C4, c = (id - C4 * r) * 4;
             if (id < T * C4) *reinterpret_cast<f4*>(GG + r * LDG + c) = gf[u];
         }
-#pragma unroll
-        for (int u = 0; u < NPF; ++u) {
-            const int e = lane + 64 * u, r = e / pch, k = (e - r * pch) * 4;
-            if (e < T * pch) {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) P2s[r * LDP + k + t] = pf[u][t];
-            }
-        }
+        stage.store(P2s);
         WAVE_SYNC();
-        if (lane < T) {
-            const bool ok = col0 + lane < n2q;
-            P2s[lane * LDP + K4 + 1] = ok ? -self2[col0 + lane] : 0.f;
-            P2s[lane * LDP + K4 + 2] = (ok && lane % Q == 0) ? 1.f : 0.f;
-        }
+        stage.extend(P2s, col0);
         WAVE_SYNC();
         {   // T' = P1' P2'^T
             f4 t[3][3];
-            const float* pb = P2s + m16 * LDP + kg;
-#pragma unroll
-            for (int ks = 0; ks < KSM; ++ks) {
-                if (ks < KS) {
-                    float bv[3];
-#pragma unroll
-                    for (int j = 0; j < 3; ++j) bv[j] = pb[j * 16 * LDP + ks * 4];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-#pragma unroll
-                        for (int j = 0; j < 3; ++j)
-                            t[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv[j], ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i][j], 0, 0, 0);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-#pragma unroll
-                for (int j = 0; j < 3; ++j)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) TT[(i * 16 + kg * 4 + r) * LDT2 + j * 16 + m16] = t[i][j][r];
+            tprime_product<KSM, 3, false>(t, areg, P2s + m16 * LDP + kg, LDP, KS);
+            store_tprime<LDT2>(TT, t, m16, kg);
         }
         WAVE_SYNC();
         // ---- micro-block transform (kernel_bwd_pair_kernel's arithmetic), rows split over the four lanes of a pair
@@ -1612,9 +1184,8 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
             }
         }
         WAVE_SYNC();                                   // row 0 of the T' micro-block is rewritten below: every lane has read it
-        const float nn = fmaxf(s1r0 - s2c0 - 2.f * t0[0], 0.f);
-        const float k = s * expf(-0.5f * nn);
-        const float kil = k * il, kil2 = k * il2;
+        const RbfPair rb(s1r0, s2c0, t0[0], s, il, il2);
+        const float nn = rb.nn, k = rb.k, kil = rb.kil, kil2 = rb.kil2;
         float gu[Q];
 #pragma unroll
         for (int b = 0; b < Q; ++b) gu[b] = 0.f;
@@ -1664,47 +1235,10 @@ __global__ __launch_bounds__(64) void kernel_bwd_split_kernel(const GT* __restri
             l_acc += k * (e1 + 2.f * e2) - t00 * nn + dots;
         }
         WAVE_SYNC();
-        {   // dP1[48, NP] += Tbar[48, 48] . P2ext[48, NP]
-            const float* pa = TT + m16 * LDT2 + kg;
-            const float* pb = P2s + kg * LDP + m16;
-#pragma unroll
-            for (int kk = 0; kk < 48; kk += 4) {
-                float av[3], bv[NNP];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) av[i] = pa[i * 16 * LDT2 + kk];
-#pragma unroll
-                for (int j = 0; j < NNP; ++j) bv[j] = (j < nnp) ? pb[kk * LDP + 16 * j] : 0.f;
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-#pragma unroll
-                    for (int j = 0; j < NNP; ++j)
-                        if (j < nnp) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i], bv[j], acc[i][j], 0, 0, 0);
-            }
-        }
+        dp1_product(acc, TT, P2s, LDP, nnp, m16, kg);
     }
-    float* myslab = slab + ((int64_t)blockIdx.x * n1q) * NP;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < NNP; ++j)
-            if (j < nnp) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int rr = i * 16 + kg * 4 + r;
-                    const int64_t gr = row0 + rr;
-                    if (rr < T && gr < n1q) myslab[gr * NP + j * 16 + m16] = acc[i][j][r];
-                }
-            }
-    float l_sum = -il * l_acc;
-    for (int off = 32; off > 0; off >>= 1) {
-        sK_sum += __shfl_down(sK_sum, off);
-        l_sum += __shfl_down(l_sum, off);
-    }
-    if (lane == 0) {
-        const int bid = blockIdx.y * gridDim.x + blockIdx.x;
-        partials[bid * 2] = sK_sum;
-        partials[bid * 2 + 1] = l_sum;
-    }
+    flush_slab<T>(acc, slab, row0, n1q, NP, nnp, m16, kg);
+    flush_partials(sK_sum, l_acc, il, partials, lane);
 }
 
 // one 256-thread block per point: slabs -> d_x1, d_v1 (through the x/ell scaling and the direction normalisation).  Each of the
@@ -1970,22 +1504,32 @@ inline int finish_points(dsvgp_ctx* ctx, const Geom& g, const float* slab, int n
     return launch_points(ctx->stream, g, slab, ns, P1, vnorm1, n1, d, p, hyp, sym, d_x1, d_v1, partials, nparts, d_hyp);
 }
 
-inline bool bwd_use_pair(const Geom& g) { return (g.q == 6 || g.q == 3) && g.NP <= 64; }     // (NP <= 32: KSM = 8; <= 64: KSM = 16)
-inline bool bwd_use_split(const Geom& g) { return g.q == 11 && g.NP <= 16; }                  // (full-gradient SVGP at d <= 12: BASELINE config 3)
+// which forward / backward kernel a geometry takes
+inline bool use_pair(const Geom& g) { return (g.q == 6 || g.q == 3) && g.NP <= 64; }     // (NP <= 32: KSM = 8; <= 64: KSM = 16)
+inline bool use_split(const Geom& g) { return g.q == 11 && g.NP <= 16; }                  // (full-gradient SVGP at d <= 12, K4 <= 12: BASELINE config 3)
+// dynamic LDS of dsvgp_kernel_fwd's / dsvgp_kernel_bwd's launch (packed width <= 96)
+inline size_t fwd_lds(const Geom& g) {
+    if (use_split(g) || use_pair(g)) return sizeof(float) * (size_t)FwdPairLds(g.K4).floats;
+    const int Trp = (g.Tr + 15) & ~15, Tcp = (g.T + 15) & ~15;
+    return sizeof(float) * ((size_t)(Trp + Tcp) * (g.K4 + 1) + (size_t)Trp * LDT + Trp + Tcp + (size_t)g.Rr * g.R);
+}
+inline size_t bwd_lds(const Geom& g) {
+    if (use_split(g)) return sizeof(float) * (size_t)BwdPairLds(g.NP, (48 / g.q) * g.q).floats;
+    if (use_pair(g)) return sizeof(float) * (size_t)BwdPairLds(g.NP, 0).floats;
+    const int Trp = (g.Tr + 15) & ~15, Tcp = (g.T + 15) & ~15;
+    return sizeof(float) * ((size_t)Trp * (g.K4 + 1) + (size_t)Tcp * (g.NP + 1) + 2 * (size_t)Trp * LDT + Trp + Tcp +
+                            (size_t)g.Rr * g.R + 2 * (size_t)g.Tr * g.R + 2 * BWD_NW);
+}
 // row-tile height / column-tile width / workgroup budget of the backward variant that will run
 inline void bwd_tiles(const Geom& g, int& tr, int& tc, int& wgs) {
-    if (bwd_use_split(g)) { tr = tc = (48 / g.q) * g.q; wgs = BWDS_WGS; }
-    else if (bwd_use_pair(g)) { tr = tc = (48 / g.q) * g.q; wgs = PAIR_WGS; }
+    if (use_split(g)) { tr = tc = (48 / g.q) * g.q; wgs = BWDS_WGS; }
+    else if (use_pair(g)) { tr = tc = (48 / g.q) * g.q; wgs = PAIR_WGS; }
     else { tr = g.Tr; tc = g.T; wgs = BWD_TARGET_WGS; }
 }
 inline int bwd_nsplit(int n1, int n2, const Geom& g) {
     int tr, tc, wgs;
     bwd_tiles(g, tr, tc, wgs);
-    const int rt = cdiv((int64_t)n1 * g.q, tr), ctiles = cdiv((int64_t)n2 * g.q, tc);
-    int ns = wgs / rt;
-    if (ns < 1) ns = 1;
-    if (ns > ctiles) ns = ctiles;
-    return ns;
+    return sweep_nsplit(wgs, cdiv((int64_t)n1 * g.q, tr), cdiv((int64_t)n2 * g.q, tc));
 }
 
 template <typename GT, int Q, int NCH>
@@ -2023,7 +1567,6 @@ inline void dispatch_bwd(hipStream_t st, dim3 grid, size_t lds, const GT* G, int
 // q in {3, 6}, packed width <= 32 (d <= 28: BASELINE configs 2 and 4), float output / float or double upstream.
 // dir_idx[p] (device memory): coordinate of direction b is dir_idx[b] - idx_base.
 // =================================================================================================
-constexpr int CAN_LDT = 52;            // row stride of the 48 x 48 output / upstream tile in LDS (even: 8-byte strips; 16-byte aligned rows)
 #ifndef CAN_FWD_WGS
 #define CAN_FWD_WGS (256 * 32)          // (probed with the result NOT in the memory-side cache: 12 / 24 / 32 / 48 / 64 per CU: 88 / 75 / 75 / 83 / 90 us at C4)
 #endif
@@ -2049,8 +1592,9 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
     constexpr int R = 48 / Q, T = 48, PPL = CanTile<Q>::PPL, NPAIR = R * R, KSM = 8;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int LDX = K4 + 5;                 // row stride of the staged side-2 value rows [16][LDX]: columns K4 + 2 = 1, K4 + 3 = |x2~|^2
-    float* Xs = smem;                       // [16][LDX]
-    float* TT = smem + ((16 * LDX + 3) & ~3);     // [48][CAN_LDT]: U^T ([point][row], rows 0 .. R-1) first, then the output tile
+    const CanFwdLds L(K4);
+    float* Xs = smem + L.xs;                // [16][LDX]
+    float* TT = smem + L.tt;                // [48][CAN_LDT]: U^T ([point][row], rows 0 .. R-1) first, then the output tile
     const int lane = threadIdx.x, m16 = lane & 15, kg = lane >> 4;
     const int row0 = blockIdx.y * T;
     const int n2q = n2 * Q;
@@ -2064,20 +1608,7 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
     cidx[0] = 0;
 
     float areg[3][KSM];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        const int gr = row0 + i * 16 + m16;
-        const bool ok = gr < n1q;
-        const int a = (i * 16 + m16) % Q;
-        const float sf = ok ? self1[gr] : 0.f;
-#pragma unroll
-        for (int ks = 0; ks < KSM; ++ks) {
-            float v = 0.f;
-            if (ks < K4 / 4) v = ok ? P1[(int64_t)gr * DP + ks * 4 + kg] : 0.f;
-            else if (ks == K4 / 4 && ok) v = (kg == 2) ? (a == 0 ? 0.f : -sf) : 0.f;
-            areg[i][ks] = v;
-        }
-    }
+    load_a_fragments<Q, KSM, true>(areg, P1, self1, row0, n1q, K4, DP, m16, kg);
     // per-pair constants of side 1: |x1~|^2, x1~[c_b], v1_a[c_b]
     int pi_[PPL], pj_[PPL];
     bool prow[PPL];
@@ -2152,34 +1683,12 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
         prefetch(min(ct + ct_step, ncoltiles - 1)); // (unconditional: one harmless reload at the end of the range)
         WAVE_SYNC();
         // U = P1' X2'^T: 3 row tiles x (one 16-column tile of which R columns are points), K = K4 + 4
-        f4 t[3];
-        {
-            const float* pb = Xs + m16 * LDX + kg;
-            auto product = [&](auto ksc) {
-                constexpr int KS_ = decltype(ksc)::value;
-#pragma unroll
-                for (int ks = 0; ks < KS_; ++ks) {
-                    const float bv = pb[ks * 4];
-#pragma unroll
-                    for (int i = 0; i < 3; ++i)
-                        t[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(areg[i][ks], bv, ks == 0 ? f4{0.f, 0.f, 0.f, 0.f} : t[i], 0, 0, 0);
-                }
-            };
-            switch (KS) {
-                case 1: product(std::integral_constant<int, 1>{}); break;
-                case 2: product(std::integral_constant<int, 2>{}); break;
-                case 3: product(std::integral_constant<int, 3>{}); break;
-                case 4: product(std::integral_constant<int, 4>{}); break;
-                case 5: product(std::integral_constant<int, 5>{}); break;
-                case 6: product(std::integral_constant<int, 6>{}); break;
-                case 7: product(std::integral_constant<int, 7>{}); break;
-                default: product(std::integral_constant<int, 8>{}); break;
-            }
-        }
+        f4 t[3][1];
+        tprime_product<KSM, 1>(t, areg, Xs + m16 * LDX + kg, LDX, KS);
         // U^T -> LDS: lane (point m16, kg) holds rows 16 i + 4 kg .. + 3 of column m16: four consecutive floats of row m16 of [point][row]
         if (m16 < R) {
 #pragma unroll
-            for (int i = 0; i < 3; ++i) *reinterpret_cast<f4*>(TT + m16 * CAN_LDT + i * 16 + kg * 4) = t[i];
+            for (int i = 0; i < 3; ++i) *reinterpret_cast<f4*>(TT + m16 * CAN_LDT + i * 16 + kg * 4) = t[i][0];
         }
         WAVE_SYNC();
         float v[PPL][Q][Q];
@@ -2216,14 +1725,7 @@ __global__ __launch_bounds__(64, CAN_FWD_MINW) void kernel_fwd_canon_kernel(cons
                     float* blk = TT + pi_[pp] * Q * CAN_LDT + pj_[pp] * Q;
 #pragma unroll
                     for (int a = 0; a < Q; ++a) {
-                        if constexpr (Q % 2 == 0) {
-                            using F2 = float __attribute__((ext_vector_type(2)));
-#pragma unroll
-                            for (int b = 0; b < Q; b += 2) *reinterpret_cast<F2*>(blk + a * CAN_LDT + b) = F2{v[pp][a][b], v[pp][a][b + 1]};
-                        } else {
-#pragma unroll
-                            for (int b = 0; b < Q; ++b) blk[a * CAN_LDT + b] = v[pp][a][b];
-                        }
+                        write_strip<Q>(blk + a * CAN_LDT, v[pp][a]);
                     }
                 }
             }
@@ -2615,6 +2117,17 @@ extern "C" int dsvgp_kernel_canon_supported(int d, int p) {
     return canon_ok(g) ? 1 : 0;
 }
 
+// the dynamic LDS of the launch of dsvgp_kernel_fwd (0), dsvgp_kernel_bwd (1), dsvgp_kernel_fwd_canon (2), dsvgp_kernel_bwd_canon with the
+// upstream through registers (3) or by LDS-DMA (4): host arithmetic on the kernels' own layouts; 0: refused, or a packed width > 96
+extern "C" size_t dsvgp_kernel_lds_bytes(int d, int p, int launch) {
+    Geom g;
+    if (make_geom(d, p, g)) return 0;
+    if (launch == 0) return fwd_lds(g);
+    if (launch == 1) return bwd_lds(g);
+    if (launch < 2 || launch > 4 || !canon_ok(g)) return 0;
+    return sizeof(float) * (size_t)(launch == 2 ? CanFwdLds(g.K4).floats : CanBwdLds(g.NP, launch == 4).floats);
+}
+
 // K_ZX with canonical (one-hot) directions on side 2, shared by all its points: see the block comment above kernel_fwd_canon_kernel.
 // P2 / self2: the packed rows of side 2 as dsvgp_pack_points leaves them (only the value rows are read).  DSVGP_EINVAL for a geometry the
 // canonical kernels do not take (q not in {3, 6} or packed width > 32): the caller uses dsvgp_kernel_fwd.
@@ -2627,11 +2140,8 @@ extern "C" int dsvgp_kernel_fwd_canon(dsvgp_ctx* ctx, const float* P1, const flo
     if (n1 == 0 || n2 == 0) return 0;
     const int n1q = n1 * g.q, n2q = n2 * g.q, R = 48 / g.q;
     if (ld < n2q) return DSVGP_EINVAL;
-    const int rt = cdiv(n1q, 48), ctiles = cdiv(n2, R);
-    int ns = CAN_FWD_WGS / rt;
-    if (ns < 1) ns = 1;
-    if (ns > ctiles) ns = ctiles;
-    const size_t lds = sizeof(float) * (((16 * (size_t)(g.K4 + 5) + 3) & ~(size_t)3) + 48 * (size_t)CAN_LDT);
+    const int rt = cdiv(n1q, 48), ns = sweep_nsplit(CAN_FWD_WGS, rt, cdiv(n2, R));
+    const size_t lds = sizeof(float) * (size_t)CanFwdLds(g.K4).floats;
     const int ovec = ((ld % 4 == 0 && (uintptr_t)out % 16 == 0) ? 2 : 0) |
                      ((size_t)n1q * (size_t)n2 * g.q * sizeof(float) >= ((size_t)192 << 20) ? 4 : 0);      // (bit 2: non-temporal stores: a result larger than the memory-side cache is written once and read by the forward solve a millisecond later, whatever of it is cached by then -- cold result buffer: 77 -> 69 us at C4)
     dim3 grid(ns, rt);
@@ -2667,7 +2177,7 @@ extern "C" int dsvgp_kernel_bwd_canon(dsvgp_ctx* ctx, const void* G, int64_t ldg
     const int esz = g_is_double ? 8 : 4;
     const int gvec = (ldg % 2 == 0) && ((uintptr_t)G % (2 * esz) == 0);
     const bool dma = !g_is_double && ldg % 4 == 0 && (uintptr_t)G % 16 == 0;       // (16-byte pieces of the upstream rows)
-    const size_t lds = sizeof(float) * (((16 * (size_t)(g.NP + 1) + 3) & ~(size_t)3) + 16 * (size_t)CAN_LDT + 48 * 8 + (dma ? 48 * 48 : 0));
+    const size_t lds = sizeof(float) * (size_t)CanBwdLds(g.NP, dma).floats;
     dim3 grid(ns, rt);
 #define DSVGP_CANON_BWD(GT_, Q_, DMA_)                                                                                                  \
     hipLaunchKernelGGL((kernel_bwd_canon_kernel<GT_, Q_, DMA_>), grid, dim3(64), lds, ctx->stream, (const GT_*)G, ldg, P1, self1, n1q, P2, \
@@ -3113,56 +2623,35 @@ extern "C" int dsvgp_kernel_fwd(dsvgp_ctx* ctx, const float* P1, const float* se
     const int n1q = n1 * g.q, n2q = n2 * g.q;
     if (ld < n2q) return DSVGP_EINVAL;
     if (geom_wide(g)) return launch_kernel_fwd_tiled(ctx->stream, P1, self1, n1q, g.q, P2, self2, n2q, g.q, g.K4, g.DP, hyp, jitter, out, ld, out_is_double);
-    if (g.q == 11 && g.K4 <= 12) {      // full-gradient SVGP at d <= 12 (BASELINE config 3): the split-row kernel
-        const int T = 44;
-        const int rt = cdiv(n1q, T), ctiles = cdiv(n2q, T);
-        int ns = FWD_PAIR_WGS_ / rt;
-        if (ns < 1) ns = 1;
-        if (ns > ctiles) ns = ctiles;
-        const size_t p2w_ = 49 * (size_t)(g.K4 + 5), ttw_ = 48 * (size_t)FWD_PAIR_LDT;
-        const size_t lds = sizeof(float) * (p2w_ > ttw_ ? p2w_ : ttw_);
-        const int ovec = (!out_is_double && ld % 4 == 0 && (uintptr_t)out % 16 == 0) ? 2 : 0;
-        dim3 grid(ns, rt);
-        if (out_is_double)
-            hipLaunchKernelGGL((kernel_fwd_split_kernel<double, 11, 4>), grid, dim3(64), lds, ctx->stream, P1, self1, n1q, P2, self2, n2q,
-                               g.K4, g.DP, ovec, hyp, jitter, (double*)out, ld);
-        else
-            hipLaunchKernelGGL((kernel_fwd_split_kernel<float, 11, 4>), grid, dim3(64), lds, ctx->stream, P1, self1, n1q, P2, self2, n2q,
-                               g.K4, g.DP, ovec, hyp, jitter, (float*)out, ld);
-        DSVGP_LAUNCH_CHECK();
-        return 0;
-    }
-    if ((g.q == 6 || g.q == 3) && g.NP <= 64) {
+    const size_t lds = fwd_lds(g);
+    if (use_split(g) || use_pair(g)) {      // one wave per T x T tile, T = (48 / q) q; q = 11: the split-row kernel (full-gradient SVGP at d <= 12, BASELINE config 3)
         const int T = (48 / g.q) * g.q;
-        const int rt = cdiv(n1q, T), ctiles = cdiv(n2q, T);
-        int ns = FWD_PAIR_WGS_ / rt;
-        if (ns < 1) ns = 1;
-        if (ns > ctiles) ns = ctiles;
-        const size_t p2w_ = 49 * (size_t)(g.K4 + 5), ttw_ = 48 * (size_t)FWD_PAIR_LDT;        // (49: the scratch row of the predicate-free staging)
-        const size_t lds = sizeof(float) * (p2w_ > ttw_ ? p2w_ : ttw_);        // (T' overlays the P2 image)
+        const int rt = cdiv(n1q, T), ns = sweep_nsplit(FWD_PAIR_WGS_, rt, cdiv(n2q, T));
         const int esz = out_is_double ? 8 : 4;
-        // bit 0: 2-wide stores of the micro-block rows; bit 1: 16-byte stores of lane pairs (float output, 16-byte aligned rows)
-        const int ovec = (((ld % 2 == 0) && ((uintptr_t)out % (2 * esz) == 0)) ? 1 : 0) |
-                         ((!out_is_double && ld % 4 == 0 && (uintptr_t)out % 16 == 0) ? 2 : 0) |
-                         ((ctx->fwd_lower_only && P1 == P2 && n1 == n2) ? 8 : 0);       // (bit 3: the block triangle the Cholesky factorisation reads)
+        // bit 0: 2-wide stores of the micro-block rows; bit 1: 16-byte stores (float output, 16-byte aligned rows); bit 3: the block triangle the
+        // Cholesky factorisation reads (pair kernel only)
+        const int o16 = (!out_is_double && ld % 4 == 0 && (uintptr_t)out % 16 == 0) ? 2 : 0;
+        const int ovec = use_split(g) ? o16 : ((((ld % 2 == 0) && ((uintptr_t)out % (2 * esz) == 0)) ? 1 : 0) | o16 |
+                                               ((ctx->fwd_lower_only && P1 == P2 && n1 == n2) ? 8 : 0));
         dim3 grid(ns, rt);
-#define DSVGP_FWD_PAIR(OT_, Q_, KSM_)                                                                                \
-        hipLaunchKernelGGL((kernel_fwd_pair_kernel<OT_, Q_, KSM_>), grid, dim3(64), lds, ctx->stream, P1, self1, n1q, P2, self2, \
-                           n2q, g.K4, g.DP, ovec, hyp, jitter, (OT_*)out, ld)
-        if (g.NP <= 32) {
-            if (out_is_double) { if (g.q == 6) DSVGP_FWD_PAIR(double, 6, 8); else DSVGP_FWD_PAIR(double, 3, 8); }
-            else { if (g.q == 6) DSVGP_FWD_PAIR(float, 6, 8); else DSVGP_FWD_PAIR(float, 3, 8); }
+        if (use_split(g)) {
+            if (out_is_double)
+                hipLaunchKernelGGL((kernel_fwd_split_kernel<double, 11, 4>), grid, dim3(64), lds, ctx->stream, P1, self1, n1q, P2, self2, n2q,
+                                   g.K4, g.DP, ovec, hyp, jitter, (double*)out, ld);
+            else
+                hipLaunchKernelGGL((kernel_fwd_split_kernel<float, 11, 4>), grid, dim3(64), lds, ctx->stream, P1, self1, n1q, P2, self2, n2q,
+                                   g.K4, g.DP, ovec, hyp, jitter, (float*)out, ld);
         } else {
-            if (out_is_double) { if (g.q == 6) DSVGP_FWD_PAIR(double, 6, 16); else DSVGP_FWD_PAIR(double, 3, 16); }
-            else { if (g.q == 6) DSVGP_FWD_PAIR(float, 6, 16); else DSVGP_FWD_PAIR(float, 3, 16); }
+            pair_instance(out_is_double, g.q, g.NP, [&](auto et, auto qc, auto kc) {
+                using OT = decltype(et);
+                hipLaunchKernelGGL((kernel_fwd_pair_kernel<OT, decltype(qc)::value, decltype(kc)::value>), grid, dim3(64), lds, ctx->stream, P1,
+                                   self1, n1q, P2, self2, n2q, g.K4, g.DP, ovec, hyp, jitter, (OT*)out, ld);
+            });
         }
-#undef DSVGP_FWD_PAIR
         DSVGP_LAUNCH_CHECK();
         return 0;
     }
-    const int Rc = g.R, Rr = g.R >= 2 ? g.R / 2 : g.R;
-    const int Tr = Rr * g.q, Tc = Rc * g.q, Trp = (Tr + 15) & ~15, Tcp = (Tc + 15) & ~15;
-    const size_t lds = sizeof(float) * ((size_t)(Trp + Tcp) * (g.K4 + 1) + (size_t)Trp * LDT + Trp + Tcp + (size_t)Rr * Rc);
+    const int Rc = g.R, Rr = g.Rr, Tr = g.Tr, Tc = g.T;
     dim3 grid(cdiv(n2q, Tc), cdiv(n1q, Tr));
     (void)hipFuncSetAttribute((const void*)kernel_fwd_kernel<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute((const void*)kernel_fwd_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -3267,48 +2756,33 @@ extern "C" int dsvgp_kernel_bwd(dsvgp_ctx* ctx, const void* G, int64_t ldg, int 
     const int rt = cdiv(n1q, tr_);
     float* slab = (float*)workspace;
     float* partials = slab + (size_t)ns * n1q * g.NP;
-    if (bwd_use_split(g)) {
-        const size_t lds = sizeof(float) * (((49 * (size_t)(g.NP + 1) + 3) & ~(size_t)3) + 48 * (size_t)PAIR_LDT + 44 * (size_t)PAIR_LDT);
-        const int esz = g_is_double ? 8 : 4;
+    const size_t lds = bwd_lds(g);
+    const int esz = g_is_double ? 8 : 4;
+    dim3 grid(ns, rt);
+    if (use_split(g)) {
         const int gvec = (ldg % 4 == 0) && ((uintptr_t)G % (4 * esz) == 0);     // 4-wide loads of the upstream tile rows (tile origins are multiples of 44)
-        dim3 grid(ns, rt);
         if (g_is_double)
             hipLaunchKernelGGL((kernel_bwd_split_kernel<double, 11, 4>), grid, dim3(64), lds, ctx->stream, (const double*)G, ldg, P1, self1, n1q,
                                P2, self2, n2q, g.K4, g.DP, g.NP, gvec, hyp, slab, partials);
         else
             hipLaunchKernelGGL((kernel_bwd_split_kernel<float, 11, 4>), grid, dim3(64), lds, ctx->stream, (const float*)G, ldg, P1, self1, n1q,
                                P2, self2, n2q, g.K4, g.DP, g.NP, gvec, hyp, slab, partials);
-        DSVGP_LAUNCH_CHECK();
-    } else if (bwd_use_pair(g)) {
-        const size_t lds = sizeof(float) * (((49 * (size_t)(g.NP + 1) + 3) & ~(size_t)3) + 48 * (size_t)PAIR_LDT);      // (49: the scratch row of the predicate-free staging)
-        const int esz = g_is_double ? 8 : 4;
+    } else if (use_pair(g)) {
         const int gvec = (ldg % 2 == 0) && ((uintptr_t)G % (2 * esz) == 0);    // 2-wide loads of the micro-block rows
-        dim3 grid(ns, rt);
-#define DSVGP_PAIR_LAUNCH(GT_, Q_, KSM_)                                                                                \
-        hipLaunchKernelGGL((kernel_bwd_pair_kernel<GT_, Q_, KSM_>), grid, dim3(64), lds, ctx->stream, (const GT_*)G, ldg, P1, self1, \
-                           n1q, P2, self2, n2q, g.K4, g.DP, g.NP, gvec, hyp, slab, partials)
-        if (g.NP <= 32) {
-            if (g_is_double) { if (g.q == 6) DSVGP_PAIR_LAUNCH(double, 6, 8); else DSVGP_PAIR_LAUNCH(double, 3, 8); }
-            else { if (g.q == 6) DSVGP_PAIR_LAUNCH(float, 6, 8); else DSVGP_PAIR_LAUNCH(float, 3, 8); }
-        } else {
-            if (g_is_double) { if (g.q == 6) DSVGP_PAIR_LAUNCH(double, 6, 16); else DSVGP_PAIR_LAUNCH(double, 3, 16); }
-            else { if (g.q == 6) DSVGP_PAIR_LAUNCH(float, 6, 16); else DSVGP_PAIR_LAUNCH(float, 3, 16); }
-        }
-#undef DSVGP_PAIR_LAUNCH
-        DSVGP_LAUNCH_CHECK();
+        pair_instance(g_is_double, g.q, g.NP, [&](auto et, auto qc, auto kc) {
+            using GT = decltype(et);
+            hipLaunchKernelGGL((kernel_bwd_pair_kernel<GT, decltype(qc)::value, decltype(kc)::value>), grid, dim3(64), lds, ctx->stream,
+                               (const GT*)G, ldg, P1, self1, n1q, P2, self2, n2q, g.K4, g.DP, g.NP, gvec, hyp, slab, partials);
+        });
     } else {
-    const int Trp = (g.Tr + 15) & ~15, Tcp = (g.T + 15) & ~15;
-    const size_t lds = sizeof(float) * ((size_t)Trp * (g.K4 + 1) + (size_t)Tcp * (g.NP + 1) + 2 * (size_t)Trp * LDT + Trp + Tcp +
-                                        (size_t)g.Rr * g.R + 2 * (size_t)g.Tr * g.R + 2 * BWD_NW);
-    // 4-wide loads of the upstream tile need 4-element aligned tile origins and rows
-    const int gvec = (g.T % 4 == 0) && (ldg % 4 == 0) && ((uintptr_t)G % 32 == 0);
-    dim3 grid(ns, rt);
-    if (g_is_double)
-        dispatch_bwd<double>(ctx->stream, grid, lds, (const double*)G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);
-    else
-        dispatch_bwd<float>(ctx->stream, grid, lds, (const float*)G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);
-    DSVGP_LAUNCH_CHECK();
+        // 4-wide loads of the upstream tile need 4-element aligned tile origins and rows
+        const int gvec = (g.T % 4 == 0) && (ldg % 4 == 0) && ((uintptr_t)G % 32 == 0);
+        if (g_is_double)
+            dispatch_bwd<double>(ctx->stream, grid, lds, (const double*)G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);
+        else
+            dispatch_bwd<float>(ctx->stream, grid, lds, (const float*)G, ldg, P1, self1, n1q, P2, self2, n2q, g, gvec, hyp, slab, partials);
     }
+    DSVGP_LAUNCH_CHECK();
     const float sym = symmetric ? 2.f : 1.f;
     return finish_points(ctx, g, slab, ns, P1, vnorm1, n1, d, p, hyp, sym, d_x1, d_v1, (const float*)partials, ns * rt, d_hyp);
 }

@@ -247,6 +247,10 @@ int dsvgp_kernel_diag_matern52_bwd(dsvgp_ctx* ctx, const float* P, int n, int p,
                                    const float* out, const float* gbar, float* d_ell, float* d_hyp);
 /* 1 when dsvgp_kernel_fwd_canon / _bwd_canon take the geometry (d, p), 0 otherwise */
 int dsvgp_kernel_canon_supported(int d, int p);
+/* The dynamic LDS, in bytes, of the launch that dsvgp_kernel_fwd (launch = 0), dsvgp_kernel_bwd (1), dsvgp_kernel_fwd_canon (2) or
+ * dsvgp_kernel_bwd_canon (3: upstream through registers, 4: float upstream by LDS-DMA) makes at (d, p): host arithmetic on the kernels'
+ * own LDS layouts.  0: a geometry the entry refuses, or a packed width > 96 (the wide-input kernels).                                */
+size_t dsvgp_kernel_lds_bytes(int d, int p, int launch);
 /* backward of dsvgp_kernel_fwd_canon (symmetric = 0 semantics; same workspace size as dsvgp_kernel_bwd) */
 int dsvgp_kernel_bwd_canon(dsvgp_ctx* ctx, const void* G, int64_t ldg, int g_is_double, const float* P1,
                            const float* self1, const float* vnorm1, int n1, const float* P2,

@@ -17,7 +17,11 @@ lengthscale of 0.7 (1 / ell is not 1), the ARD and Matern entries on ARD packs.
 Shapes (n1, p1, n2, p2, d): the smallest at which each shared part of the kernels can go wrong -- ragged tiles, a split contraction,
 p1 = 0 and p2 = 0, 1 x 1 micro-blocks with several column tiles, duplicate points (nn == 0 off the diagonal: the Matern f3 guard), q1 = 96
 (Rr = 1) with the backward's column cap at q1 >= 52, the cap at q1 <= 4 (Rc = 69 at 1 x 1), seven K chunks with K4 no multiple of 32, the
-wide K_ZZ, one point."""
+wide K_ZZ, one point.
+
+--narrow --dump runs a second entry list instead: dsvgp_kernel_fwd / _bwd on the pair and split kernels and dsvgp_kernel_fwd_canon /
+_bwd_canon (csrc/wave_tile.h) at every K depth of the T' product, on ragged, full and single tiles, float and double outputs and
+upstreams, 16-byte aligned rows and rows that are not, K_ZZ with jitter and the symmetric backward (NARROW_DP, NARROW_TILES below)."""
 import argparse
 import math
 import os
@@ -110,16 +114,88 @@ def run_shape(ops, ctx, dev, shape, duplicates, res):
         keep("kernel_diag_%s and its backward" % fam, out, dl, dh)
 
 
-def dump(path):
+# ---- the second entry list (--narrow): the one-wave 48 x 48 kernels of csrc/assemble.hip on csrc/wave_tile.h --------------------------
+# dsvgp_kernel_fwd / _bwd (pair kernels at q = 3, 6; split kernels at q = 11) and dsvgp_kernel_fwd_canon / _bwd_canon.  (d, p): every K
+# depth of the T' product's dispatch -- KSM = 8 (d <= 28, also through the canon entries), KSM = 16 (d <= 60) -- and the split kernels.
+# (n1, n2): one tile smaller than 48 rows, exactly one full tile (R = 48 / q points), full tiles plus a ragged last row and column tile.
+NARROW_DP = [(d, p) for d in (2, 5, 9, 13, 17, 20, 25, 28, 29, 40, 50, 60) for p in (2, 5)] + [(10, 10), (7, 10)]
+NARROW_FULL = {(20, 5), (5, 2), (50, 5), (40, 2), (10, 10), (7, 10)}      # every tile shape; the others: the first two and the full tile
+NARROW_TILES = [(3, 5), (33, 70), (50, 131), (9, 300)]
+
+
+def padded(rows, cols, dtype, dev, aligned):
+    """a [rows, cols] view: 16-byte aligned rows with ld % 4 == 0, or rows that are not (ld = cols + 3, offset 1)"""
+    if aligned:
+        return torch.zeros(rows, (cols + 3) // 4 * 4 + 4, dtype=dtype, device=dev)[:, :cols]
+    return torch.zeros(rows, cols + 3, dtype=dtype, device=dev)[:, 1:1 + cols]
+
+
+def run_narrow(ops, ctx, dev, d, p, n1, n2, res):
+    q = p + 1
+    tag = "d%d-p%d-%dx%d" % (d, p, n1, n2)
+    g = torch.Generator().manual_seed(1000 * d + 100 * p + 7 * n1 + n2)
+    x1, v1 = torch.rand(n1, d, generator=g).to(dev), torch.randn(n1 * p, d, generator=g).to(dev)
+    x2, v2 = torch.rand(n2, d, generator=g).to(dev), torch.randn(n2 * p, d, generator=g).to(dev)
+    G64 = torch.randn(n1 * q, n2 * q, generator=g, dtype=torch.float64).to(dev)
+    S64 = torch.randn(n1 * q, n1 * q, generator=g, dtype=torch.float64).to(dev)
+    S64 = (S64 + S64.t()).contiguous()
+    hyp = torch.tensor([ELL, S, 0.1, 0.0], device=dev)
+    center = ops.column_mean(ctx, x1)
+    pk1, pk2 = ops.pack_points(ctx, x1, v1, p, hyp, center), ops.pack_points(ctx, x2, v2, p, hyp, center)
+
+    def keep(name, *tensors):
+        for i, t in enumerate(tensors):
+            res["%s %s [%d]" % (name, tag, i)] = t.detach().contiguous().cpu()
+
+    def grads():
+        return torch.zeros(n1, d, device=dev), torch.zeros(n1 * p, d, device=dev), torch.zeros(4, device=dev)
+
+    def upstream(G, aligned):
+        V = padded(G.shape[0], G.shape[1], G.dtype, dev, aligned)
+        V.copy_(G)
+        return V
+
+    for dtype in (torch.float32, torch.float64):
+        for aligned in (True, False):
+            out = padded(n1 * q, n2 * q, dtype, dev, aligned)
+            keep("kernel_fwd %s aligned %d" % (dtype, aligned), ops.kernel_fwd(ctx, pk1, n1, pk2, n2, d, p, hyp, out=out, dtype=dtype))
+        keep("kernel_fwd K_ZZ jitter %s" % dtype, ops.kernel_fwd(ctx, pk1, n1, pk1, n1, d, p, hyp, jitter=JITTER, dtype=dtype))
+    for G, sym in ((G64.float(), False), (G64, False), (upstream(G64.float(), False), False), (S64.float(), True), (S64, True)):
+        dx, dv, dh = grads()
+        ops.kernel_bwd(ctx, G, pk1, n1, pk1 if sym else pk2, n1 if sym else n2, d, p, hyp, sym, dx, dv, dh)
+        keep("kernel_bwd G %s ld %d sym %d" % (G.dtype, G.stride(0) - G.shape[1], sym), dx, dv, dh)
+    if not ops.canon_supported(d, p):
+        return
+    idx = (torch.arange(p, dtype=torch.int32) % d).to(dev)          # one-hot directions e_idx[b], the same for every point of side 2
+    e2 = torch.zeros(n2 * p, d, device=dev)
+    e2[torch.arange(n2 * p, device=dev), idx.long().repeat(n2)] = 1.0
+    ck2 = ops.pack_points(ctx, x2, e2, p, hyp, center)
+    for aligned in (True, False):
+        keep("kernel_fwd_canon aligned %d" % aligned,
+             ops.kernel_fwd_canon(ctx, pk1, n1, ck2, n2, d, p, idx, 0, hyp, out=padded(n1 * q, n2 * q, torch.float32, dev, aligned)))
+    for G in (upstream(G64.float(), True), upstream(G64.float(), False), G64):     # LDS-DMA, registers, double
+        dx, dv, dh = grads()
+        ops.kernel_bwd_canon(ctx, G, pk1, n1, ck2, n2, d, p, idx, 0, hyp, dx, dv, dh)
+        keep("kernel_bwd_canon G %s ld %d" % (G.dtype, G.stride(0) - G.shape[1]), dx, dv, dh)
+
+
+def dump(path, narrow=False):
     import dsvgp_amd
     assert torch.cuda.is_available(), "tiled_ab --dump needs the GPU"
     dev = torch.device("cuda", 0)
     ops = dsvgp_amd._ops
     ctx = ops.Context.get(dev)
     res = {}
-    for shape in SHAPES:
-        run_shape(ops, ctx, dev, shape, False, res)
-    run_shape(ops, ctx, dev, DUP, True, res)
+    if narrow:
+        for d, p in NARROW_DP:
+            R = 48 // (p + 1)
+            tiles = NARROW_TILES if (d, p) in NARROW_FULL else NARROW_TILES[:2]
+            for n1, n2 in tiles + [(R, R)]:
+                run_narrow(ops, ctx, dev, d, p, n1, n2, res)
+    else:
+        for shape in SHAPES:
+            run_shape(ops, ctx, dev, shape, False, res)
+        run_shape(ops, ctx, dev, DUP, True, res)
     torch.cuda.synchronize()
     torch.save(res, path)
     print("tiled_ab: %d output tensors of %s -> %s" % (len(res), dsvgp_amd._lib.LIB_PATH, path))
@@ -145,9 +221,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dump", metavar="FILE")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"))
+    ap.add_argument("--narrow", action="store_true", help="--dump the second entry list: the one-wave kernels of csrc/wave_tile.h")
     args = ap.parse_args()
     if args.dump:
-        dump(args.dump)
+        dump(args.dump, args.narrow)
     return compare(*args.compare) if args.compare else 0
 
 
