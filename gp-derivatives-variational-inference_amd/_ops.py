@@ -135,6 +135,10 @@ class StepPlan:
         flat = workspace[off.value:off.value + rows.value * ld.value * esz].view(dt)
         return flat.view(rows.value, ld.value)[:, :cols.value]
 
+    def clear_mode(self):
+        """clearing regime of the step queued last: 0 launchers, 1 one memset over the arena, 2 side-stream preclear (+ 4 with the Gram target)"""
+        return int(lib.dsvgp_elbo_step_clear_mode(self.h))
+
     def timed_count(self):
         return int(lib.dsvgp_elbo_step_timed_count(self.h))
 

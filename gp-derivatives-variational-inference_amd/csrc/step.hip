@@ -55,6 +55,7 @@ struct dsvgp_step_plan {
     size_t o_PZ, o_sZ, o_vZ, o_PX, o_sX, o_vX;
     size_t o_phi32 = 0; bool phi32_own = false;
     bool precleared_ge = false;
+    bool prezeroed = false;                   // the step queued last cleared its whole arena with one memset (dsvgp_elbo_step_clear_mode)
     bool precleared = false;                  // this step's targets of the main stream's split-K / OUT_LOWER products were cleared on the side stream (step_front)
     size_t o_L, o_trsm, o_potrf, o_Kzx, o_A32e, o_S32e, o_var0, o_stats, o_Ge, o_Qe64, o_S64e, o_Qe32, o_Kb32, o_G1, o_Yt, o_Kbar, o_kbwd, o_kbwd2;
     size_t o_arena, arena_bytes;     // contiguous region of everything a launcher would clear (see step_layout)
@@ -254,6 +255,12 @@ extern "C" int dsvgp_elbo_step_timings(dsvgp_step_plan* pl, int back, float* ms3
 extern "C" int dsvgp_elbo_step_timings5(dsvgp_step_plan* pl, int back, float* ms5) { return step_timings(pl, back, ms5, 5); }
 
 extern "C" size_t dsvgp_elbo_step_plan_bytes(const dsvgp_step_plan* pl) { return pl ? pl->bytes : 0; }
+// Who cleared the split-K / OUT_LOWER targets of the step queued last (step_front): 0 the launchers themselves, 1 the one memset over the
+// arena, 2 the side stream ahead of the products (+ 4: [tril(G) ; b^T] among them).  Read-only: for tests that must prove which regime ran.
+extern "C" int dsvgp_elbo_step_clear_mode(const dsvgp_step_plan* pl) {
+    if (!pl) return DSVGP_EINVAL;
+    return pl->prezeroed ? 1 : pl->precleared ? 2 + (pl->precleared_ge ? 4 : 0) : 0;
+}
 // number of steps queued with flag 4 so far (the step queued last with that flag has index count - 1: callers that keep an index
 // per step read its timings with back = count - 1 - index, whatever was queued in between)
 extern "C" long dsvgp_elbo_step_timed_count(const dsvgp_step_plan* pl) { return pl ? pl->timed_steps : 0; }
@@ -437,6 +444,7 @@ static int step_front(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const dsvgp_elbo_step
     static const bool preclear_env = !getenv("DSVGP_PRECLEAR") || atoi(getenv("DSVGP_PRECLEAR")) != 0;
     pl->precleared = preclear && preclear_env && overlap && !prezero && !ctx->det_slab && !(flags & (16 | 32 | 64));
     pl->precleared_ge = false;
+    pl->prezeroed = prezero;
     STEP_HIP(hipMemsetAsync(io->flat, 0, io->flat_floats * sizeof(float), main));
     if (prezero) STEP_HIP(hipMemsetAsync(w + pl->o_arena, 0, pl->arena_bytes, main));
     else STEP_HIP(hipMemsetAsync(w + pl->o_zero, 0, pl->zero_bytes, main));
@@ -839,6 +847,7 @@ extern "C" int dsvgp_elbo_step_po_f32(dsvgp_ctx* ctx, dsvgp_step_plan* pl, const
     float* mu_bar = A32e + (size_t)Mp * Bp;
     double* Lbar = Qe64;                                // [M', M'] fp64 (the fast path's [Q' | a] scratch)
     pl->timed = false;
+    pl->prezeroed = pl->precleared = pl->precleared_ge = false;     // (every launcher of this step clears for itself)
     struct PrezeroGuard {
         dsvgp_ctx* c; bool prev;
         PrezeroGuard(dsvgp_ctx* c_) : c(c_), prev(c_->prezeroed) { c->prezeroed = false; }

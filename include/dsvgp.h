@@ -683,6 +683,11 @@ size_t dsvgp_elbo_step_workspace_bytes(int M, int d, int p, int B);
 int dsvgp_elbo_step_plan_create(dsvgp_ctx* ctx, int M, int d, int p, int B, dsvgp_step_plan** out);
 int dsvgp_elbo_step_plan_destroy(dsvgp_step_plan* plan);
 size_t dsvgp_elbo_step_plan_bytes(const dsvgp_step_plan* plan);
+/* Which of its clearing regimes the step queued last on this plan used for its split-K / OUT_LOWER targets: 0 every launcher cleared
+ * its own target; 1 one memset over the whole arena at the start of the step (small problems); 2 the targets of the later products
+ * were cleared on the second stream at the start of the step (large problems with flag 1), + 4 when the Gram product's target
+ * was among them.  Read-only; 0 before the first step and after a per-output or data-parallel step.                            */
+int dsvgp_elbo_step_clear_mode(const dsvgp_step_plan* plan);
 int dsvgp_elbo_step_f32(dsvgp_ctx* ctx, dsvgp_step_plan* plan, const dsvgp_elbo_step_io* io, void* workspace,
                         size_t workspace_bytes, int flags);
 int dsvgp_elbo_step_status(dsvgp_step_plan* plan, float* hyp4, int* info);

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import dsvgp_oracle as O
+from _poison import poison_
 from test_gpu_fp64 import CASES, make_problem64, relmax
 
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "oracle"))
@@ -155,8 +156,8 @@ def test_fp64_one_call_step_reports_a_failed_factorisation(dsvgp, gpu_device):
 
 
 def test_fp64_one_call_step_plans_and_workspace(dsvgp, gpu_device):
-    """two steps on one plan and workspace with different minibatches; flag 8 after the workspace was overwritten; a ragged last batch
-    gets its own plan -- every result against the oracle"""
+    """two steps on one plan and workspace with different minibatches; flag 8 after the workspace was overwritten with NaN bytes; a
+    ragged last batch gets its own plan -- every result against the oracle"""
     N, d, M, p, B = 600, 5, 40, 2, 128
     P, x, y, D, nd = make_problem64(N, d, M, p, 2 * B + 37, seed=21)
     Pg = _to(P, gpu_device)
@@ -178,7 +179,7 @@ def test_fp64_one_call_step_plans_and_workspace(dsvgp, gpu_device):
     # the tensors of the last step: `held`, `grads`, `mu`, alive here)
     (plan,) = eng._plans.values()
     ws = eng._buf["cstep64_ws_%d_%d_%d_%d" % (M, d, p, B)]
-    ws.fill_(0xA5)
+    poison_(ws)                                 # (0xFF bytes: NaN as a double -- accumulating onto it, or reading it as padding, shows)
     grads["chol_variational_covar"].fill_(7.0)
     ctx = dsvgp._ops.Context.get(gpu_device)
     plan.run(ctx, ws, 1 | 2 | 8)
